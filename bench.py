@@ -15,9 +15,12 @@ every rank makes the same host -> host call.
          --master-port 29500 bench.py --gpus 8 --steps 300 --warmup 30
   python bench.py --gpus 8         # no torchrun around it: spawns the 8 ranks itself (fresh children)
 
-Timing: W warm-up steps, then --blocks (default 3) blocks of EXACTLY K steps, each bracketed by a
-barrier + torch.cuda.synchronize(); per block the MAX over ranks; `value` comes from the MEDIAN block
-(so a 20-step run is not a single 2 ms sample); all block times are in the line.
+Timing: W warm-up steps, a >= 0.35 s clock ramp, a barrier + torch.cuda.synchronize() and 8 settling steps (all
+untimed), then EXACTLY K timed steps (--steps), cut by the host clock into --blocks (default 3) blocks of near-equal
+size, and a barrier after the last; per block the MAX over ranks; `ms_per_step` and `value` come from the MEDIAN
+block's time per step (so one slow stretch does not set the figure); all block times are in the line.
+--dump-outputs DIR writes F and G of the last timed step to DIR/F.npy and DIR/G.npy (float64); the inputs are
+seeded, so two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0 (contract: see the task statement), including
   roofline      dominant kernel (sweep) against the 8 TB/s HBM peak with the ALGORITHMIC bytes of
@@ -25,11 +28,14 @@ Prints ONE JSON line on rank 0 (contract: see the task statement), including
                 inside the timed region (on the launch stream; every 8th launch carries the event pair,
                 GRAPE_FLAG_TIME_SAMPLED, because a pair costs ~5 us of the ~90 us call).  Also: the bytes/flops of the data
                 flow actually run (`flow`), the FP64 fraction, and the end-to-end fraction
-                (model S x value / peak, BASELINE.md section 2 formula);
+                (model S x value / peak, BASELINE.md section 2 formula).
+A plain run stops there.  --full also measures what takes runs of its own:
+  box           the clock the sweep kernel ran at (a stamped context right after the timed blocks);
   cpu_baseline  the C oracle (a port of the reference's serial algorithm) timed on this
-                host on a bounded member sample, rank 0 / N = 1 only;
+                host on a bounded member sample, + `parity` of those members, rank 0 / N = 1 only;
   extra         the device-resident pipelined loop (grape_eval_device back to back, what round 1
-                reported) for comparison;
+                reported) for comparison, L-BFGS rates, shard overheads and the scaling forecast;
+                N > 1: the weak-scaling and mailbox-exchange companions;
   extra_configs C2, C4 (E=1024), C5 (E=4096) host->host value + roofline on one GPU (N = 1 only).
 """
 import argparse
@@ -449,16 +455,39 @@ def clock_ramp(step, seconds=0.35, reduce_max=None):
     return probe + n
 
 
-def time_blocks(step, steps, blocks, barrier, reduce_max):
-    out = []
-    for _ in range(blocks):
-        barrier()
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            step()
-        barrier()
-        out.append(reduce_max(time.perf_counter() - t0))
-    return out
+def split_steps(steps, blocks):
+    """`steps` timed steps cut into min(blocks, steps) blocks of near-equal size: --steps is the number of steps timed."""
+    blocks = max(1, min(blocks, steps))
+    return [steps // blocks + (i < steps % blocks) for i in range(blocks)]
+
+
+def time_blocks(step, sizes, barrier, reduce_max, settle=0):
+    """Consecutive timed blocks of sizes[i] steps between a barrier before the first and one after the last; per block
+    the MAX over ranks.  Blocks are cut by the host clock alone: a step returns with its results in host memory, and a
+    barrier between blocks would drain the device work a step leaves behind (which the next step overlaps in a caller's
+    loop) and charge it, with the cold start that follows, to a short block.  `settle` untimed steps follow the first
+    barrier for the same reason (C3 on an MI355X: the first ~7 steps after it take 20-30 us more in all).  Also returns
+    what the last step returned."""
+    last = None
+    barrier()
+    for _ in range(settle):
+        step()
+    marks = [time.perf_counter()]
+    for i, n in enumerate(sizes):
+        for _ in range(n):
+            last = step()
+        if i == len(sizes) - 1:
+            barrier()
+        marks.append(time.perf_counter())
+    return [reduce_max(b - a) for a, b in zip(marks, marks[1:])], last
+
+
+def dump_outputs(path, F, G):
+    """What a caller of the timed step receives, from its last call: F as a (1,) array, G as (K, N), float64."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "F.npy"), np.array([F], dtype=np.float64))
+    np.save(os.path.join(path, "G.npy"), np.ascontiguousarray(G, dtype=np.float64))
 
 
 def run_extra_config(qoc, name, dev_index, steps, warmup):
@@ -804,9 +833,14 @@ def spawn_ranks(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=300)
+    ap.add_argument("--steps", type=int, default=300, help="timed steps")
     ap.add_argument("--warmup", type=int, default=30)
-    ap.add_argument("--blocks", type=int, default=3, help="timed blocks of --steps calls; value = median block")
+    ap.add_argument("--blocks", type=int, default=3, help="the timed steps are cut into this many blocks; value = median block")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: box clock, CPU baseline + parity, device-resident loop, "
+                         "L-BFGS, shard overheads, extra configs (N > 1: the weak-scaling and mailbox companions)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write F and G of the last timed step to DIR/F.npy and DIR/G.npy (float64, G as (K, N))")
     ap.add_argument("--config", default="C3", help="workload: C2, C3 (headline), C4, C5")
     ap.add_argument("--ensemble", type=int, default=0, help="override E (default: the config's)")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
@@ -814,8 +848,8 @@ def main():
                          "weak: every GPU gets a full-size ensemble shard")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-sample", type=int, default=32)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the device-resident loop and the extra configs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the device-resident loop and the extra configs")
     ap.add_argument("--extra-configs", default="C4,C5,C4dense,C4expm,C6,C7,C2,C5x1,C4x1,C6x1,C7x1,L1d,C3pm,C4pm,C5pm")
     ap.add_argument("--details", default="", help="also write the complete record (every note, per-kernel model, L-BFGS traces) "
                                                   "to this file; the printed line stays compact")
@@ -836,6 +870,9 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    extras = args.full and not args.no_extra
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)                          # does not return
@@ -905,12 +942,13 @@ def main():
     barrier()
     if sg.local is not None:
         sg.local.kernel_time(reset=True)
-    block_s = time_blocks(step, args.steps, args.blocks, barrier, reduce_max)
+    sizes = split_steps(args.steps, args.blocks)
+    block_s, (F_last, G_last) = time_blocks(step, sizes, barrier, reduce_max, settle=8)
+    G_last = np.array(G_last.T if direct else G_last)          # (K, N), as grape_eval's caller reads it
     samples = sg.local.kernel_samples() if sg.local is not None else ([], [])
-    F_last, _ = step()
     info = sg.local.info if sg.local is not None else {}
     names = sg.local.kernel_names() if sg.local is not None and hasattr(sg.local, "kernel_names") else []
-    elapsed = statistics.median(block_s)
+    step_s = statistics.median([t / n for t, n in zip(block_s, sizes)])
     rank_kernel = None
     if world > 1:                                  # every rank's own sweep-kernel time (median of its HIP-event samples): min / max over ranks
         mine = float(np.median(samples[0]) * 1e3) if len(samples[0]) else float("nan")
@@ -920,11 +958,11 @@ def main():
 
     # ---- the device-resident pipelined loop round 1 reported (x and [G,F] stay in HBM, one sync at the end)
     extra = None
-    if not args.no_extra:
+    if extras:
         x_dev = torch.as_tensor(np.ascontiguousarray(w.x.T), device=device)
         for _ in range(min(args.warmup, 10)):
             sg.eval_device(x_dev)
-        dev_s = time_blocks(lambda: sg.eval_device(x_dev), args.steps, 1, barrier, reduce_max)[0]
+        dev_s = time_blocks(lambda: sg.eval_device(x_dev), [args.steps], barrier, reduce_max)[0][0]
         extra = {"device_resident_pipelined": {
             "value": args.steps / dev_s * (E_total / E_cfg), "ms_per_step": 1e3 * dev_s / args.steps,
             "what": "grape_eval_device back to back, x and [G,F] resident in HBM, one sync after all steps: "
@@ -933,7 +971,7 @@ def main():
     # ---- N > 1: the companion weak-scaling figure (every GPU a full-size ensemble shard, same step, same all-reduce):
     # the headline stays the north star's strong-scaling number; this one shows what the exchange costs when the
     # per-GPU work does not shrink
-    if world > 1 and args.scaling == "strong" and not args.no_extra:
+    if world > 1 and args.scaling == "strong" and extras:
         try:
             w_weak = qoc.workloads.config(args.config, E=E_cfg * world)
             sg_w = sharded_engine(w_weak, device, force_collective=args.force_dist, collective=args.collective,
@@ -945,7 +983,7 @@ def main():
             step_w = (lambda: bound_w()) if direct_w else (lambda: sg_w.eval(np.ascontiguousarray(w_weak.x)))
             for _ in range(min(args.warmup, 10)):
                 step_w()
-            weak_s = statistics.median(time_blocks(step_w, args.steps, args.blocks, barrier, reduce_max))
+            weak_s = statistics.median(time_blocks(step_w, [args.steps] * args.blocks, barrier, reduce_max)[0])
             sg_w.close()
             extra = dict(extra or {})
             extra["weak_scaling"] = {
@@ -962,7 +1000,7 @@ def main():
     # a companion that gets stuck on hardware nobody has tried it on must not take the line with it (after 90 s the ranks
     # print what they have and leave through os._exit).
     companion_stuck = False
-    if world > 1 and args.scaling == "strong" and not args.no_extra and args.collective == "lib" \
+    if world > 1 and args.scaling == "strong" and extras and args.collective == "lib" \
             and os.environ.get("GRAPE_BENCH_IPC_COMPANION", "1") != "0":
         import threading
         box = {}
@@ -975,7 +1013,7 @@ def main():
                     bound_i = sg_i.local.bind_eval(xf, Gi)
                     for _ in range(min(args.warmup, 10)):
                         bound_i()
-                    ipc_s = statistics.median(time_blocks(bound_i, args.steps, args.blocks, barrier, reduce_max))
+                    ipc_s = statistics.median(time_blocks(bound_i, [args.steps] * args.blocks, barrier, reduce_max)[0])
                     box["res"] = {"value": args.steps / ipc_s, "unit": "gradient-evals/s", "ms_per_step": 1e3 * ipc_s / args.steps,
                                   "what": "the same step with collective='ipc' (ipc_allreduce_kernel instead of ncclAllReduce + copy)"}
                 else:
@@ -991,7 +1029,9 @@ def main():
         extra["ipc_exchange"] = {"error": "did not finish within 90 s"} if companion_stuck else box.get("res", {"error": "no result"})
 
     if rank == 0:
-        evals_per_s = args.steps / elapsed
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, F_last, G_last)
+        evals_per_s = 1.0 / step_s
         # units: with weak scaling the job evaluates world x the config's ensemble per step;
         # report in the metric's unit (evaluations of the CONFIG's E-member ensemble).
         value = evals_per_s * (E_total / E_cfg)
@@ -999,12 +1039,10 @@ def main():
         traffic = committed_traffic(f"{args.config}_E{local.E}")
         roof = roofline(local, info, samples, evals_per_s, world, traffic, committed_mfma(f"{args.config}_E{local.E}"), names)
         n_joined = sg.comm_size if (world > 1 or args.force_dist) else 1
-        box = box_record(qoc, local, dev_index, {"min": roof["kernel_min_us"], "median": roof["kernel_median_us"],
-                                                 "max": roof["kernel_max_us"]})
         out = {
             "metric": "GRAPE gradient-evals/sec", "value": value, "unit": "gradient-evals/s",
             "n_gpus": n_joined, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
+            "ms_per_step": 1e3 * step_s, "higher_is_better": True,
             "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": f"{args.config}: {w.sys_type} {w.n}x{w.n}, K={w.K}, N={w.N} slices, "
                                    f"ensemble E={E_total} ({'sharded' if world > 1 else 'one GPU'}, "
@@ -1016,20 +1054,22 @@ def main():
                        "collective": sg.collective if (world > 1 or args.force_dist) else None,
                        "slices_per_lane": info.get("slices_per_lane"),
                        "waves_per_member": info.get("waves_per_member")},
-            "blocks": {"count": args.blocks, "steps_each": args.steps, "seconds": block_s, "statistic": "median",
+            "blocks": {"count": len(sizes), "steps_each": sizes, "seconds": block_s, "statistic": "median time per step",
                        "untimed_ramp_steps": ramp_steps},
             "member_evals_per_s": evals_per_s * E_total,
             "roofline": roof,
-            "box": box,
             "F": float(F_last),
         }
+        if args.full:
+            out["box"] = box_record(qoc, local, dev_index, {"min": roof["kernel_min_us"], "median": roof["kernel_median_us"],
+                                                            "max": roof["kernel_max_us"]})
         if extra is not None:
             out["extra"] = extra
         if world > 1 or args.force_dist:
             out["ranks_seen"] = n_joined           # the communicator's own count (ncclCommCount / the mailbox group), not WORLD_SIZE
             if rank_kernel:
                 out["rank_kernel_us"] = rank_kernel
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cb, (foms_ref, grads_ref) = cpu_baseline(w, args.cpu_seconds, args.cpu_sample)
             out["cpu_baseline"] = cb
             m = len(foms_ref)
@@ -1047,7 +1087,7 @@ def main():
         out = None
 
     sg.close()
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and extras:
         try:
             out["extra"]["lbfgs"] = lbfgs_rates(qoc, dev_index)
         except Exception as exc:                   # noqa: BLE001 -- an extra must not kill the headline
@@ -1065,7 +1105,7 @@ def main():
             except Exception as exc:               # noqa: BLE001
                 shards[cfg] = {"error": repr(exc)}
         out["extra"]["scaling_forecast"] = scaling_forecast(shards)
-    if rank == 0 and world == 1 and not args.no_extra and args.extra_configs:
+    if rank == 0 and world == 1 and extras and args.extra_configs:
         out["extra_configs"] = []
         for name in [s for s in args.extra_configs.split(",") if s and s != args.config]:
             heavy = name in ("C4", "C4dense", "C4expm", "C5", "C6", "C7", "C4pm", "C5pm", "C6x1", "C7x1")

@@ -3,6 +3,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 from conftest import ROOT
 
 
@@ -111,3 +113,52 @@ def test_scaling_forecast_and_compact_line_stay_within_the_drivers_tail():
     assert pm["vs_shared_controls"] == 1.0 and pm["parity"][0] == 4 and pm["parity"][3] is True
     assert next(e for e in c["extra_configs"] if e["id"] == "C7")["parity"][3] is True
     assert next(e for e in c["extra_configs"] if e["id"] == "C3pm")["vs_shared_controls"] is not None
+
+
+def test_steps_are_the_timed_steps_and_outputs_dump_as_float64(tmp_path):
+    """--steps is the number of timed steps (cut into near-equal blocks, barriers only around all of them, settling steps
+    untimed), the last step's return value comes back from time_blocks, and --dump-outputs writes F as a (1,) array and G
+    as given, both float64."""
+    import numpy as np
+    bench = _bench_module()
+    for steps, blocks in ((20, 3), (1, 3), (7, 7), (300, 3), (5, 1), (4, 0)):
+        sizes = bench.split_steps(steps, blocks)
+        assert sum(sizes) == steps and len(sizes) == max(1, min(blocks, steps)) and max(sizes) - min(sizes) <= 1
+    calls = [0]
+
+    def step():
+        calls[0] += 1
+        return calls[0]
+    barriers = []
+    times, last = bench.time_blocks(step, [3, 3, 2], lambda: barriers.append(calls[0]), lambda s: s, settle=4)
+    assert len(times) == 3 and calls[0] == 12 and last == 12
+    assert barriers == [0, 12]                             # before the settling steps and after the last block, not between
+    G = np.arange(8.0).reshape(2, 4)
+    bench.dump_outputs(str(tmp_path / "out"), 0.25, G)
+    F = np.load(tmp_path / "out" / "F.npy")
+    g = np.load(tmp_path / "out" / "G.npy")
+    assert F.dtype == g.dtype == np.float64 and F.tolist() == [0.25] and np.array_equal(g, G)
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_the_last_timed_step(tmp_path):
+    """Without --full the line holds the headline only (no box clock, CPU baseline, parity or extras), timed over exactly
+    --steps steps; --dump-outputs holds what grape_eval's caller received from the last of them, the F and G a fresh
+    context computes for the same seeded inputs."""
+    import json
+    import numpy as np
+    import quoptimalcontrol_jl_amd as qoc
+    p = _run(["--gpus", "1", "--steps", "10", "--warmup", "2", "--dump-outputs", str(tmp_path / "out")])
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    d = json.loads(p.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 10 and len(d["blocks_s"]) == 3 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) <= 1e-3 * d["value"]
+    assert not {"box", "cpu_baseline", "parity", "extra", "extra_configs"} & set(d)
+    F = np.load(tmp_path / "out" / "F.npy")
+    G = np.load(tmp_path / "out" / "G.npy")
+    w = qoc.workloads.config("C3")
+    with qoc.GrapeEngine(w.sys_type, w.A, w.B, w.Xi, w.Xt, w.wts, w.T, w.N) as eng:
+        F_ref, G_ref = eng.eval(w.x)
+    assert F.dtype == G.dtype == np.float64 and F.shape == (1,) and G.shape == (w.K, w.N)
+    assert F[0] == d["F"]
+    assert abs(F[0] - F_ref) <= 1e-12 and np.abs(G - G_ref).max() <= 1e-12 * np.abs(G_ref).max()

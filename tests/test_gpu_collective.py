@@ -177,7 +177,7 @@ def test_two_ranks_sharing_the_gpu_fall_back_consistently(qoc):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, GRAPE_BENCH_SHARE_GPU="1")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                          "--blocks", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                          "--blocks", "1", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True,
                          timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])

@@ -45,7 +45,7 @@ def test_bench_line_fits_the_drivers_tail_and_is_labelled_by_the_library():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "3", "--cpu-seconds", "1",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "10", "--warmup", "3", "--cpu-seconds", "1",
                           "--cpu-sample", "4", "--extra-configs", "C4,C2,C4x1"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     line = out.stdout.strip().splitlines()[-1]

@@ -6,6 +6,7 @@
 BASE=${1:-build/r3tree}
 ROUNDS=${2:-10}
 ARGS="--steps 20 --warmup 5 --no-extra --no-cpu-baseline"
+full() { grep -q -e '"--full"' "$1/bench.py" && echo --full; }      # the box clock is a --full figure where --full exists
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 pick='import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d["roofline"]
@@ -14,9 +15,9 @@ b=d.get("box",{})
 print("%-5s value %8.1f  ms_per_step %.5f  kernel_us avg %.2f min %.2f median %.2f  step-kernel %.2f us  clock %s" % (sys.argv[1], d["value"], d["ms_per_step"], ku["avg"], ku["min"], ku["median"], 1e3*d["ms_per_step"]-ku["avg"], b.get("clock_ghz")))'
 echo "# A/B on one box, alternating, python bench.py $ARGS;  base = $BASE ($(git -C "$ROOT/$BASE" rev-parse --short HEAD 2>/dev/null)), head = $(git -C "$ROOT" rev-parse --short HEAD 2>/dev/null)"
 for i in $(seq 1 "$ROUNDS"); do
-    (cd "$ROOT/$BASE" && python3 bench.py $ARGS 2>/dev/null | python3 -c "$pick" base)
-    (cd "$ROOT" && python3 bench.py $ARGS 2>/dev/null | python3 -c "$pick" head)
+    (cd "$ROOT/$BASE" && python3 bench.py $(full .) $ARGS 2>/dev/null | python3 -c "$pick" base)
+    (cd "$ROOT" && python3 bench.py $(full .) $ARGS 2>/dev/null | python3 -c "$pick" head)
     if [ -n "$AB_THIRD_ENV" ]; then       # e.g. AB_THIRD_ENV="GRAPE_MF_PUBLISH=0": head again with one switch flipped
-        (cd "$ROOT" && env $AB_THIRD_ENV python3 bench.py $ARGS 2>/dev/null | python3 -c "$pick" "head*")
+        (cd "$ROOT" && env $AB_THIRD_ENV python3 bench.py $(full .) $ARGS 2>/dev/null | python3 -c "$pick" "head*")
     fi
 done

@@ -54,12 +54,12 @@ for seed in 51 52 53 54 55 56 57 58; do python3 tools/soak.py 1500 $seed 2>&1 | 
 python3 -m pytest tests/test_gpu_perf_gate.py -q -s 2>&1 | grep -E "perf gate|passed|failed" > "$OUT/perf_gate.txt"
 python3 tools/soak_api.py 600 5 2>&1 | tail -1 >> "$OUT/soak.txt"
 python3 tools/parity_report.py > "$OUT/parity.json" 2> "$OUT/parity.log"
-python3 bench.py --details "$OUT/bench_C3_1gpu_details.json" 2> /dev/null | tail -1 > "$OUT/bench_C3_1gpu.json"
-python3 bench.py --steps 20 --warmup 5 2> /dev/null | tail -1 > "$OUT/bench_C3_1gpu_driver_args.json"
-python3 bench.py --force-general --no-extra 2> /dev/null | tail -1 > "$OUT/bench_C3_general_flow_1gpu.json"
-python3 bench.py --force-dist --no-extra 2> /dev/null | tail -1 > "$OUT/bench_C3_1gpu_forced_1rank_collective.json"
+python3 bench.py --full --details "$OUT/bench_C3_1gpu_details.json" 2> /dev/null | tail -1 > "$OUT/bench_C3_1gpu.json"
+python3 bench.py --full --steps 20 --warmup 5 2> /dev/null | tail -1 > "$OUT/bench_C3_1gpu_driver_args.json"
+python3 bench.py --full --force-general --no-extra 2> /dev/null | tail -1 > "$OUT/bench_C3_general_flow_1gpu.json"
+python3 bench.py --full --force-dist --no-extra 2> /dev/null | tail -1 > "$OUT/bench_C3_1gpu_forced_1rank_collective.json"
 for E in 128 256 512; do
-  python3 bench.py --ensemble $E --no-extra --no-cpu-baseline 2> /dev/null | tail -1 > "$OUT/bench_C3_shard_E$E.json"
+  python3 bench.py --full --ensemble $E --no-extra --no-cpu-baseline 2> /dev/null | tail -1 > "$OUT/bench_C3_shard_E$E.json"
 done
 # keep the raw PMC CSVs out of the merge (64 MiB cap): summaries only
 find "$OUT" -name 'pass*' -maxdepth 2 -type d -exec rm -rf {} + 2> /dev/null
