@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define GRAPE_ABI_VERSION 6
+#define GRAPE_ABI_VERSION 7
 
 typedef enum grape_status {
     GRAPE_OK = 0,
@@ -267,6 +267,22 @@ int grape_ipc_attach(grape_ctx *ctx, const grape_ipc_handle *handles, int32_t ra
  * (wts: EnsembleProblem.wts, src/problems.jl:40; pass {1.0} for a plain Problem). */
 int grape_set_operators(grape_ctx *ctx, const double *A, const double *B, const double *Xi,
                         const double *Xt, const double *wts);
+
+/* ABI v7.  Control penalties of the reference's cost library, src/cost_functions.jl:29-39 (C3, C4) combined as
+ * PenaltyFunctionals does (:66-69), added to the objective of every evaluation on this context:
+ *   F_tot = F + sum_c amp_w[c] sum_t x[c,t]^2 + sum_c var_w[c] sum_{t<N-1} (x[c,t+1] - x[c,t])^2
+ *   G_tot[c,t] = G[c,t] + 2 amp_w[c] x[c,t] + 2 var_w[c] ([t>0](x[c,t] - x[c,t-1]) - [t<N-1](x[c,t+1] - x[c,t]))
+ * amp_w, var_w: host f64[K] (K = n_controls), each nullable (NULL: that term off; both NULL or all weights 0: no penalty,
+ * and the evaluation is exactly the one without this call).  The penalty belongs to the pulse, not to a member: it is not
+ * scaled by the ensemble weights, it is added ONCE per control array (grape_eval_batch: every array its own), and it
+ * does not enter grape_get_member_results.  grape_eval, grape_eval_device, the batched forms and grape_lbfgs (whose
+ * minimum and g_norm are then those of F_tot) all return the penalised [G, F].
+ * Weights must be finite and >= 0; otherwise GRAPE_ERR_INVALID_ARG and the previous weights stay in force.  Valid any
+ * time after grape_create, before or after grape_set_operators (the weights persist across it); ordered behind an
+ * in-flight grape_eval_device as grape_set_operators is.  Multi-device contexts add the penalty once, on the first
+ * device.  With grape_comm_attach / grape_ipc_attach only rank 0 adds it to its row before the exchange: every rank calls
+ * grape_set_penalties with the same weights, just as every rank passes the same x. */
+int grape_set_penalties(grape_ctx *ctx, const double *amp_w, const double *var_w);
 
 /* The closure body, src/solve.jl:164-196 (E>1) / :75-100 (E=1):
  *   F = sum_k w_k F_k ,  G[c,t] = sum_k w_k g_k[c,t]   with (F_k, g_k) = _fom_and_gradient_GRAPE!.

@@ -59,6 +59,7 @@ Base.@kwdef struct GRAPE_HIP{OPTS}
     device::Int = -1
     devices::Vector{Int} = Int[]     # 2..8 HIP ordinals: the ensemble is sharded over them inside the library
     peer_sum::Bool = false           # GRAPE_FLAG_GROUP_PEER_SUM: sum the shards on devices[1] by peer copies, no RCCL
+    penalties::Any = nothing         # ABI v7: PenaltyFunctionals of C3 / C4 (src/cost_functions.jl:29-39, 66-69), on the device
     optim_options::OPTS = Optim.Options()
 end
 
@@ -74,6 +75,7 @@ Base.@kwdef struct ADGRAPE_HIP{OPTS}
     n_slices::Int
     device::Int = -1
     devices::Vector{Int} = Int[]
+    penalties::Any = nothing
     optim_options::OPTS = Optim.Options()
 end
 
@@ -117,8 +119,21 @@ mutable struct GrapeContext
         check(ctx, ccall((:grape_set_operators, libgrape), Cint,
                          (Ptr{Cvoid}, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{Float64}),
                          ctx.handle, A, B, Xi, Xt, wts))
+        alg.penalties === nothing || set_penalties!(ctx, alg.penalties)
         ctx
     end
+end
+
+# grape_set_penalties (ABI v7): per-control weights of C3 (amplitude) and C4 (variation); a weight is a scalar or a K-vector
+function set_penalties!(ctx::GrapeContext, pf)
+    w = Dict{Any,Vector{Float64}}()
+    for (wt, f) in zip(pf.weights, pf.functions)
+        (f === QuOptimalControl.C3 || f === QuOptimalControl.C4) || error("set_penalties!: only C3 and C4 run on the device")
+        w[f] = wt isa Number ? fill(Float64(wt), ctx.K) : Vector{Float64}(wt)
+    end
+    amp, var = get(w, QuOptimalControl.C3, nothing), get(w, QuOptimalControl.C4, nothing)
+    check(ctx, ccall((:grape_set_penalties, libgrape), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), ctx.handle,
+                     amp === nothing ? C_NULL : amp, var === nothing ? C_NULL : var))
 end
 
 check(ctx::GrapeContext, rc) =

@@ -10,6 +10,7 @@ the reference's own tests (test/state_transfer_tests.jl, test/unitary_gate_tests
   solve(prob, alg) -> SolutionResult / EnsembleSolutionResult  src/solve.jl:63-143, :145-250
   init_ensemble(ens)                                           src/tools.jl:42-53
   C1(KT, KN)                                                   src/cost_functions.jl:13-17
+  C3(u), C4(u), PenaltyFunctionals(weights, functions)         src/cost_functions.jl:29-39, :66-69
 
 What differs, on purpose: the body of the (F, G, x) closure is one call into libgrape_hip.so
 (engine.GrapeEngine) instead of _fom_and_gradient_GRAPE!, and the L-BFGS driver is SciPy's
@@ -88,6 +89,8 @@ class GRAPE:
     devices: Optional[list] = None  # HIP ordinals: the library shards the ensemble over them (grape_config.n_devices /
                                     # device_ids, as julia/GrapeHIP.jl's `devices`) and all-reduces [G, F] once per evaluation
     peer_sum: bool = False         # with `devices`: GRAPE_FLAG_GROUP_PEER_SUM (sum on the first device, ids may repeat)
+    penalties: Any = None          # PenaltyFunctionals of C3 / C4 (new: the reference's solvers call none): added to the
+                                   # objective on the device (grape_set_penalties); res.minimum / fidelity then include them
 
 
 @dataclass
@@ -102,6 +105,7 @@ class ADGRAPE:
     optimizer: str = "host"
     devices: Optional[list] = None
     peer_sum: bool = False
+    penalties: Any = None
 
 
 @dataclass
@@ -128,6 +132,66 @@ def C1(KT, KN):
     KN = np.asarray(KN, complex)
     D = KT.shape[0]
     return 1.0 - abs(np.trace(KT.conj().T @ KN) / D) ** 2
+
+
+def C3(u):
+    """Control amplitudes, src/cost_functions.jl:29-31: sum(abs2.(u))."""
+    return float(np.sum(np.abs(np.asarray(u, dtype=np.float64)) ** 2))
+
+
+def C4(u):
+    """Control variations, src/cost_functions.jl:36-39: sum(abs2.(diff(u, dims = 2))) -- along the time axis of (K, N)."""
+    u = np.atleast_2d(np.asarray(u, dtype=np.float64))
+    return float(np.sum(np.abs(np.diff(u, axis=1)) ** 2))
+
+
+class PenaltyFunctionals:
+    """src/cost_functions.jl:66-69: relative weights and the penalty functionals they scale.  Only C3 and C4 -- the
+    functionals of the pulse alone, which the device adds to every evaluation (grape_set_penalties).  A weight is a
+    scalar (every control) or a length-K vector (per control); a functional may appear once."""
+
+    def __init__(self, weights, functions):
+        if len(weights) != len(functions):
+            raise ValueError("PenaltyFunctionals: one weight per functional")
+        self.weights, self.functions = list(weights), list(functions)
+        seen = set()
+        for f in self.functions:
+            if f not in (C3, C4):
+                raise ValueError("PenaltyFunctionals: only C3 and C4 are supported")
+            if f in seen:
+                raise ValueError("PenaltyFunctionals: each functional may appear once")
+            seen.add(f)
+
+    def device_weights(self, K):
+        """(amp, var) for grape_set_penalties: K-vectors of weights, or None for a term that is absent."""
+        out = {C3: None, C4: None}
+        for w, f in zip(self.weights, self.functions):
+            w = np.asarray(w, dtype=np.float64)
+            w = np.full(K, float(w)) if w.ndim == 0 else np.array(w, dtype=np.float64)
+            if w.shape != (K,):
+                raise ValueError(f"PenaltyFunctionals: a weight must be a scalar or have {K} entries")
+            out[f] = w
+        return out[C3], out[C4]
+
+    def __call__(self, u):
+        """sum of weight x functional, each control scaled by its own weight."""
+        u = np.atleast_2d(np.asarray(u, dtype=np.float64))
+        amp, var = self.device_weights(u.shape[0])
+        total = 0.0
+        for c in range(u.shape[0]):
+            if amp is not None:
+                total += amp[c] * C3(u[c])
+            if var is not None:
+                total += var[c] * C4(u[c:c + 1])
+        return total
+
+    def to_json(self):
+        return {"weights": [np.asarray(w, dtype=np.float64).tolist() for w in self.weights],
+                "functions": ["C3" if f is C3 else "C4" for f in self.functions]}
+
+    @classmethod
+    def from_json(cls, d):
+        return cls(d["weights"], [{"C3": C3, "C4": C4}[f] for f in d["functions"]])
 
 
 def init_ensemble(ens):
@@ -166,10 +230,19 @@ def make_engine(prob, alg, **engine_kw):
         if getattr(alg, "peer_sum", False):
             engine_kw["flags"] = engine_kw.get("flags", 0) | FLAG_GROUP_PEER_SUM
     if isinstance(alg, ADGRAPE):            # pw_evolve adds A first (src/timeevolution.jl:32-35): the static summation order
-        return GrapeEngine(first.sys_type.name, A, B, Xi, Xt, wts, first.T, alg.n_slices, variant=1, device=alg.device,
-                           gradient="exact", objective="c1", **engine_kw)
-    return GrapeEngine(first.sys_type.name, A, B, Xi, Xt, wts, first.T, alg.n_slices,
-                       variant=0 if alg.isinplace else 1, device=alg.device, **engine_kw)
+        eng = GrapeEngine(first.sys_type.name, A, B, Xi, Xt, wts, first.T, alg.n_slices, variant=1, device=alg.device,
+                          gradient="exact", objective="c1", **engine_kw)
+    else:
+        eng = GrapeEngine(first.sys_type.name, A, B, Xi, Xt, wts, first.T, alg.n_slices,
+                          variant=0 if alg.isinplace else 1, device=alg.device, **engine_kw)
+    pen = getattr(alg, "penalties", None)
+    if pen is not None:                     # on the device: the host optimiser, grape_lbfgs and every shard see them
+        try:
+            eng.set_penalties(*pen.device_weights(first.n_controls))
+        except Exception:
+            eng.close()
+            raise
+    return eng
 
 
 def fom_and_gradient(prob, alg, x, engine=None):
@@ -218,7 +291,9 @@ def save(solres, file_path):
         "alg_fields": np.array(json.dumps({"expm_method": alg.expm_method, "optim_options": alg.optim_options,
                                             "device": int(alg.device), "optimizer": alg.optimizer,
                                             "devices": None if alg.devices is None else [int(v) for v in alg.devices],
-                                            "peer_sum": bool(alg.peer_sum)}, default=_json_default)),
+                                            "peer_sum": bool(alg.peer_sum),
+                                            **({"penalties": alg.penalties.to_json()} if alg.penalties is not None else {})},
+                                           default=_json_default)),
     }
     if ens:
         members = init_ensemble(prob)
@@ -240,6 +315,8 @@ def load(file_path):
                    guess=d["guess"], sys_type=st)
     alg_cls = ADGRAPE if str(d["alg_kind"]) == "ADGRAPE" else GRAPE
     extra = json.loads(str(d["alg_fields"])) if "alg_fields" in d.files else {}      # (files of earlier rounds: defaults)
+    if extra.get("penalties") is not None:
+        extra["penalties"] = PenaltyFunctionals.from_json(extra["penalties"])
     alg = alg_cls(n_slices=int(d["n_slices"]), **extra) if alg_cls is ADGRAPE else GRAPE(n_slices=int(d["n_slices"]),
                                                                                            isinplace=bool(d["isinplace"]), **extra)
     if str(d["kind"]) == "ensemble":
@@ -304,7 +381,8 @@ def _device_lbfgs(eng, x0, options):
 
 
 def solve(prob, alg: Optional[GRAPE] = None, engine=None):
-    """solve(::Problem, ::GRAPE) / solve(::EnsembleProblem, ::GRAPE)."""
+    """solve(::Problem, ::GRAPE) / solve(::EnsembleProblem, ::GRAPE).  With alg.penalties the minimised objective is the
+    figure of merit plus the C3 / C4 penalties, and `fidelity` (res.minimum, as src/solve.jl:139) includes them."""
     if alg is None:
         raise TypeError("solve(prob) without an algorithm has no integrator in the reference either "
                         "(src/solve.jl:57,66); pass GRAPE(n_slices=...)")

@@ -173,6 +173,12 @@ struct grape_ctx {
     int tp_G = 0, tp_g = 0;                    // two-level scan: groups, chunks per group
     double2 *d_tp_a = nullptr;
     bool direct_publish = true;                // GRAPE_DIRECT_PUBLISH=0: always go through the reduce kernel
+    // control penalties (grape_set_penalties, src/cost_functions.jl:29-39): C3 / C4 weights whose value and gradient the final
+    // reduction adds (DoneSignal::pen_x).  Only the context that holds comm_rank 0 (a single-device context, shard 0 of a
+    // group, rank 0 of an attached communicator / mailbox exchange) adds them: the cross-shard sums count them exactly once.
+    bool pen_on = false;                       // some weight > 0
+    std::vector<double> pen_w;                 // host copy [amp (K) | var (K)]
+    double *d_pen_w = nullptr;                 // device copy of pen_w
     bool mf_publish = true;                    // GRAPE_MF_PUBLISH=0: reduce_rows_kernel's staged publication instead of per-workgroup host flags
     unsigned long long seq = 0;
     std::string kernel_log;                    // names of the kernels the last evaluation launched (grape_get_kernel_names)
@@ -434,6 +440,7 @@ static void free_all(grape_ctx *c)
     (void)hipFree(c->d_any_sp_i); (void)hipFree(c->d_any_sp_c);
     (void)hipFree(c->d_tp_q); (void)hipFree(c->d_tp_r); (void)hipFree(c->d_tp_m); (void)hipFree(c->d_tp_z); (void)hipFree(c->d_tp_vec); (void)hipFree(c->d_tp_a);
     (void)hipFree(c->d_x_bar);
+    (void)hipFree(c->d_pen_w);
     (void)hipFree(c->d_ha); (void)hipFree(c->d_ha_norm); (void)hipFree(c->d_gc); (void)hipFree(c->d_gcn);
     (void)hipFree(c->d_act_a); (void)hipFree(c->d_act_b); (void)hipFree(c->d_act_bf); (void)hipFree(c->d_act_g);
     (void)hipFree(c->d_act_an); (void)hipFree(c->d_act_gn); (void)hipFree(c->d_act_bs); (void)hipFree(c->d_act_bo); (void)hipFree(c->d_act_bn); (void)hipFree(c->d_wrec); (void)hipFree(c->d_props_t);
@@ -1067,6 +1074,55 @@ extern "C" int grape_ipc_attach(grape_ctx *c, const grape_ipc_handle *handles, i
     c->comm_rank = rank;
     c->comm_size = n_ranks;
     return GRAPE_OK;
+}
+
+// one device context: the validated weights w = [amp | var] (on: some weight > 0), behind whatever evaluation is in flight
+static int shard_set_penalties(grape_ctx *c, const std::vector<double> &w, bool on)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->dev_pending) {                                    // (as grape_set_operators: d_pen_w may be in use)
+        HIP_TRY(c, hipEventSynchronize(c->ev_dev));
+        c->dev_pending = false;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (on && !c->d_pen_w) {
+        HIP_TRY(c, hipMalloc((void **)&c->d_pen_w, sizeof(double) * w.size()));
+        c->bytes += sizeof(double) * w.size();
+    }
+    if (on) HIP_TRY(c, hipMemcpy(c->d_pen_w, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice));
+    c->pen_w = w;
+    c->pen_on = on;
+    return GRAPE_OK;
+}
+
+extern "C" int grape_set_penalties(grape_ctx *c, const double *amp_w, const double *var_w)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_set_penalties: null context");
+    const int K = c->cfg.n_controls;
+    std::vector<double> w(2 * (size_t)K, 0.0);
+    bool on = false;
+    for (int j = 0; j < 2 * K; ++j) {
+        const double *src = j < K ? amp_w : var_w;
+        if (!src) continue;
+        const double v = src[j % K];
+        if (!std::isfinite(v) || v < 0.0)
+            return fail(c, GRAPE_ERR_INVALID_ARG, std::string("grape_set_penalties: ") + (j < K ? "amp_w[" : "var_w[") +
+                                                      std::to_string(j % K) + "] = " + std::to_string(v) +
+                                                      " (weights must be finite and >= 0)");
+        w[j] = v;
+        on = on || v > 0.0;
+    }
+    if (c->is_group) {                                       // every shard keeps them; shard 0 (comm_rank 0) adds them
+        for (grape_ctx *s : c->sub) {
+            const int rc = shard_set_penalties(s, w, on);
+            if (rc) return fail(c, rc, s->err);
+        }
+        c->pen_w = w;
+        c->pen_on = on;
+        return GRAPE_OK;
+    }
+    return shard_set_penalties(c, w, on);
 }
 
 // smallest ensemble the vector flow of action_thin.hip is chosen for.  A member's two chains are strictly sequential in
@@ -1984,9 +2040,13 @@ static bool states_stored(const grape_ctx *c)
 // ONE problem whose flow ends in a forms kernel of action_thin.hip or in a unitary chain kernel (chain_tile_unitary_kernel,
 // coop_chain_unitary_kernel: every launch path of launch_nt with p.unitary and no stored costates): that kernel closes the
 // evaluation (no reduce launch)
+// this context adds the control penalties to its [G, F] (see grape_ctx::pen_on)
+static bool pen_active(const grape_ctx *c) { return c->pen_on && c->comm_rank == 0; }
+
 static bool tile_folds_reduce(const grape_ctx *c, int n_x)
 {
-    if (c->family != 1 || c->cfg.n_ensemble != 1 || n_x != 1 || c->cfg.gradient == GRAPE_GRADIENT_EXACT || !c->direct_publish)
+    if (c->family != 1 || c->cfg.n_ensemble != 1 || n_x != 1 || c->cfg.gradient == GRAPE_GRADIENT_EXACT || !c->direct_publish ||
+        pen_active(c))                                       // (penalties: the reduce kernel adds them)
         return false;
     return c->action || c->thin_dpp || (c->unitary && !c->thin && !c->d_costates);
 }
@@ -2095,8 +2155,9 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
     // one workgroup holds the whole ensemble (single problems): its row is [G, F], no reduce launch
     // (done.stage_base: this evaluation is the last array of a batch that runs array by array -- its publication has to
     // copy out the WHOLE staging buffer, which only the reduce kernels do: no self-closing sweep / fold then)
+    // (penalties: the reduce kernel adds them -- the sweep's own row goes through it)
     const bool direct = c->family == 0 && c->NB == 1 && n_x == 1 && !exact && c->direct_publish && !done.probe_out &&
-                        !done.stage_base;
+                        !done.stage_base && !pen_active(c);
     const bool fold = !done.stage_base && tile_folds_reduce(c, n_x);
     if (direct) {
         p.direct_dst = done.flag && done.host_out ? done.host_out : d_fg;
@@ -2225,15 +2286,26 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
         if (rc) return rc;
     }
     if (timed) HIP_TRY(c, hipEventRecord(e1, stream));
+    // the control penalties of the n_x arrays: added once, by the final reduction below (reduce.hip) -- never per member
+    // block or per shard
+    auto with_pen = [&](grape::DoneSignal d, int b) {
+        if (pen_active(c)) {
+            d.pen_x = d_x + (size_t)b * KN(c);
+            d.pen_w = c->d_pen_w;
+            d.pen_K = c->cfg.n_controls;
+            d.pen_N = c->cfg.n_slices;
+        }
+        return d;
+    };
     if (exact)
         HIP_TRY(c, grape::launch_reduce(c->d_member_out, c->d_wts, c->d_partial, d_fg, p.E, (int)(KN(c) + 1), c->ksplit,
-                                        stream, done));
+                                        stream, with_pen(done, 0)));
     else if (direct || fold)
         ;                                                    // the sweep / forms kernel has written [G, F] (and the flag)
     else if (c->family == 0) {
         if (done.mflags && done.flag && done.host_out && !done.probe_out)
             c->mf_wait = grape::reduce_rows_mflags((int)(KN(c) + 1), n_x);       // (the launch takes the same decision)
-        HIP_TRY(c, grape::launch_reduce_rows(c->d_block_out, d_fg, c->NB, (int)(KN(c) + 1), n_x, stream, done));
+        HIP_TRY(c, grape::launch_reduce_rows(c->d_block_out, d_fg, c->NB, (int)(KN(c) + 1), n_x, stream, with_pen(done, 0)));
     }
     else {
         // one weighted reduction per control array (each reuses d_partial, in stream order); with a host
@@ -2249,7 +2321,7 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
                 }
             }
             HIP_TRY(c, grape::launch_reduce(c->d_member_out + (size_t)b * p.E * Qs, c->d_wts, c->d_partial,
-                                            d_fg + (size_t)b * Qs, p.E, (int)Qs, c->ksplit, stream, db));
+                                            d_fg + (size_t)b * Qs, p.E, (int)Qs, c->ksplit, stream, with_pen(db, b)));
         }
     }
     c->evaluated = true;

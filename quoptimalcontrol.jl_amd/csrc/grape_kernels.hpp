@@ -51,6 +51,12 @@ struct DoneSignal {
     // round 5: publication WITHOUT a device-side fan-in (reduce_rows_mf_kernel): workgroup b writes its outputs straight to
     // host_out, fences at system scope and stores `seq` into mflags[b] (mapped host memory); the host waits for all of them
     unsigned long long *mflags = nullptr;
+    // ABI v7, the control penalties C3 / C4 of grape_set_penalties (src/cost_functions.jl:29-39): the final reduction adds
+    // Gp = 2 a_c x + 2 v_c ([t>0](x[c,t]-x[c,t-1]) - [t<N-1](x[c,t+1]-x[c,t])) and Fp = sum a_c x^2 + v_c (x[c,t+1]-x[c,t])^2
+    // of these controls to the ensemble sum before it stores / publishes (reduce.hip, pen_grad / pen_value)
+    const double *pen_x = nullptr;             // device: the (K,N) control array(s) of the evaluation; nullptr: no penalty
+    const double *pen_w = nullptr;             // device: [amp (K) | var (K)]
+    int pen_K = 0, pen_N = 0;
 };
 constexpr int kMaxMflags = 1000;               // flags behind grape_ctx::h_flag (8 KB: [0] flag, [1] exchange failure, [8..] these)
 // workgroups (= host flags) reduce_rows_mf_kernel publishes with for Q outputs x n_x control arrays; 0: not applicable

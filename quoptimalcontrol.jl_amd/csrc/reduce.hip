@@ -10,6 +10,43 @@
 
 namespace grape {
 
+// ---- control penalties (DoneSignal::pen_x, grape_set_penalties; src/cost_functions.jl:29-39) ----------------------------
+// Added ONCE, by the final reduction of the context that holds them, behind the ensemble sum and before the store / publication:
+// every output q < K N its gradient entry, the F output the penalty value.  pen_value is called by every thread of the
+// workgroup that owns the F output (a workgroup-uniform condition) and sums in a fixed order (thread-strided partial sums,
+// then a halving tree through LDS): bitwise reproducible run to run.
+__device__ __forceinline__ double pen_grad(const DoneSignal &d, const double *__restrict__ x, int i)
+{
+    const int K = d.pen_K, c = i % K, t = i / K;
+    const double xi = x[i];
+    const double dn = t + 1 < d.pen_N ? x[i + K] - xi : 0.0;    // x[c,t+1] - x[c,t]
+    const double dp = t > 0 ? xi - x[i - K] : 0.0;              // x[c,t] - x[c,t-1]
+    return 2.0 * d.pen_w[c] * xi + 2.0 * d.pen_w[K + c] * (dp - dn);
+}
+
+template <int NT>
+__device__ double pen_value(const DoneSignal &d, const double *__restrict__ x)
+{
+    __shared__ double s_pen[NT];
+    const int K = d.pen_K, KN = K * d.pen_N;
+    double f = 0.0;
+    for (int i = threadIdx.x; i < KN; i += NT) {
+        const int c = i % K, t = i / K;
+        const double xi = x[i];
+        const double dn = t + 1 < d.pen_N ? x[i + K] - xi : 0.0;
+        f += d.pen_w[c] * xi * xi + d.pen_w[K + c] * dn * dn;
+    }
+    s_pen[threadIdx.x] = f;
+    __syncthreads();
+#pragma unroll
+    for (int h = NT / 2; h >= 1; h >>= 1) {
+        if ((int)threadIdx.x < h)
+            s_pen[threadIdx.x] += s_pen[threadIdx.x + h];
+        __syncthreads();
+    }
+    return s_pen[0];
+}
+
 constexpr int kTileQ = 64;    // outputs per block (one wave-width, coalesced)
 constexpr int kSubK = 4;      // member sub-lanes per block
 
@@ -52,6 +89,13 @@ __global__ __launch_bounds__(256) void reduce_stage2(const double *__restrict__ 
 #pragma unroll
     for (int d = kMaxSplit / 2; d >= 1; d >>= 1)
         v += __shfl_xor(v, d, 64);
+    if (done.pen_x) {                                // the control penalties: once, behind the ensemble sum
+        const double pf = blockIdx.x == gridDim.x - 1 ? pen_value<256>(done, done.pen_x) : 0.0;
+        if (q < Q - 1)
+            v += pen_grad(done, done.pen_x, q);
+        else if (q == Q - 1)
+            v += pf;
+    }
     if (done.flag) {
         if (ks == 0 && q < Q)
             stage_store(fg, q, v);
@@ -89,12 +133,16 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(const double *__restri
         }
     }
     s_acc[bl][ql] = acc;
+    const double *px = done.pen_x ? done.pen_x + (size_t)blockIdx.y * (Q - 1) : nullptr;     // (this control array's)
+    const double pf = px && blockIdx.x == gridDim.x - 1 ? pen_value<256>(done, px) : 0.0;  // (its barriers cover s_acc)
     __syncthreads();
     if (bl == 0 && q < Q) {
         double s = s_acc[0][ql];
 #pragma unroll
         for (int i = 1; i < 32; ++i)
             s += s_acc[i][ql];
+        if (px)                                      // the control penalties: once, behind the ensemble sum
+            s += q < Q - 1 ? pen_grad(done, px, q) : pf;
         if (done.flag && (done.host_out || done.probe_out))
             stage_store(fg, q, s);
         else
@@ -136,6 +184,8 @@ __global__ __launch_bounds__(1024) void reduce_rows_mf_kernel(const double *__re
         }
     }
     s_acc[bl][ql] = acc;
+    const double *px = done.pen_x ? done.pen_x + (size_t)blockIdx.y * (Q - 1) : nullptr;
+    const double pf = px && blockIdx.x == gridDim.x - 1 ? pen_value<1024>(done, px) : 0.0;
     __syncthreads();
     if (bl == 0) {                                   // lanes 0..31 of the first wave
         if (q < Q) {
@@ -143,6 +193,8 @@ __global__ __launch_bounds__(1024) void reduce_rows_mf_kernel(const double *__re
 #pragma unroll
             for (int i = 1; i < 32; ++i)
                 s += s_acc[i][ql];
+            if (px)                                  // the control penalties: once, behind the ensemble sum
+                s += q < Q - 1 ? pen_grad(done, px, q) : pf;
             fg[(size_t)blockIdx.y * Q + q] = s;
             done.host_out[(size_t)blockIdx.y * Q + q] = s;
         }
@@ -208,6 +260,13 @@ __global__ __launch_bounds__(256) void reduce_few_kernel(const double *__restric
     if (q < Q)
         for (int k = 0; k < E; ++k)
             acc = fma(member_out[(size_t)k * Q + q], wts[k], acc);
+    if (done.pen_x) {                                // the control penalties: once, behind the ensemble sum
+        const double pf = blockIdx.x == gridDim.x - 1 ? pen_value<256>(done, done.pen_x) : 0.0;
+        if (q < Q - 1)
+            acc += pen_grad(done, done.pen_x, q);
+        else if (q == Q - 1)
+            acc += pf;
+    }
     if (done.flag) {
         if (q < Q)
             stage_store(fg, q, acc);

@@ -250,14 +250,27 @@ class ShardedGrape:
         h = fg.cpu().numpy()
         return float(h[-1]), np.ascontiguousarray(h[:-1].reshape(self.N, self.K).T)
 
+    def set_penalties(self, amp=None, var=None):
+        """The control penalties C3 / C4 (GrapeEngine.set_penalties) of the full-ensemble objective, counted once: every
+        rank passes the same weights.  With the library's exchange (collective "lib" / "ipc") the library lets rank 0
+        alone add them; with the torch.distributed sum, only rank 0's shard is given them."""
+        if self.local is None:
+            return
+        summed_here = self.collective == "torch" and (self.world > 1 or self.force_collective)
+        if summed_here and self.rank != 0:
+            self.local.set_penalties(None, None)
+        else:
+            self.local.set_penalties(amp, var)
+
     def close(self):
         if self.local is not None and hasattr(self.local, "close"):
             self.local.close()
             self.local = None
 
 
-def sharded_engine(workload, device, group=None, force_collective=False, collective="lib", **engine_kw):
-    """The product wiring: every rank builds a GrapeEngine for its block of `workload`."""
+def sharded_engine(workload, device, group=None, force_collective=False, collective="lib", penalties=None, **engine_kw):
+    """The product wiring: every rank builds a GrapeEngine for its block of `workload`.  penalties: (amp, var) weights
+    of the C3 / C4 control penalties (ShardedGrape.set_penalties), the same on every rank."""
     from .engine import GrapeEngine
 
     w = workload
@@ -267,4 +280,7 @@ def sharded_engine(workload, device, group=None, force_collective=False, collect
         return GrapeEngine(w.sys_type, w.A[lo:hi], w.B[lo:hi], w.Xi[lo:hi], w.Xt[lo:hi], w.wts[lo:hi],
                            w.T, w.N, device=dev_index, **engine_kw)
 
-    return ShardedGrape(w.E, w.K, w.N, make_local, device, group, force_collective, collective)
+    sg = ShardedGrape(w.E, w.K, w.N, make_local, device, group, force_collective, collective)
+    if penalties is not None:
+        sg.set_penalties(*penalties)
+    return sg

@@ -28,14 +28,14 @@ FLAG_FORCE_COLLECTIVE = 32
 FLAG_TIME_SAMPLED = 64
 FLAG_GROUP_PEER_SUM = 128
 MAX_DEVICES = 8
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 STATUS = {0: "GRAPE_OK", -1: "GRAPE_ERR_INVALID_ARG", -2: "GRAPE_ERR_UNSUPPORTED",
           -3: "GRAPE_ERR_NO_DEVICE", -4: "GRAPE_ERR_HIP", -5: "GRAPE_ERR_NOT_READY",
           -6: "GRAPE_ERR_ALLOC", -7: "GRAPE_ERR_TIMEOUT", -8: "GRAPE_ERR_COMM"}
 
 # every symbol include/grape_hip.h declares
-EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_operators",
+EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_operators", "grape_set_penalties",
            "grape_comm_unique_id", "grape_comm_attach", "grape_ipc_export", "grape_ipc_attach",
            "grape_eval", "grape_eval_device", "grape_eval_batch", "grape_eval_batch_device", "grape_lbfgs", "grape_lbfgs_get_trace",
            "grape_get_member_results", "grape_get_trajectory",
@@ -120,6 +120,7 @@ def load_library():
     L.grape_create.argtypes = [C.POINTER(GrapeConfig), C.POINTER(vp)]
     L.grape_destroy.argtypes = [vp]
     L.grape_set_operators.argtypes = [vp] * 6
+    L.grape_set_penalties.argtypes = [vp, vp, vp]
     L.grape_comm_unique_id.argtypes = [C.POINTER(GrapeCommId)]
     L.grape_comm_attach.argtypes = [vp, C.POINTER(GrapeCommId), i32, i32]
     L.grape_ipc_export.argtypes = [vp, i32, vp]
@@ -221,6 +222,22 @@ class GrapeEngine:
                 Xi.shape != (self.E, self.n, self.m) or Xt.shape != Xi.shape or wts.shape != (self.E,):
             raise ValueError("operator shapes must match the context")
         self._check(self._lib.grape_set_operators(self._h, _p(_cm(A)), _p(_cm(B)), _p(_cm(Xi)), _p(_cm(Xt)), _p(wts)))
+
+    def set_penalties(self, amp=None, var=None):
+        """grape_set_penalties: control-amplitude (C3) and control-variation (C4) weights, src/cost_functions.jl:29-39.
+        Each of amp, var is None (term off), a scalar (every control) or a length-K vector of weights >= 0.  From now on
+        every evaluation of this context returns F + sum_c amp_c sum_t x[c,t]^2 + sum_c var_c sum_t (x[c,t+1]-x[c,t])^2
+        and its gradient (once per control array, not scaled by the ensemble weights); amp = var = None clears them."""
+        def vec(w):
+            if w is None:
+                return None
+            w = np.asarray(w, dtype=np.float64)
+            w = np.full(self.K, float(w)) if w.ndim == 0 else np.ascontiguousarray(w)
+            if w.shape != (self.K,):
+                raise ValueError(f"penalty weights must be a scalar or have {self.K} entries")
+            return w
+        a, v = vec(amp), vec(var)
+        self._check(self._lib.grape_set_penalties(self._h, _p(a), _p(v)))
 
     # ------------------------------------------------------------------ plumbing
     def _check(self, rc):
