@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define GRAPE_ABI_VERSION 7
+#define GRAPE_ABI_VERSION 8
 
 typedef enum grape_status {
     GRAPE_OK = 0,
@@ -315,6 +315,33 @@ int grape_eval_batch(grape_ctx *ctx, int32_t n_x, const double *x, double *F, do
 
 /* Device-pointer form: d_x (K,N,n_x), d_fg f64[(K*N + 1) * n_x] = n_x blocks of { G, F }. */
 int grape_eval_batch_device(grape_ctx *ctx, int32_t n_x, const double *d_x, double *d_fg, void *stream);
+
+/* ABI v8.  The figure of merit WITHOUT the gradient: src/timeevolution.jl:28-39 (pw_evolve) followed by fom_func
+ * (src/cost_functions.jl:99-111, objective = 0) or C1(Xt, U Xi [U']) (src/solve.jl:268-361, objective = 1), summed
+ * over the ensemble as src/solve.jl:166-187 does -- for callers that rank pulses by their value: dCRAB / Nelder-Mead
+ * (src/dCRAB.jl:13-89), robustness landscapes over a grid of members, multi-start screening.
+ *   x         host f64 (K,N,n_x), 1 <= n_x <= max(1, grape_config.max_batch)
+ *   F         host f64[n_x]          the value grape_eval / grape_eval_batch return as F (penalties of
+ *                                    grape_set_penalties included)
+ *   member_F  host f64 (E,n_x), nullable: every member's unweighted F_k (no penalty), member index fastest
+ * Valid on EVERY context grape_eval serves (any n, system type, variant, gradient / objective setting, n x m states;
+ * member-chunked, multi-device and communicator / mailbox contexts), blocking like grape_eval and ordered behind an
+ * in-flight grape_eval_device in the same way.  Collective contexts: all ranks call it together, like grape_eval.
+ * Fast path -- single-device contexts without communicator or mailbox in kernel family 0 (n = 2, 3, 4): a forward-only
+ *   kernel (fom_lane_kernel / fom_pair_kernel) forms the propagators in registers and multiplies them up; nothing is written
+ *   to the propagator / state / costate workspace or to the member-result rows, so grape_get_trajectory,
+ *   grape_get_member_results, grape_get_kernel_time and an eval -> fom -> eval sequence behave as if the call had not
+ *   happened; grape_get_kernel_names reports the kernels of this call.  It needs no P_t storage: a member-chunked context
+ *   is evaluated in one launch, a batch in one launch whatever the workspace holds.  member_F is always available.  The
+ *   value agrees with grape_eval's F to rounding (the two flows multiply in different orders), not bit for bit.
+ * Fallback -- everywhere else: the full evaluation runs and its F is returned, BITWISE what grape_eval (grape_eval_batch,
+ *   entry b) returns for the same x.  member_F then follows grape_get_member_results: available where the rows exist
+ *   (n >= 5, or GRAPE_FLAG_MEMBER_RESULTS), otherwise GRAPE_ERR_NOT_READY (the message names GRAPE_FLAG_MEMBER_RESULTS)
+ *   before anything runs; with n_x > 1 it is served by running the arrays one after another.
+ * Errors as grape_eval: null x or F, n_x out of range -> GRAPE_ERR_INVALID_ARG; before grape_set_operators ->
+ * GRAPE_ERR_NOT_READY.  Non-finite x propagates NaN.  Results are bitwise reproducible call to call: the chunk products
+ * of a member combine in a tree fixed by the decomposition, the member sum has a fixed order. */
+int grape_eval_fom(grape_ctx *ctx, int32_t n_x, const double *x, double *F, double *member_F);
 
 /* Device-resident L-BFGS: stands in for
  *     Optim.optimize(Optim.only_fg!(topt), x0, Optim.LBFGS(), optim_options)       src/solve.jl:138, :244

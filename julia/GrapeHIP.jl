@@ -152,6 +152,16 @@ function fom_and_gradient!(ctx::GrapeContext, G, x::Matrix{Float64}; want_F = tr
     F[]
 end
 
+"grape_eval_fom (ABI v8): the figure of merit of `x` without its gradient -- what a gradient-free optimiser (src/dCRAB.jl) or a
+robustness scan needs; for n = 2..4 on one device a forward-only kernel, elsewhere the full evaluation's F."
+function grape_fom(ctx::GrapeContext, x::Matrix{Float64})
+    size(x) == (ctx.K, ctx.N) || throw(DimensionMismatch("x must be (n_controls, n_slices)"))
+    F = Ref{Float64}(NaN)
+    GC.@preserve x check(ctx, ccall((:grape_eval_fom, libgrape), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ref{Float64}, Ptr{Float64}),
+                                    ctx.handle, Int32(1), x, F, C_NULL))
+    F[]
+end
+
 "The kernels the last evaluation launched, in launch order (grape_get_kernel_names, ABI v4)."
 function kernel_names(ctx::GrapeContext)
     need = ccall((:grape_get_kernel_names, libgrape), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Cint), ctx.handle, C_NULL, 0)

@@ -11,6 +11,7 @@ the reference's own tests (test/state_transfer_tests.jl, test/unitary_gate_tests
   init_ensemble(ens)                                           src/tools.jl:42-53
   C1(KT, KN)                                                   src/cost_functions.jl:13-17
   C3(u), C4(u), PenaltyFunctionals(weights, functions)         src/cost_functions.jl:29-39, :66-69
+  dCRAB(n_slices=..., n_freq=2, n_coeff=2)                     src/dCRAB.jl:2-5, :13-89
 
 What differs, on purpose: the body of the (F, G, x) closure is one call into libgrape_hip.so
 (engine.GrapeEngine) instead of _fom_and_gradient_GRAPE!, and the L-BFGS driver is SciPy's
@@ -106,6 +107,44 @@ class ADGRAPE:
     devices: Optional[list] = None
     peer_sum: bool = False
     penalties: Any = None
+
+
+@dataclass
+class dCRAB:
+    """src/dCRAB.jl:2-5 (dCRAB_options) and :13-89: the gradient-free solver.  n_freq super-iterations; each draws one
+    frequency per control in [0, 1) and minimises the functional over n_coeff coefficients per control of the ansatz
+    c1 cos(w t) + c2 sin(w t) added to the current pulse, with Nelder-Mead; the pulse is updated after each.  The
+    functional is the one the reference's `_solve` wrappers (:97-142) and ADGRAPE use, sum_k w_k C1(Xt_k, U Xi_k [U']),
+    evaluated on the device WITHOUT its gradient (GrapeEngine.fom).  `options`: SciPy Nelder-Mead options (maxiter,
+    xatol, fatol, ...); `seed`: numpy.random.default_rng(seed) draws the frequencies and the initial coefficients."""
+    n_slices: int
+    n_freq: int = 2
+    n_coeff: int = 2
+    seed: Any = None
+    options: Optional[dict] = None
+    device: int = -1
+    devices: Optional[list] = None
+    peer_sum: bool = False
+    penalties: Any = None
+
+    def __post_init__(self):
+        if int(self.n_freq) < 1:
+            raise ValueError("dCRAB: n_freq must be at least 1")
+        if int(self.n_coeff) != 2:       # the ansatz reads coeffs[1] and coeffs[2] and nothing else (src/dCRAB.jl:26)
+            raise ValueError("dCRAB: the ansatz c1 cos(w t) + c2 sin(w t) has n_coeff = 2 coefficients per control")
+        if int(self.n_slices) < 1:
+            raise ValueError("dCRAB: n_slices must be at least 1")
+
+
+def dcrab_pulse(coeffs, freqs, n_slices, duration):
+    """The pulse the ansatz of src/dCRAB.jl:26 adds: row j is c[j,0] cos(w_j t) + c[j,1] sin(w_j t) on the grid
+    t = 0, dt, ..., T - dt (`0:dt:duration-dt`, :42), dt = T / n_slices.  coeffs: K x 2, or flat with control j's pair
+    at [2j, 2j + 1] (first(j):second(j), :45-46); freqs: K.  Returns (K, n_slices)."""
+    freqs = np.asarray(freqs, dtype=np.float64).reshape(-1)
+    c = np.asarray(coeffs, dtype=np.float64).reshape(freqs.shape[0], 2)
+    t = np.arange(int(n_slices), dtype=np.float64) * (float(duration) / int(n_slices))
+    wt = freqs[:, None] * t[None, :]
+    return c[:, 0:1] * np.cos(wt) + c[:, 1:2] * np.sin(wt)
 
 
 @dataclass
@@ -229,7 +268,7 @@ def make_engine(prob, alg, **engine_kw):
         engine_kw = dict(engine_kw, devices=list(alg.devices))
         if getattr(alg, "peer_sum", False):
             engine_kw["flags"] = engine_kw.get("flags", 0) | FLAG_GROUP_PEER_SUM
-    if isinstance(alg, ADGRAPE):            # pw_evolve adds A first (src/timeevolution.jl:32-35): the static summation order
+    if isinstance(alg, (ADGRAPE, dCRAB)):   # pw_evolve adds A first (src/timeevolution.jl:32-35): the static summation order
         eng = GrapeEngine(first.sys_type.name, A, B, Xi, Xt, wts, first.T, alg.n_slices, variant=1, device=alg.device,
                           gradient="exact", objective="c1", **engine_kw)
     else:
@@ -380,12 +419,60 @@ def _device_lbfgs(eng, x0, options):
                            success=info["status"] in (0, 1), device_lbfgs=info)
 
 
+def _solve_dcrab(prob, alg, eng):
+    """src/dCRAB.jl:13-89 on the device functional.  Deviations, on purpose: the start vector has n_coeff K entries (the
+    reference hard-codes `reshape(..., 4)`, :71, i.e. two controls); and Nelder-Mead's first simplex is SciPy's default one
+    around the drawn coefficients with its last vertex moved to the origin -- the CURRENT pulse -- so a super-iteration never
+    returns a worse pulse than it was given (the reference starts every search from random coefficients only)."""
+    from scipy.optimize import minimize
+
+    base = prob.prob if isinstance(prob, EnsembleProblem) else prob
+    K, N, T = int(base.n_controls), int(alg.n_slices), float(base.T)
+    pulse = np.array(base.guess, dtype=np.float64).reshape(K, N)
+    rng = np.random.default_rng(alg.seed)
+    freqs = rng.random((alg.n_freq, K))                        # init_freq, :29
+    coeffs = rng.random((alg.n_freq, K, alg.n_coeff))          # init_coeffs, :33 (control j's coefficients adjacent)
+    results, minima = [], []
+    for i in range(alg.n_freq):
+        current = pulse
+
+        def to_minimize(c, current=current, w=freqs[i]):
+            return eng.fom(current + dcrab_pulse(c, w, N, T))
+
+        x0 = coeffs[i].reshape(-1)
+        sim = np.tile(x0, (x0.size + 1, 1))
+        for k in range(x0.size - 1):                            # scipy.optimize's default simplex ...
+            sim[k + 1, k] = sim[k + 1, k] * 1.05 if sim[k + 1, k] != 0 else 0.00025
+        sim[-1] = 0.0                                           # ... but for the vertex that keeps the pulse as it is
+        if x0[-1] == 0.0:                                       # (a degenerate simplex otherwise; the draw is in [0, 1))
+            sim[0, -1] = 0.00025
+        opts = dict(alg.options or {})
+        opts["initial_simplex"] = sim
+        res = minimize(to_minimize, x0, method="Nelder-Mead", options=opts)
+        res.minimum, res.minimizer, res.frequencies = float(res.fun), res.x.copy(), freqs[i].copy()
+        pulse = current + dcrab_pulse(res.x, freqs[i], N, T)    # the pulse whose functional is res.fun
+        results.append(res)
+        minima.append(float(res.fun))
+    return results, minima, pulse
+
+
 def solve(prob, alg: Optional[GRAPE] = None, engine=None):
     """solve(::Problem, ::GRAPE) / solve(::EnsembleProblem, ::GRAPE).  With alg.penalties the minimised objective is the
-    figure of merit plus the C3 / C4 penalties, and `fidelity` (res.minimum, as src/solve.jl:139) includes them."""
+    figure of merit plus the C3 / C4 penalties, and `fidelity` (res.minimum, as src/solve.jl:139) includes them.
+    solve(prob, dCRAB(...)): `result` is the list of the super-iterations' Nelder-Mead results, `fidelity` the list of their
+    minima and `opti_pulses` the final (K, N) pulse (src/dCRAB.jl:114)."""
     if alg is None:
         raise TypeError("solve(prob) without an algorithm has no integrator in the reference either "
                         "(src/solve.jl:57,66); pass GRAPE(n_slices=...)")
+    if isinstance(alg, dCRAB):
+        eng = engine or make_engine(prob, alg)
+        try:
+            results, minima, pulse = _solve_dcrab(prob, alg, eng)
+        finally:
+            if engine is None:
+                eng.close()
+        cls = EnsembleSolutionResult if isinstance(prob, EnsembleProblem) else SolutionResult
+        return cls(results, minima, pulse, prob, alg)
     own = engine is None
     device_opt = getattr(alg, "optimizer", "host") == "device"
     batched = device_opt and not isinstance(alg, ADGRAPE) and not getattr(alg, "devices", None) and \

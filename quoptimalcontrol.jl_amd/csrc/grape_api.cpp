@@ -100,6 +100,9 @@ struct grape_ctx {
     bool exact_w1 = false;                     // exact gradient from the unitary flow's W_t dump (UnitaryGate, Hermitian generators, pair kernel)
     double *d_member_out = nullptr;
     double *d_partial = nullptr;
+    // grape_eval_fom's fast path (fom_small.hip), allocated by its first call: the members' F_k (E x B) and the workgroups'
+    // weighted rows (NB x B) -- its only device outputs besides d_fg
+    double *d_fom_member = nullptr, *d_fom_rows = nullptr;
     unsigned long long *d_stamps = nullptr;
     // host
     double *h_stage = nullptr;    // pinned + device-mapped, K*N + 1 doubles: x on the way in
@@ -441,6 +444,7 @@ static void free_all(grape_ctx *c)
     (void)hipFree(c->d_tp_q); (void)hipFree(c->d_tp_r); (void)hipFree(c->d_tp_m); (void)hipFree(c->d_tp_z); (void)hipFree(c->d_tp_vec); (void)hipFree(c->d_tp_a);
     (void)hipFree(c->d_x_bar);
     (void)hipFree(c->d_pen_w);
+    (void)hipFree(c->d_fom_member); (void)hipFree(c->d_fom_rows);
     (void)hipFree(c->d_ha); (void)hipFree(c->d_ha_norm); (void)hipFree(c->d_gc); (void)hipFree(c->d_gcn);
     (void)hipFree(c->d_act_a); (void)hipFree(c->d_act_b); (void)hipFree(c->d_act_bf); (void)hipFree(c->d_act_g);
     (void)hipFree(c->d_act_an); (void)hipFree(c->d_act_gn); (void)hipFree(c->d_act_bs); (void)hipFree(c->d_act_bo); (void)hipFree(c->d_act_bn); (void)hipFree(c->d_wrec); (void)hipFree(c->d_props_t);
@@ -2882,6 +2886,141 @@ extern "C" int grape_eval_batch_device(grape_ctx *c, int32_t n_x, const double *
         return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_batch_device: n_x must be in 1..grape_config.max_batch");
     if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, "grape_eval_batch_device: operators not set");
     return eval_device_impl(c, d_x, d_fg, stream, n_x);
+}
+
+// ---- ABI v8: the figure of merit without the gradient ----------------------------------------------------------------------
+// fast path of grape_eval_fom: single device, no exchange attached, kernel family 0
+static bool fom_fast(const grape_ctx *c) { return !c->is_group && !c->comm && c->ipc_ranks <= 1 && c->family == 0; }
+
+// The launches of the fast path on the context's stream: x upload, the forward-only kernel (reached through the sweep
+// launchers, SweepParams::fom_only) over the WHOLE ensemble and all n_x arrays at once -- it stores nothing per slice, so
+// neither a member-chunked workspace nor one sized for a single array restricts it -- and the fixed-order sum of the
+// workgroups' weighted rows with the penalty and the publication (launch_reduce_rows, Q = 1).  No event is recorded, no
+// workspace array, member row or stamp is written, c->evaluated is not touched.
+static int fom_issue(grape_ctx *c, const double *x, int n_x)
+{
+    const size_t kn = KN(c);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->d_fom_member) {
+        HIP_TRY(c, hipMalloc((void **)&c->d_fom_member, sizeof(double) * (size_t)c->cfg.n_ensemble * c->B));
+        HIP_TRY(c, hipMalloc((void **)&c->d_fom_rows, sizeof(double) * (size_t)c->NB * c->B));
+    }
+    shard_stage_x(c, x, n_x);
+    if (c->dev_pending) {                                   // order behind the last grape_eval_device
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_dev, 0));
+        c->dev_pending = false;
+    }
+    KernelLogScope log_scope(&c->kernel_log);
+    const double *d_x = c->d_x;
+    if (c->x_upload == 2)
+        d_x = c->d_x_bar;
+    else if (c->x_upload == 1)
+        HIP_TRY(c, grape::launch_copy(c->d_h_stage, c->d_x, (int)(kn * n_x), c->stream));
+    else
+        HIP_TRY(c, hipMemcpyAsync(c->d_x, c->h_stage, sizeof(double) * kn * n_x, hipMemcpyHostToDevice, c->stream));
+    c->kernel_log.clear();                                   // (the names of THIS call's evaluation kernels: not the x upload, as grape_eval)
+    grape::DoneSignal done;
+    done.counter = c->d_done_counter;
+    done.flag = c->d_h_flag;
+    done.seq = ++c->seq;
+    done.host_out = c->d_h_fg;
+    c->mf_wait = 0;
+    SweepParams p{};
+    p.ops = c->d_ops;
+    p.x = d_x;
+    p.wts = c->d_wts;
+    p.MPB = c->MPB;
+    p.BPX = c->NB;
+    p.n_x = n_x;
+    p.sk_magic = (uint32_t)((1ull << 32) / ((uint64_t)c->S * c->cfg.n_controls)) + 1u;
+    p.K = c->cfg.n_controls;
+    p.N = c->cfg.n_slices;
+    p.E = c->cfg.n_ensemble;
+    p.S = c->S;
+    p.LT = c->LT;
+    p.s_forced = c->cfg.expm_squarings;
+    p.variant = c->cfg.variant;
+    p.dt = c->cfg.duration / c->cfg.n_slices;
+    p.fom_only = 1;
+    p.fom_objective = c->cfg.objective;
+    p.fom_member = c->d_fom_member;
+    p.fom_rows = c->d_fom_rows;
+    // one workgroup holds the whole ensemble (single problems): its row is F, no reduce launch (penalties: the reduce adds them)
+    const bool direct = c->NB == 1 && n_x == 1 && c->direct_publish && !pen_active(c);
+    if (direct) {
+        p.direct_dst = done.host_out;
+        p.direct_flag = done.flag;
+        p.direct_seq = done.seq;
+    }
+    const int mode = c->unitary ? 2 : 0;
+    if (c->pair)
+        HIP_TRY(c, grape::launch_sweep_pair(c->cfg.n, c->cfg.sys_type != GRAPE_UNITARY_GATE, mode, p, c->stream));
+    else
+        HIP_TRY(c, grape::launch_sweep_small(c->cfg.n, c->cfg.sys_type != GRAPE_UNITARY_GATE, mode, p, c->stream));
+    if (direct)
+        return GRAPE_OK;
+    if (!pen_active(c)) {
+        if (c->mf_publish) {
+            done.mflags = c->d_h_flag + 8;
+            c->mf_wait = grape::reduce_rows_mflags(1, n_x);    // (the launch takes the same decision)
+        }
+        HIP_TRY(c, grape::launch_reduce_rows(c->d_fom_rows, c->d_fg, c->NB, 1, n_x, c->stream, done));
+        return GRAPE_OK;
+    }
+    // penalties belong to one control array each (DoneSignal::pen_x): one sum per array, the last one publishes them all
+    for (int b = 0; b < n_x; ++b) {
+        grape::DoneSignal db;
+        if (b == n_x - 1) {
+            db = done;
+            db.stage_base = c->d_fg;
+            db.n_total = n_x;
+        }
+        db.pen_x = d_x + (size_t)b * kn;
+        db.pen_w = c->d_pen_w;
+        db.pen_K = c->cfg.n_controls;
+        db.pen_N = c->cfg.n_slices;
+        HIP_TRY(c, grape::launch_reduce_rows(c->d_fom_rows + (size_t)b * c->NB, c->d_fg + b, c->NB, 1, 1, c->stream, db));
+    }
+    return GRAPE_OK;
+}
+
+extern "C" int grape_eval_fom(grape_ctx *c, int32_t n_x, const double *x, double *F, double *member_F)
+{
+    DeviceGuard guard;
+    if (!c) return GRAPE_ERR_INVALID_ARG;
+    if (!x || !F) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_fom: x or F is null");
+    if (n_x < 1 || n_x > c->B)
+        return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_fom: n_x must be in 1..max(1, grape_config.max_batch)");
+    if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, "grape_eval_fom: operators not set");
+    const size_t kn = KN(c), E = (size_t)c->cfg.n_ensemble;
+    if (!fom_fast(c)) {
+        // fallback: the full evaluation, its F bit for bit; member_F from the member rows, array by array
+        if (!member_F)
+            return eval_host(c, n_x, x, F, nullptr, "grape_eval_fom");
+        for (grape_ctx *s : c->is_group ? c->sub : std::vector<grape_ctx *>{c})
+            if (!s->d_member_out)
+                return fail(c, GRAPE_ERR_NOT_READY, "grape_eval_fom: member_F needs a context created with GRAPE_FLAG_MEMBER_RESULTS");
+        for (int b = 0; b < n_x; ++b) {
+            int rc = eval_host(c, 1, x + (size_t)b * kn, F + b, nullptr, "grape_eval_fom");
+            if (rc) return rc;
+            rc = grape_get_member_results(c, member_F + (size_t)b * E, nullptr);
+            if (rc) return rc;
+        }
+        return GRAPE_OK;
+    }
+    int rc = ipc_check(c);
+    if (rc) return rc;
+    rc = fom_issue(c, x, n_x);
+    if (rc) return rc;
+    rc = wait_flag(c);                                       // F is in host memory
+    if (rc) return rc;
+    for (int b = 0; b < n_x; ++b) F[b] = c->h_fg[b];
+    if (member_F) {                                          // (the kernel that wrote them has finished: its successor published)
+        HIP_TRY(c, hipMemcpyAsync(member_F, c->d_fom_member, sizeof(double) * E * n_x, hipMemcpyDeviceToHost, c->stream));
+        rc = wait_stream(c, c->stream);
+        if (rc) return rc;
+    }
+    return GRAPE_OK;
 }
 
 // group accessors: the shard that owns `member`

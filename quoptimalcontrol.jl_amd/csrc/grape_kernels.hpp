@@ -106,7 +106,16 @@ struct SweepParams {
     int32_t tune;         // pair kernel, set by its launcher from GRAPE_PAIR_TUNE (tuning experiments; 0 in the product)
     int32_t vec;          // pair kernel, general flow, left multiplication, n = 4: the states are n x 1 (column 0 of the padded
                           // matrices) -- the sweep back runs on vectors and phase A stores no in-chunk prefixes
+    // ABI v8, grape_eval_fom (fom_small.hip): the figure of merit WITHOUT the gradient.  launch_sweep_small / launch_sweep_pair
+    // hand a launch with fom_only set to the forward-only kernels: no workspace array, no member_out / block_out row and no
+    // stamp is touched; E, BPX are the WHOLE ensemble's and n_x any number of control arrays (nothing is stored per slice)
+    double *fom_member;   // (E, n_x) unweighted F_k, member index fastest
+    double *fom_rows;     // (BPX, n_x) sum over the workgroup's members of w_k F_k: launch_reduce_rows with Q = 1 sums them
+    int32_t fom_only;
+    int32_t fom_objective;   // grape_objective: 0 fom_func, 1 C1(Xt, U Xi [U']) for every system type
 };
+// fom_small.hip; reached through launch_sweep_small (pair = false) / launch_sweep_pair (pair = true) only
+hipError_t launch_fom_small(int n, int sandwich, int mode, bool pair, const SweepParams &p, hipStream_t stream);
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel, device) instead of once per launch: the driver call sits
 // on the host's critical path in front of an evaluation's launches (grape_api.cpp; thread-safe: group contexts launch from one

@@ -615,6 +615,8 @@ static hipError_t launch_ns(int mode, const SweepParams &p, hipStream_t stream)
 
 hipError_t launch_sweep_small(int n, int sandwich, int mode, const SweepParams &p, hipStream_t stream)
 {
+    if (p.fom_only)                                  // grape_eval_fom: the forward-only kernel (fom_small.hip)
+        return launch_fom_small(n, sandwich, mode, false, p, stream);
     switch (n * 2 + (sandwich ? 1 : 0)) {
     case 4: return launch_ns<2, 0>(mode, p, stream);
     case 5: return launch_ns<2, 1>(mode, p, stream);

@@ -28,7 +28,7 @@ FLAG_FORCE_COLLECTIVE = 32
 FLAG_TIME_SAMPLED = 64
 FLAG_GROUP_PEER_SUM = 128
 MAX_DEVICES = 8
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 STATUS = {0: "GRAPE_OK", -1: "GRAPE_ERR_INVALID_ARG", -2: "GRAPE_ERR_UNSUPPORTED",
           -3: "GRAPE_ERR_NO_DEVICE", -4: "GRAPE_ERR_HIP", -5: "GRAPE_ERR_NOT_READY",
@@ -37,7 +37,7 @@ STATUS = {0: "GRAPE_OK", -1: "GRAPE_ERR_INVALID_ARG", -2: "GRAPE_ERR_UNSUPPORTED
 # every symbol include/grape_hip.h declares
 EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_operators", "grape_set_penalties",
            "grape_comm_unique_id", "grape_comm_attach", "grape_ipc_export", "grape_ipc_attach",
-           "grape_eval", "grape_eval_device", "grape_eval_batch", "grape_eval_batch_device", "grape_lbfgs", "grape_lbfgs_get_trace",
+           "grape_eval", "grape_eval_device", "grape_eval_batch", "grape_eval_batch_device", "grape_eval_fom", "grape_lbfgs", "grape_lbfgs_get_trace",
            "grape_get_member_results", "grape_get_trajectory",
            "grape_get_kernel_time", "grape_get_kernel_samples", "grape_get_kernel_names", "grape_get_group_timing", "grape_get_phase_stamps",
            "grape_get_info",
@@ -129,6 +129,7 @@ def load_library():
     L.grape_eval_device.argtypes = [vp, vp, vp, vp]
     L.grape_eval_batch.argtypes = [vp, i32, vp, vp, vp]
     L.grape_eval_batch_device.argtypes = [vp, i32, vp, vp, vp]
+    L.grape_eval_fom.argtypes = [vp, i32, vp, vp, vp]
     L.grape_lbfgs.argtypes = [vp, vp, C.POINTER(GrapeLbfgsOptions), vp, C.POINTER(GrapeLbfgsResult)]
     L.grape_get_member_results.argtypes = [vp, vp, vp]
     L.grape_get_trajectory.argtypes = [vp, i32, vp, vp, vp]
@@ -387,6 +388,25 @@ class GrapeEngine:
         G = np.empty((n_x, self.N, self.K))
         self._check(self._lib.grape_eval_batch(self._h, n_x, _p(xf), _p(F), _p(G)))
         return F, np.ascontiguousarray(np.swapaxes(G, 1, 2))
+
+    def fom(self, x, members=False):
+        """grape_eval_fom: the figure of merit WITHOUT the gradient (pw_evolve + fom_func / C1).  x (K,N) -> F, or
+        (F, member_F (E,)) with members=True; x (B,K,N), B <= max_batch -> F (B,) and member_F (B,E).  F is what eval(x)
+        returns as F (penalties included), member_F the members' unweighted F_k.  For n = 2..4 on one device a
+        forward-only kernel does the work (no propagator is stored, no backward sweep); elsewhere the full evaluation
+        runs and its F is returned bit for bit."""
+        x = np.asarray(x, dtype=np.float64)
+        single = x.ndim == 2
+        if (x.shape if single else x.shape[1:]) != (self.K, self.N) or x.ndim not in (2, 3):
+            raise ValueError(f"x must be ({self.K},{self.N}) or (n_x,{self.K},{self.N})")
+        n_x = 1 if single else x.shape[0]
+        xf = np.ascontiguousarray(np.swapaxes(x, -1, -2))          # each (K,N) column-major
+        F = np.empty(n_x)
+        mF = np.empty((n_x, self.E)) if members else None
+        self._check(self._lib.grape_eval_fom(self._h, n_x, _p(xf), _p(F), _p(mF)))
+        if single:
+            return (float(F[0]), mF[0]) if members else float(F[0])
+        return (F, mF) if members else F
 
     def eval_device(self, d_x_ptr, d_fg_ptr, stream=0):
         """grape_eval_device with raw device pointers (e.g. torch tensor .data_ptr())."""
