@@ -66,15 +66,17 @@ constexpr int flip_block(int r) { return (r + N / 2) % N; }
 // C = A * B.   C_loc[r, jl] = sum_kl A_loc[r, kl] B_loc[kl, jl] + Apar[rbar, kl] B_loc[NC + kl, jl]
 // (k = own block: A's column is mine; k = partner block: A's column is the partner's, whose local
 // row order has the blocks swapped).  CONJ_A / CONJ_B conjugate the operand elementwise.
-template <int N>
-GRAPE_DEV void pmul(PMat<N> &c, const PMat<N> &a, const PMat<N> &apar, const PMat<N> &b)
+// SEEDED: C = S + A * B -- the accumulators start from S instead of zero (S may be C itself), so the
+// addend costs no instruction of its own: the first FMA of every chain takes it as its third operand.
+template <int N, bool SEEDED>
+GRAPE_DEV void pmul_impl(PMat<N> &c, const PMat<N> &s, const PMat<N> &a, const PMat<N> &apar, const PMat<N> &b)
 {
     constexpr int NC = N / 2;
 #pragma unroll
     for (int jl = 0; jl < NC; ++jl)
 #pragma unroll
         for (int r = 0; r < N; ++r) {
-            double sr = 0.0, si = 0.0;
+            double sr = SEEDED ? s.re[r + jl * N] : 0.0, si = SEEDED ? s.im[r + jl * N] : 0.0;
 #pragma unroll
             for (int kl = 0; kl < NC; ++kl) {
                 {
@@ -93,6 +95,18 @@ GRAPE_DEV void pmul(PMat<N> &c, const PMat<N> &a, const PMat<N> &apar, const PMa
             c.re[r + jl * N] = sr;
             c.im[r + jl * N] = si;
         }
+}
+
+template <int N>
+GRAPE_DEV void pmul(PMat<N> &c, const PMat<N> &a, const PMat<N> &apar, const PMat<N> &b)
+{
+    pmul_impl<N, false>(c, c, a, apar, b);
+}
+
+template <int N>
+GRAPE_DEV void pmul_add(PMat<N> &c, const PMat<N> &s, const PMat<N> &a, const PMat<N> &apar, const PMat<N> &b)
+{
+    pmul_impl<N, true>(c, s, a, apar, b);
 }
 
 // C = A^H * B.   C_loc[(0,rl), jl] = sum_s conj(A_loc[s, rl]) B_loc[s, jl]
@@ -302,15 +316,23 @@ GRAPE_DEV void psquare_antihermitian(PMat<N> &c, const PMat<N> &g, const PMat<N>
     }
 }
 
-// p = exp(g), degree-8 Taylor polynomial in 3 products + scaling/squaring: cmat.hpp's expm_t8 on pair matrices
-// (same coefficients, same operation order per element, so both layouts give the same propagators up to
-// the summation order inside the products).  g is destroyed.
+// p = exp(g), degree-8 Taylor polynomial in 3 products + scaling/squaring: cmat.hpp's expm_t8 on pair matrices, with the
+// combination passes trimmed to one FMA per term:
+//   * the polynomial's low part I + g + y2 a2 SEEDS the accumulators of the last product (pmul_add) instead of being added
+//     in a pass of its own behind it (where no squaring follows, s = 0: see below) -- and g, a2 are dead before that
+//     product starts, which is where the register pressure of the whole sweep peaks;
+//   * the first combination is kept monic in a2, t/x2 = (x1/x2) g + a2, so that it is one FMA; the factor x2 that a4 and
+//     u then lack is folded into the coefficients of the last product's right operand (u/x2)(x2 t) = u t.
+// Against expm_t8 the propagators differ in the summation order of the last product and by the rounding of the folded
+// coefficients: last bits.  g is destroyed.
 // ANTIHERM: g is known to be anti-Hermitian (unitary flow): half the partner traffic for g and g^2, and the
 // Hermitian half product for g^2.  norm_bound >= 0: an upper bound of |g|_1 supplied by the caller.
 template <int N, bool ANTIHERM = false>
 GRAPE_DEV void pexpm_t8(PMat<N> &p, PMat<N> &g, int s_forced, double norm_bound = -1.0)
 {
     constexpr int NE = N * PMat<N>::NC;
+    constexpr double c1 = kX1 / kX2, c3 = kX3 / kX2;                       // t / x2, u / x2
+    constexpr double c4 = kX2 * kX4, c5 = kX2 * kX5, c6 = kX2 * kX6, c7 = kX2 * kX2 * kX7;    // x2 t, in a4 / x2
     const int s = s_forced >= 0 ? s_forced : squarings_for(norm_bound >= 0.0 ? norm_bound : pnorm1_bound(g));
     if (s > 0) {
         const double sc = ldexp(1.0, -s);
@@ -330,39 +352,45 @@ GRAPE_DEV void pexpm_t8(PMat<N> &p, PMat<N> &g, int s_forced, double norm_bound 
     }
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
-        t.re[e] = fma(kX1, g.re[e], kX2 * a2.re[e]);
-        t.im[e] = fma(kX1, g.im[e], kX2 * a2.im[e]);
+        t.re[e] = fma(c1, g.re[e], a2.re[e]);
+        t.im[e] = fma(c1, g.im[e], a2.im[e]);
     }
     if (ANTIHERM)
         partner_of_hermitian<N, 1>(par, a2);
     else
         fetch_partner(par, a2);
-    pmul(a4, a2, par, t);
+    pmul(a4, a2, par, t);                          // a2 (t / x2) = g^4-part / x2
     PMat<N> u;
 #pragma unroll
     for (int jl = 0; jl < PMat<N>::NC; ++jl)
 #pragma unroll
         for (int r = 0; r < N; ++r) {
             const int e = r + jl * N;
-            u.re[e] = fma(kX3, a2.re[e], a4.re[e]);
-            u.im[e] = fma(kX3, a2.im[e], a4.im[e]);
-            t.re[e] = fma(kX5, g.re[e], fma(kX6, a2.re[e], kX7 * a4.re[e]));
-            t.im[e] = fma(kX5, g.im[e], fma(kX6, a2.im[e], kX7 * a4.im[e]));
-            if (r == jl)
-                t.re[e] += kX4;
+            u.re[e] = fma(c3, a2.re[e], a4.re[e]);
+            u.im[e] = fma(c3, a2.im[e], a4.im[e]);
+            t.re[e] = fma(c5, g.re[e], fma(c6, a2.re[e], c7 * a4.re[e]));
+            t.im[e] = fma(c5, g.im[e], fma(c6, a2.im[e], c7 * a4.im[e]));
+            p.re[e] = fma(kY2, a2.re[e], g.re[e]);           // the seed: I + g + y2 a2
+            p.im[e] = fma(kY2, a2.im[e], g.im[e]);
+            if (r == jl) {
+                t.re[e] += c4;
+                p.re[e] += 1.0;
+            }
         }
     fetch_partner(par, u);
-    pmul(p, u, par, t);                            // A8
+    if (s == 0) {
+        pmul_add(p, p, u, par, t);                 // A8
+    } else {
+        // squarings follow and double whatever the last bits hold, s times: the product is summed on its own and added once
+        // (measured: seeded, the 4 x 4 big-norm fixture's propagators miss their 2e-13 bar with 2.7e-13; summed apart they keep it)
+        PMat<N> q;
+        pmul(q, u, par, t);
 #pragma unroll
-    for (int jl = 0; jl < PMat<N>::NC; ++jl)
-#pragma unroll
-        for (int r = 0; r < N; ++r) {
-            const int e = r + jl * N;
-            p.re[e] += fma(kY2, a2.re[e], g.re[e]);
-            p.im[e] += fma(kY2, a2.im[e], g.im[e]);
-            if (r == jl)
-                p.re[e] += 1.0;
+        for (int e = 0; e < NE; ++e) {
+            p.re[e] += q.re[e];
+            p.im[e] += q.im[e];
         }
+    }
     for (int i = 0; i < s; ++i) {                  // undo the scaling
         fetch_partner(par, p);
         pmul(t, p, par, p);

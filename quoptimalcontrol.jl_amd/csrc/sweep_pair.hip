@@ -68,6 +68,23 @@ GRAPE_DEV void pstore_ws(double2 *__restrict__ base, size_t stride, const PMat<N
             base[(size_t)gelem<N>(q, r, jl) * stride] = make_double2(m.re[r + jl * N], m.im[r + jl * N]);
 }
 
+// The same store with the address split as the hardware wants it: element (r, jl) of a lane of parity q lies
+//   [((r / NC) ^ q) NC + q NC n] + [(r % NC) + jl n]   rows of `stride` double2 into the slice -- a part that depends on the lane
+// only through the row block (voff[r / NC], in BYTES, the chunk's 16 ch bytes included) and a wave-uniform part, which goes into
+// the scalar base of the store.  Two address registers per lane instead of one 64-bit offset per element (16 VGPRs at n = 4,
+// live through the whole of phase A).
+template <int N>
+GRAPE_DEV void pstore_ws_split(double2 *__restrict__ sbase, const unsigned (&voff)[2], size_t stride, const PMat<N> &m)
+{
+#pragma unroll
+    for (int jl = 0; jl < N / 2; ++jl)
+#pragma unroll
+        for (int r = 0; r < N; ++r) {
+            char *row = reinterpret_cast<char *>(sbase + (size_t)((r % (N / 2)) + jl * N) * stride);
+            *reinterpret_cast<double2 *>(row + voff[r / (N / 2)]) = make_double2(m.re[r + jl * N], m.im[r + jl * N]);
+        }
+}
+
 template <int N>
 GRAPE_DEV void pload_ws(PMat<N> &m, const double2 *__restrict__ base, size_t stride, int q)
 {
@@ -394,6 +411,11 @@ __global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restr
     double2 *__restrict__ Xw = p.states + wbase;
     double *__restrict__ out = p.member_out + (size_t)k * ((size_t)K * Nsl + 1);
     const int t0 = ch * S;
+    // the lane's two row-block offsets into a slice of P_t (pstore_ws_split, PBuf) and the member's wave-uniform base
+    const unsigned p_rowb = (unsigned)CH * 16u;
+    const unsigned p_voff[2] = {(unsigned)(par * NC + par * NC * N) * p_rowb + (unsigned)ch * 16u,
+                                (unsigned)((1 - par) * NC + par * NC * N) * p_rowb + (unsigned)ch * 16u};
+    double2 *__restrict__ const p_Pk = p.props + (size_t)k * (GRAPE_PLAYOUT ? 1 : S) * NN * stride;
     unsigned long long *__restrict__ st =
         p.stamps ? p.stamps + ((size_t)k * W + wave) * kStampSlots : nullptr;
     if (st && lane == 0)
@@ -462,18 +484,20 @@ __global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restr
         pexpm_t8<N, UNI>(P, G, p.s_forced, nb);
         __builtin_amdgcn_sched_barrier(0);
         if (!(GRAPE_ABL & 2))
-        pstore_ws(Pw + (size_t)j * pstep, stride, P, par);
+        pstore_ws_split(p_Pk + (size_t)j * pstep, p_voff, stride, P);
         if (UNI && XGLDS && p.plast_lds && j == S - 1) {          // the backward sweep's first operand stays on chip
 #pragma unroll
             for (int e = 0; e < NE; ++e)
                 s_plast[e * blockDim.x + threadIdx.x] = make_double2(P.re[e], P.im[e]);
         }
-        if (GRAPE_ABL & 4) { Qout = Qin; Qout.re[0] += P.re[1]; } else if (first) {
-            Qout = P;
+        PMat<N> R;
+        if (GRAPE_ABL & 4) { R = Qin; R.re[0] += P.re[1]; } else if (first) {
+            R = P;
         } else {
             fetch_partner(Ppar, P);
-            pmul(Qout, P, Ppar, Qin);
+            pmul(R, P, Ppar, Qin);
         }
+        Qout = R;
         if (MODE == PMODE_GENERAL && !VEC)            // in-chunk prefix product, read back in phase D
             pstore_ws(Xw + (size_t)j * NN * stride, stride, Qout, par);
         __builtin_amdgcn_sched_barrier(0);
@@ -513,20 +537,18 @@ __global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restr
     // backward sweep's propagator ring (see PBuf): addresses, and with GRAPE_PD_EARLY the first one or two slices requested
     // BEFORE the scan -- HBM is idle during phase B and the sweep then has two slices fewer to wait for
     PBuf bA, bB;
-    const unsigned pd_rowb = (unsigned)CH * 16u;
-    const unsigned pd_voff0 = (unsigned)(10 * par) * pd_rowb + (unsigned)ch * 16u;
-    const unsigned pd_voff1 = (unsigned)(2 + 6 * par) * pd_rowb + (unsigned)ch * 16u;
-    const double2 *pd_Pk = p.props + (size_t)k * (GRAPE_PLAYOUT ? 1 : S) * NN * stride;   // wave-uniform
-    auto pd_issue = [&](PBuf &b, int jj) {
-        const double2 *s0 = pd_Pk + (size_t)max(jj, 0) * pstep;
-        pbuf_issue(b, pd_voff0, pd_voff1, s0, s0 + CH, s0 + 4 * CH, s0 + 5 * CH);
+    // the sandwich flow's scan epilogue holds six matrices: a second buffer in flight across it does not fit in 256 registers
+    constexpr int PD_EARLY = (SAND && GRAPE_PD_EARLY > 1) ? 1 : GRAPE_PD_EARLY;
+    auto pd_issue = [&](PBuf &b, int jj) {                 // (n = 4: p_voff = rows 10 par and 2 + 6 par)
+        const double2 *s0 = p_Pk + (size_t)max(jj, 0) * pstep;
+        pbuf_issue(b, p_voff[0], p_voff[1], s0, s0 + CH, s0 + 4 * CH, s0 + 5 * CH);
     };
     // (no wait in front: phase A's stores may still be draining; the sweep starts with vmcnt(0), which covers both)
     auto pd_early = [&]() {
-        if constexpr (PDASM && GRAPE_PD_EARLY >= 1) {
+        if constexpr (PDASM && PD_EARLY >= 1) {
             const int jm0 = (XGLDS && p.plast_lds) ? S - 2 : S - 1;
             pd_issue(bA, jm0);
-            if (GRAPE_PD_EARLY >= 2)
+            if (PD_EARLY >= 2)
                 pd_issue(bB, jm0 - 1);
         }
     };
@@ -596,21 +618,27 @@ __global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restr
                 lds_barrier();
             else
                 __syncthreads();
-            PMat<N> T, Tp, C0, xi_m, xi_o, xt_m, xt_o;
+            PMat<N> T, C0, xi_m, xi_o;
             pload_lds(T, &s_tot[1][wbase_tot][par * NE]);
             if (SAND) {
-                pload_lds(Tp, &s_tot[1][wbase_tot][(1 - par) * NE]);
-                pload_lds(xi_m, sXi);
-                pload_lds(xi_o, sXi_o);
-                pload_lds(xt_m, sXt);
-                pload_lds(xt_o, sXt_o);
-            }
-            if (SAND) {
+                // every operand is read from LDS right in front of its first use: six matrices live at most (with the two
+                // propagator buffers already in flight that is all the register file holds)
                 PMat<N> Em, Ep;
-                pmul(tmp, xt_m, xt_o, T);            // Xt T
-                pmul_ah_b(Em, T, Tp, tmp);           // E = T' Xt T
+                {
+                    PMat<N> xt_m, xt_o;
+                    pload_lds(xt_m, sXt);
+                    pload_lds(xt_o, sXt_o);
+                    pmul(tmp, xt_m, xt_o, T);        // Xt T
+                }
+                {
+                    PMat<N> Tp;
+                    pload_lds(Tp, &s_tot[1][wbase_tot][(1 - par) * NE]);
+                    pmul_ah_b(Em, T, Tp, tmp);       // E = T' Xt T
+                }
+                pload_lds(xi_m, sXi);
                 ptrace_ah_b(zr, zi, xi_m, Em);       // tr(Xi' E) = tr(X_t' L_t) for every t
                 fetch_partner(Ep, Em);
+                pload_lds(xi_o, sXi_o);
                 pmul_a_bh(C0, xi_m, xi_o, Em, Ep);   // Xi E'
                 pmul_ah_b(tmp, Em, Ep, xi_m);        // E' Xi
 #pragma unroll
@@ -827,15 +855,15 @@ __global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restr
             };
             const bool plast = XGLDS && p.plast_lds;
             const int jm = plast ? S - 2 : S - 1;                 // the first slice that comes from memory
-            if (GRAPE_PD_EARLY >= 1) {
+            if (PD_EARLY >= 1) {
                 pbuf_wait<0>(bA);                                 // issued before the scan: long landed
-                if (GRAPE_PD_EARLY >= 2)
+                if (PD_EARLY >= 2)
                     pbuf_wait<0>(bB);
             } else {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // phase A's stores are long done: the count starts at zero
                 pd_issue(bA, jm);
             }
-            if (GRAPE_PD_EARLY < 2)
+            if (PD_EARLY < 2)
                 pd_issue(bB, jm - 1);
             if (plast) {
                 products(j, PA);

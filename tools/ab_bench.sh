@@ -5,8 +5,9 @@
 #   tools/ab_bench.sh build/r3tree 10 > profiles/r05_C3_ab.txt
 BASE=${1:-build/r3tree}
 ROUNDS=${2:-10}
-ARGS="--steps 20 --warmup 5 --no-extra --no-cpu-baseline"
 full() { grep -q -e '"--full"' "$1/bench.py" && echo --full; }      # the box clock is a --full figure where --full exists
+ARGS=${AB_ARGS:-"--steps 20 --warmup 5 --no-extra --no-cpu-baseline"}     # AB_ARGS="--gpus 1 --steps 300 --warmup 30": the driver's own pass
+[ -n "$AB_ARGS" ] && full() { :; }
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 pick='import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d["roofline"]
