@@ -284,6 +284,34 @@ int grape_set_operators(grape_ctx *ctx, const double *A, const double *B, const 
  * grape_set_penalties with the same weights, just as every rank passes the same x. */
 int grape_set_penalties(grape_ctx *ctx, const double *amp_w, const double *var_w);
 
+/* Pulses restricted to a basis (Fourier / CRAB series, splines, Slepians, the impulse response of an AWG filter), with the
+ * gradient with respect to the coefficients -- "parameter mode".  Additive to ABI v8.
+ *   x[c,t] = x0[c,t] + sum_{m<M} theta[c,m] * phi_b[t,m],   b = (n_bases == 1 ? 0 : c)
+ *   phi  host f64 (N, M, n_bases) column-major, phi[t + N*(m + M*b)];  n_bases is 1 (one basis for every control) or K
+ *   x0   host f64 (K, N), nullable (NULL = 0);  M = n_params, 1 <= M <= N.  phi == NULL or n_params == 0: basis off.
+ * With a basis in force every `x` argument of grape_eval, grape_eval_device, grape_eval_batch, grape_eval_batch_device,
+ * grape_eval_fom and grape_lbfgs (x0 and x_min; its vectors are K*M long) is theta, (K, M) column-major theta[c + K*m]
+ * (batches (K, M, n_x)), every returned G is (K, M), and d_fg is f64[K*M + 1] per control array:
+ *   F(theta) is the F of the physical pulse, the penalties of grape_set_penalties evaluated on the physical x;
+ *   G_theta[c,m] = sum_t G_tot[c,t] * phi_b[t,m], G_tot including the penalty gradient.
+ * The expansion runs on the device in front of the evaluation (basis_expand_kernel: m ascending, one FMA per term), the
+ * projection behind the complete summed row -- after the cross-device sum or exchange, after the penalty -- in a fixed tree
+ * over t (basis_project_kernel): results are bitwise reproducible call to call, and F is bit for bit what a context
+ * without a basis returns through the device-pointer entry points for the expanded pulse.  grape_get_member_results,
+ * grape_get_trajectory and the member_F of grape_eval_fom stay in physical slice space ((K, N) rows, per-slice data).
+ * Valid any time after grape_create, before or after grape_set_operators (the basis persists across it); ordered behind an
+ * in-flight grape_eval_device as grape_set_operators is.  Non-finite phi or x0, n_params outside 1..N, n_bases other than
+ * 1 or K: GRAPE_ERR_INVALID_ARG, and the previous basis stays in force (as after any other failure).  Switching the basis
+ * off restores the slice-mode behaviour exactly; a context that never calls this launches the kernels it always did.
+ * Multi-device contexts expand once on the first device, in front of the fan-out of x.  With grape_comm_attach /
+ * grape_ipc_attach every rank sets the same basis and expands its own copy; every rank projects the exchanged row. */
+int grape_set_basis(grape_ctx *ctx, int32_t n_params, int32_t n_bases, const double *phi, const double *x0);
+
+/* The physical pulse of a parameter array, expanded ON THE DEVICE by the kernel the evaluations use:
+ *   theta host f64 (K, M)      x host f64 (K, N)
+ * Blocking; ordered behind an in-flight grape_eval_device.  Without a basis x = theta ((K, N) both). */
+int grape_get_controls(grape_ctx *ctx, const double *theta, double *x);
+
 /* The closure body, src/solve.jl:164-196 (E>1) / :75-100 (E=1):
  *   F = sum_k w_k F_k ,  G[c,t] = sum_k w_k g_k[c,t]   with (F_k, g_k) = _fom_and_gradient_GRAPE!.
  * x: host (K,N) f64.  F (nullable): host f64.  G (nullable): host (K,N) f64 -- Optim passes

@@ -136,6 +136,31 @@ function set_penalties!(ctx::GrapeContext, pf)
                      amp === nothing ? C_NULL : amp, var === nothing ? C_NULL : var))
 end
 
+# grape_set_basis: from here on every x handed to this context is theta (K, M) and every gradient is with respect to theta:
+#   x[c,t] = x0[c,t] + sum_m theta[c,m] phi[t,m];  phi (N, M) for every control or (N, M, K), one basis per control -- Julia's
+# column-major arrays are the layout the library reads.  phi = nothing switches the basis off.  (Not executed where this
+# file was written: no Julia toolchain there; the Python binding makes the same two calls and is tested on the GPU.)
+function set_basis!(ctx::GrapeContext, phi::Union{Nothing,Array{Float64}}, x0::Union{Nothing,Matrix{Float64}} = nothing)
+    if phi === nothing
+        return check(ctx, ccall((:grape_set_basis, libgrape), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}),
+                                ctx.handle, Int32(0), Int32(1), C_NULL, C_NULL))
+    end
+    size(phi, 1) == ctx.N && (ndims(phi) == 2 || (ndims(phi) == 3 && size(phi, 3) == ctx.K)) ||
+        throw(DimensionMismatch("phi must be (n_slices, M) or (n_slices, M, n_controls)"))
+    x0 === nothing || size(x0) == (ctx.K, ctx.N) || throw(DimensionMismatch("x0 must be (n_controls, n_slices)"))
+    GC.@preserve phi x0 check(ctx, ccall((:grape_set_basis, libgrape), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}),
+                                         ctx.handle, Int32(size(phi, 2)), Int32(ndims(phi) == 3 ? ctx.K : 1), phi,
+                                         x0 === nothing ? C_NULL : x0))
+end
+
+"grape_get_controls: the physical pulse (K, N) of a parameter array theta (K, M), expanded on the device."
+function controls(ctx::GrapeContext, theta::Matrix{Float64})
+    x = Matrix{Float64}(undef, ctx.K, ctx.N)
+    GC.@preserve theta x check(ctx, ccall((:grape_get_controls, libgrape), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}),
+                                          ctx.handle, theta, x))
+    x
+end
+
 check(ctx::GrapeContext, rc) =
     rc == 0 || error("libgrape_hip: ", unsafe_string(ccall((:grape_last_error, libgrape), Cstring, (Ptr{Cvoid},), ctx.handle)))
 

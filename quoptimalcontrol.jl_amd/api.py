@@ -12,6 +12,8 @@ the reference's own tests (test/state_transfer_tests.jl, test/unitary_gate_tests
   C1(KT, KN)                                                   src/cost_functions.jl:13-17
   C3(u), C4(u), PenaltyFunctionals(weights, functions)         src/cost_functions.jl:29-39, :66-69
   dCRAB(n_slices=..., n_freq=2, n_coeff=2)                     src/dCRAB.jl:2-5, :13-89
+  fourier_basis(n_slices, duration, freqs), GRAPE(basis=...)   new: gradient-based optimisation over the coefficients of
+                                                               dCRAB's ansatz (or any other basis), grape_set_basis
 
 What differs, on purpose: the body of the (F, G, x) closure is one call into libgrape_hip.so
 (engine.GrapeEngine) instead of _fom_and_gradient_GRAPE!, and the L-BFGS driver is SciPy's
@@ -92,6 +94,11 @@ class GRAPE:
     peer_sum: bool = False         # with `devices`: GRAPE_FLAG_GROUP_PEER_SUM (sum on the first device, ids may repeat)
     penalties: Any = None          # PenaltyFunctionals of C3 / C4 (new: the reference's solvers call none): added to the
                                    # objective on the device (grape_set_penalties); res.minimum / fidelity then include them
+    basis: Any = None              # (N, M) or (K, N, M) basis functions (new; e.g. fourier_basis): the optimiser -- host or
+                                   # device -- runs over the coefficients theta (K, M) of x = basis_offset + theta @ basis.T,
+                                   # expanded and projected on the device (grape_set_basis).  The start is the least-squares
+                                   # fit of the problem's guess; the result carries the physical pulse and `parameters`
+    basis_offset: Any = None       # (K, N) pulse the expansion is added to; None: zero
 
 
 @dataclass
@@ -147,6 +154,19 @@ def dcrab_pulse(coeffs, freqs, n_slices, duration):
     return c[:, 0:1] * np.cos(wt) + c[:, 1:2] * np.sin(wt)
 
 
+def fourier_basis(n_slices, duration, freqs):
+    """The functions of dCRAB's ansatz as a basis for GRAPE(basis=...): (n_slices, 2 len(freqs)) with columns
+    cos(w_0 t), sin(w_0 t), cos(w_1 t), sin(w_1 t), ... on dcrab_pulse's grid t = 0, dt, ..., T - dt.  Row j of
+    dcrab_pulse(c, w, N, T) is c[j] @ fourier_basis(N, T, [w[j]]).T."""
+    freqs = np.asarray(freqs, dtype=np.float64).reshape(-1)
+    t = np.arange(int(n_slices), dtype=np.float64) * (float(duration) / int(n_slices))
+    wt = freqs[:, None] * t[None, :]
+    out = np.empty((int(n_slices), 2 * freqs.shape[0]))
+    out[:, 0::2] = np.cos(wt).T
+    out[:, 1::2] = np.sin(wt).T
+    return out
+
+
 @dataclass
 class SolutionResult:
     result: Any
@@ -154,6 +174,7 @@ class SolutionResult:
     opti_pulses: Any
     problem: Problem
     alg: GRAPE
+    parameters: Any = None         # GRAPE(basis=...): the optimal coefficients theta (K, M); opti_pulses is their pulse
 
 
 @dataclass
@@ -163,6 +184,7 @@ class EnsembleSolutionResult:
     opti_pulses: Any
     problem: EnsembleProblem
     alg: GRAPE
+    parameters: Any = None
 
 
 def C1(KT, KN):
@@ -419,6 +441,18 @@ def _device_lbfgs(eng, x0, options):
                            success=info["status"] in (0, 1), device_lbfgs=info)
 
 
+def _basis_start(eng, guess, basis, offset):
+    """GRAPE(basis=...): puts the engine into parameter mode and returns the start theta (K, M), the least-squares fit of
+    guess - offset in the basis (per control when every control has its own)."""
+    basis = np.asarray(basis, dtype=np.float64)
+    off = None if offset is None else np.asarray(offset, dtype=np.float64).reshape(guess.shape)
+    eng.set_basis(basis, off)
+    r = guess if off is None else guess - off
+    if basis.ndim == 2:
+        return np.ascontiguousarray(np.linalg.lstsq(basis, r.T, rcond=None)[0].T)
+    return np.array([np.linalg.lstsq(basis[c], r[c], rcond=None)[0] for c in range(guess.shape[0])])
+
+
 def _solve_dcrab(prob, alg, eng):
     """src/dCRAB.jl:13-89 on the device functional.  Deviations, on purpose: the start vector has n_coeff K entries (the
     reference hard-codes `reshape(..., 4)`, :71, i.e. two controls); and Nelder-Mead's first simplex is SciPy's default one
@@ -478,14 +512,25 @@ def solve(prob, alg: Optional[GRAPE] = None, engine=None):
     batched = device_opt and not isinstance(alg, ADGRAPE) and not getattr(alg, "devices", None) and \
         alg.optim_options.get("line_search") == "ladder"          # the ladder search probes several step lengths per launch
     eng = engine or make_engine(prob, alg, **({"max_batch": 4} if batched else {}))
+    basis = getattr(alg, "basis", None)
+    params = None
     try:
         guess = np.asarray((prob.prob if isinstance(prob, EnsembleProblem) else prob).guess, float)
-        if device_opt:
-            res = _device_lbfgs(eng, guess, alg.optim_options)
-        else:
-            res = _lbfgs(lambda x: eng.eval(x), guess, alg.optim_options)
+        if basis is not None:
+            guess = _basis_start(eng, guess, basis, getattr(alg, "basis_offset", None))
+        try:
+            if device_opt:
+                res = _device_lbfgs(eng, guess, alg.optim_options)
+            else:
+                res = _lbfgs(lambda x: eng.eval(x), guess, alg.optim_options)
+            pulse = res.minimizer
+            if basis is not None:                              # the physical pulse, from the kernel the evaluations used
+                params, pulse = res.minimizer, eng.controls(res.minimizer)
+        finally:
+            if basis is not None and not own:                  # a caller's engine goes back as it came
+                eng.set_basis(None)
     finally:
         if own:
             eng.close()
     cls = EnsembleSolutionResult if isinstance(prob, EnsembleProblem) else SolutionResult
-    return cls(res, res.minimum, res.minimizer, prob, alg)
+    return cls(res, res.minimum, pulse, prob, alg, params)

@@ -1,0 +1,91 @@
+// basis.hip -- grape_set_basis: the two kernels around an evaluation in parameter mode.
+//
+//   x[c,t]        = x0[c,t] + sum_{m<M} theta[c,m] phi_b[t,m]          (basis_expand_kernel, in front of the sweeps)
+//   G_theta[c,m]  = sum_t G_tot[c,t] phi_b[t,m]                         (basis_project_kernel, behind the final sum)
+//
+// b = 0 for a shared basis, c for one basis per control.  Both sums have a fixed order (m ascending; t in a lane stride of
+// 64, ascending, then a 64-lane xor butterfly), so a parameter-mode evaluation is bitwise reproducible call to call.  The
+// expansion writes the (K, N[, n_x]) control array the sweep kernels and the penalty terms already read; the projection
+// reads the complete summed rows { G_tot, F } -- behind the cross-device sum / exchange, penalties included -- and is the
+// evaluation's LAST kernel: it publishes to the host as copy_kernel does (done_signal.hpp).
+// Both are reached through launch_copy (DoneSignal::basis), so the host layer links against the same launcher set as before.
+#include "done_signal.hpp"
+
+namespace grape {
+
+// one thread per entry of x: an M-term FMA chain, m ascending.  A workgroup owns 256 slices of ONE control (blockIdx.y) of
+// one array (blockIdx.z) and passes that control's coefficients through LDS in tiles of 256: theta may live in mapped host
+// memory (the blocking entry points stage it there -- the expansion IS the upload), where every read is a trip over the
+// bus; this way each coefficient is fetched once per workgroup instead of once per slice.  phi is read coalesced in t.
+constexpr int kBasisTile = 256;
+__global__ __launch_bounds__(256) void basis_expand_kernel(const BasisOp op, const double *__restrict__ theta,
+                                                           double *__restrict__ x)
+{
+    __shared__ double s_th[kBasisTile];
+    const int t = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y, b = blockIdx.z;
+    const bool live = t < op.N;
+    const double *ph = op.phi + (size_t)(op.n_bases == 1 ? 0 : c) * op.N * op.M + (live ? t : 0);
+    const double *th = theta + (size_t)b * op.K * op.M + c;
+    double acc = live && op.x0 ? op.x0[c + (size_t)op.K * t] : 0.0;
+    for (int m0 = 0; m0 < op.M; m0 += kBasisTile) {
+        const int cnt = op.M - m0 < kBasisTile ? op.M - m0 : kBasisTile;
+        __syncthreads();
+        if ((int)threadIdx.x < cnt)
+            s_th[threadIdx.x] = th[(size_t)op.K * (m0 + threadIdx.x)];
+        __syncthreads();
+        if (live)
+            for (int j = 0; j < cnt; ++j)
+                acc = fma(s_th[j], ph[(size_t)op.N * (m0 + j)], acc);
+    }
+    if (live)
+        x[(size_t)b * op.K * op.N + c + (size_t)op.K * t] = acc;
+}
+
+// one wave per output (c, m) of control array blockIdx.y; four waves per workgroup.  Lane l sums t = l, l + 64, ...
+// ascending, the 64 partial sums meet in an xor butterfly (every lane ends with the same bits).  The wave of output 0 also
+// carries F through.
+__global__ __launch_bounds__(256) void basis_project_kernel(const BasisOp op, const double *__restrict__ rows,
+                                                            double *__restrict__ out, DoneSignal done)
+{
+    const int KM = op.K * op.M, Qn = op.K * op.N + 1, Qm = KM + 1;
+    const int lane = threadIdx.x & 63;
+    const int o = blockIdx.x * 4 + (threadIdx.x >> 6);       // c + K m
+    const int b = blockIdx.y;
+    if (o < KM) {
+        const int c = o % op.K, m = o / op.K;
+        const double *g = rows + (size_t)b * Qn + c;
+        const double *ph = op.phi + ((size_t)(op.n_bases == 1 ? 0 : c) * op.M + m) * op.N;
+        double part = 0.0;
+        for (int t = lane; t < op.N; t += 64)
+            part = fma(g[(size_t)op.K * t], ph[t], part);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1)
+            part += __shfl_xor(part, d, 64);
+        if (lane == 0) {
+            out[(size_t)b * Qm + o] = part;
+            if (o == 0)
+                out[(size_t)b * Qm + KM] = rows[(size_t)b * Qn + Qn - 1];
+        }
+    }
+    if (done.flag) {
+        __threadfence_system();
+        __syncthreads();
+        if (threadIdx.x == 0)
+            signal_done(done, gridDim.x * gridDim.y);
+    }
+}
+
+hipError_t launch_basis(const BasisOp &op, const double *src, double *dst, hipStream_t stream, DoneSignal done)
+{
+    if (op.K < 1 || op.K > 65535 || op.N < 1 || op.M < 1 || op.M > op.N || op.n_x < 1 || op.n_x > 65535 || !op.phi || !src || !dst)
+        return hipErrorInvalidValue;
+    done.basis = nullptr;                                    // (a host address: nothing for the device)
+    if (!op.project) {
+        GRAPE_LAUNCH(basis_expand_kernel, dim3((op.N + 255) / 256, op.K, op.n_x), dim3(256), 0, stream, op, src, dst);
+        return hipGetLastError();
+    }
+    GRAPE_LAUNCH(basis_project_kernel, dim3((op.K * op.M + 3) / 4, op.n_x), dim3(256), 0, stream, op, src, dst, done);
+    return hipGetLastError();
+}
+
+}  // namespace grape

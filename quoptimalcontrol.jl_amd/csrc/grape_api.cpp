@@ -182,6 +182,13 @@ struct grape_ctx {
     bool pen_on = false;                       // some weight > 0
     std::vector<double> pen_w;                 // host copy [amp (K) | var (K)]
     double *d_pen_w = nullptr;                 // device copy of pen_w
+    // grape_set_basis ("parameter mode"): the entry points take theta (K, M) and return G_theta; basis_expand_kernel writes the
+    // physical controls into d_x in front of the evaluation, basis_project_kernel folds the complete summed rows in d_fg behind
+    // it (basis.hip).  Kept by the context the caller holds (a group: device buffers on its first device); shards never see it.
+    int basis_M = 0;                           // > 0: a basis is in force
+    int basis_nb = 1;                          // bases: 1 (shared) or K (one per control)
+    double *d_basis_phi = nullptr;             // (N, M, n_bases)
+    double *d_basis_x0 = nullptr;              // (K, N), or null
     bool mf_publish = true;                    // GRAPE_MF_PUBLISH=0: reduce_rows_kernel's staged publication instead of per-workgroup host flags
     unsigned long long seq = 0;
     std::string kernel_log;                    // names of the kernels the last evaluation launched (grape_get_kernel_names)
@@ -397,6 +404,8 @@ static bool env_off(const char *name)
 }
 
 static size_t KN(const grape_ctx *c) { return (size_t)c->cfg.n_controls * c->cfg.n_slices; }
+// length of the vector the entry points take and return the gradient of: K M with a basis in force (grape_set_basis), else K N
+static size_t KP(const grape_ctx *c) { return c->basis_M > 0 ? (size_t)c->cfg.n_controls * c->basis_M : KN(c); }
 
 static void free_all(grape_ctx *c)
 {
@@ -417,6 +426,7 @@ static void free_all(grape_ctx *c)
     if (c->is_group) {
         if (c->d_gather) { (void)hipSetDevice(c->device); (void)hipFree(c->d_gather); }
         if (c->d_arrive) { (void)hipSetDevice(c->device); (void)hipFree(c->d_arrive); }
+        if (c->d_basis_phi) { (void)hipSetDevice(c->device); (void)hipFree(c->d_basis_phi); (void)hipFree(c->d_basis_x0); }
         delete c;
         return;
     }
@@ -444,6 +454,7 @@ static void free_all(grape_ctx *c)
     (void)hipFree(c->d_tp_q); (void)hipFree(c->d_tp_r); (void)hipFree(c->d_tp_m); (void)hipFree(c->d_tp_z); (void)hipFree(c->d_tp_vec); (void)hipFree(c->d_tp_a);
     (void)hipFree(c->d_x_bar);
     (void)hipFree(c->d_pen_w);
+    (void)hipFree(c->d_basis_phi); (void)hipFree(c->d_basis_x0);
     (void)hipFree(c->d_fom_member); (void)hipFree(c->d_fom_rows);
     (void)hipFree(c->d_ha); (void)hipFree(c->d_ha_norm); (void)hipFree(c->d_gc); (void)hipFree(c->d_gcn);
     (void)hipFree(c->d_act_a); (void)hipFree(c->d_act_b); (void)hipFree(c->d_act_bf); (void)hipFree(c->d_act_g);
@@ -1127,6 +1138,99 @@ extern "C" int grape_set_penalties(grape_ctx *c, const double *amp_w, const doub
         return GRAPE_OK;
     }
     return shard_set_penalties(c, w, on);
+}
+
+static int wait_stream(grape_ctx *c, hipStream_t stream);
+
+extern "C" int grape_set_basis(grape_ctx *c, int32_t n_params, int32_t n_bases, const double *phi, const double *x0)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_set_basis: null context");
+    const int K = c->cfg.n_controls, N = c->cfg.n_slices;
+    const bool off = !phi || n_params == 0;
+    if (!off) {
+        if (n_params < 1 || n_params > N)
+            return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_basis: n_params = " + std::to_string(n_params) + " (must be in 1..n_slices)");
+        if (n_bases != 1 && n_bases != K)
+            return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_basis: n_bases = " + std::to_string(n_bases) + " (must be 1 or n_controls)");
+        const size_t np = (size_t)N * n_params * n_bases;
+        for (size_t i = 0; i < np; ++i)
+            if (!std::isfinite(phi[i]))
+                return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_basis: phi[" + std::to_string(i) + "] is not finite");
+        for (size_t i = 0; x0 && i < KN(c); ++i)
+            if (!std::isfinite(x0[i]))
+                return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_basis: x0[" + std::to_string(i) + "] is not finite");
+    }
+    grape_ctx *lead = c->is_group ? c->sub[0] : c;
+    HIP_TRY(c, hipSetDevice(lead->device));
+    if (lead->dev_pending) {                                 // (as grape_set_operators: the buffers may be in use)
+        HIP_TRY(c, hipEventSynchronize(lead->ev_dev));
+        lead->dev_pending = false;
+    }
+    HIP_TRY(c, hipStreamSynchronize(lead->stream));
+    double *d_phi = nullptr, *d_x0 = nullptr;
+    if (!off) {                                              // new buffers first: a failure leaves the previous basis in force
+        const size_t np = (size_t)N * n_params * n_bases;
+        hipError_t e = hipMalloc((void **)&d_phi, sizeof(double) * np);
+        if (e == hipSuccess) e = hipMemcpy(d_phi, phi, sizeof(double) * np, hipMemcpyHostToDevice);
+        if (e == hipSuccess && x0) e = hipMalloc((void **)&d_x0, sizeof(double) * KN(c));
+        if (e == hipSuccess && x0) e = hipMemcpy(d_x0, x0, sizeof(double) * KN(c), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d_phi);
+            (void)hipFree(d_x0);
+            (void)hipGetLastError();
+            return fail(c, e == hipErrorOutOfMemory ? GRAPE_ERR_ALLOC : GRAPE_ERR_HIP, std::string("grape_set_basis: ") + hipGetErrorString(e));
+        }
+    }
+    (void)hipFree(c->d_basis_phi);
+    (void)hipFree(c->d_basis_x0);
+    c->d_basis_phi = d_phi;
+    c->d_basis_x0 = d_x0;
+    c->basis_M = off ? 0 : n_params;
+    c->basis_nb = off ? 1 : n_bases;
+    return GRAPE_OK;
+}
+
+// what launch_copy needs to run one of basis.hip's kernels in place of the copy
+static grape::BasisOp basis_op(const grape_ctx *c, bool project, int n_x)
+{
+    grape::BasisOp op;
+    op.project = project ? 1 : 0;
+    op.phi = c->d_basis_phi;
+    op.x0 = c->d_basis_x0;
+    op.K = c->cfg.n_controls;
+    op.N = c->cfg.n_slices;
+    op.M = c->basis_M;
+    op.n_bases = c->basis_nb;
+    op.n_x = n_x;
+    return op;
+}
+
+extern "C" int grape_get_controls(grape_ctx *c, const double *theta, double *x)
+{
+    DeviceGuard guard;
+    if (!c) return GRAPE_ERR_INVALID_ARG;
+    if (!theta || !x) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_get_controls: null argument");
+    if (c->basis_M <= 0) {                                   // no basis: the parameters ARE the controls
+        std::memmove(x, theta, sizeof(double) * KN(c));
+        return GRAPE_OK;
+    }
+    grape_ctx *lead = c->is_group ? c->sub[0] : c;
+    HIP_TRY(c, hipSetDevice(lead->device));
+    if (lead->dev_pending) {                                 // order behind the last grape_eval_device (it reads d_x)
+        HIP_TRY(c, hipStreamWaitEvent(lead->stream, lead->ev_dev, 0));
+        lead->dev_pending = false;
+    }
+    std::memcpy(lead->h_stage, theta, sizeof(double) * KP(c));
+    const grape::BasisOp op = basis_op(c, false, 1);
+    grape::DoneSignal d;
+    d.basis = &op;
+    HIP_TRY(c, grape::launch_copy(lead->d_h_stage, lead->d_x, (int)KN(c), lead->stream, d));
+    HIP_TRY(c, hipMemcpyAsync(lead->h_fg, lead->d_x, sizeof(double) * KN(c), hipMemcpyDeviceToHost, lead->stream));
+    const int rc = wait_stream(lead, lead->stream);
+    if (rc) return c->is_group ? fail(c, rc, lead->err) : rc;
+    std::memcpy(x, lead->h_fg, sizeof(double) * KN(c));
+    return GRAPE_OK;
 }
 
 // smallest ensemble the vector flow of action_thin.hip is chosen for.  A member's two chains are strictly sequential in
@@ -2060,6 +2164,7 @@ static bool tile_folds_reduce(const grape_ctx *c, int n_x)
 static bool eval_ends_in_reduce(const grape_ctx *c)
 {
     if (c->is_group || c->comm || c->ipc_ranks > 1) return false;
+    if (c->basis_M > 0) return false;                        // parameter mode ends in basis_project_kernel
     return c->family == 0 ? true : !tile_folds_reduce(c, 1);
 }
 
@@ -2675,12 +2780,46 @@ static int eval_device_impl(grape_ctx *c, const double *d_x, double *d_fg, void 
     return GRAPE_OK;
 }
 
+// Parameter mode (grape_set_basis), every kind of context: theta (K, M, n_x; device memory, or mapped host memory of the
+// blocking entry points) -> basis_expand_kernel -> the first device's d_x -> the evaluation exactly as the device-pointer entry
+// points run it (groups fan x out, communicators / mailboxes exchange; the penalties are added by the final reduction) ->
+// the complete summed rows in the first device's d_fg -> basis_project_kernel -> `out`, n_x blocks of K M + 1 (device, or
+// mapped host memory with `done` carrying the publication).  Nothing is synchronised.
+static int eval_param_device(grape_ctx *c, const double *theta, double *out, hipStream_t st, int n_x,
+                             grape::DoneSignal done = grape::DoneSignal())
+{
+    grape_ctx *lead = c->is_group ? c->sub[0] : c;
+    HIP_TRY(c, hipSetDevice(lead->device));
+    std::string head;                                        // (the evaluation below starts the log afresh)
+    {
+        KernelLogScope log_scope(&head);
+        const grape::BasisOp op = basis_op(c, false, n_x);
+        grape::DoneSignal d;
+        d.basis = &op;
+        HIP_TRY(c, grape::launch_copy(theta, lead->d_x, (int)(KN(c) * (size_t)n_x), st, d));
+    }
+    const int rc = eval_device_impl(c, lead->d_x, lead->d_fg, st, n_x);
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(lead->device));
+    lead->kernel_log = head + ";" + lead->kernel_log;
+    {
+        KernelLogScope log_scope(&lead->kernel_log, true);
+        const grape::BasisOp op = basis_op(c, true, n_x);
+        done.basis = &op;
+        HIP_TRY(c, grape::launch_copy(lead->d_fg, out, (int)((KP(c) + 1) * (size_t)n_x), st, done));
+    }
+    HIP_TRY(c, hipEventRecord(lead->ev_dev, st));            // (the event of eval_device_impl sits in front of the projection)
+    lead->dev_pending = true;
+    return GRAPE_OK;
+}
+
 extern "C" int grape_eval_device(grape_ctx *c, const double *d_x, double *d_fg, void *stream)
 {
     DeviceGuard guard;
     if (!c) return GRAPE_ERR_INVALID_ARG;
     if (!d_x || !d_fg) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_device: null argument");
     if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, "grape_eval_device: operators not set");
+    if (c->basis_M > 0) return eval_param_device(c, d_x, d_fg, (hipStream_t)stream, 1);
     return eval_device_impl(c, d_x, d_fg, stream, 1);
 }
 
@@ -2733,6 +2872,38 @@ static int eval_host(grape_ctx *c, int n_x, const double *x, double *F, double *
     grape_ctx *lead = c->is_group ? c->sub[0] : c;
     int rc = ipc_check(c);
     if (rc) return rc;
+    if (c->basis_M > 0) {
+        // parameter mode: theta is staged in mapped host memory, where the expansion kernel reads it (the expansion is the
+        // upload); the projection kernel writes [G_theta, F] to the mapped host buffer and publishes -- one host flag, as ever
+        const size_t kp = KP(c), Qp = kp + 1;
+        HIP_TRY(c, hipSetDevice(lead->device));
+        if (lead->dev_pending) {                             // order behind the last grape_eval_device
+            HIP_TRY(c, hipStreamWaitEvent(lead->stream, lead->ev_dev, 0));
+            lead->dev_pending = false;
+        }
+        std::memcpy(lead->h_stage, x, sizeof(double) * kp * n_x);
+        grape::DoneSignal done;
+        done.counter = lead->d_done_counter;
+        done.flag = lead->d_h_flag;
+        done.seq = ++lead->seq;
+        rc = eval_param_device(c, lead->d_h_stage, lead->d_h_fg, lead->stream, n_x, done);
+        if (rc) return rc;
+        lead->dev_pending = false;                           // (issued on the context's own stream: already in order)
+        lead->mf_wait = 0;
+        rc = wait_flag(lead);
+        if (rc) return c->is_group ? group_fail(c, lead, rc) : rc;
+        for (size_t i = 1; i < c->sub.size(); ++i) {         // (the other shards' streams end with the sum: done or nearly)
+            rc = wait_stream(c->sub[i], c->sub[i]->stream);
+            if (rc) return group_fail(c, c->sub[i], rc);
+        }
+        rc = ipc_check(c);                                   // an exchange that gave up poisons the rows instead of the flag here
+        if (rc) return rc;
+        for (int b = 0; b < n_x; ++b) {
+            if (G) std::memcpy(G + (size_t)b * kp, lead->h_fg + (size_t)b * Qp, sizeof(double) * kp);
+            if (F) F[b] = lead->h_fg[(size_t)b * Qp + kp];
+        }
+        return GRAPE_OK;
+    }
     if (!c->is_group && !c->comm && c->ipc_ranks <= 1) {
         // single GPU: the final reduce kernel writes its result straight into mapped pinned host
         // memory (no D2H copy node) and the host polls the stream
@@ -2885,6 +3056,7 @@ extern "C" int grape_eval_batch_device(grape_ctx *c, int32_t n_x, const double *
     if (n_x < 1 || n_x > c->B)
         return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_batch_device: n_x must be in 1..grape_config.max_batch");
     if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, "grape_eval_batch_device: operators not set");
+    if (c->basis_M > 0) return eval_param_device(c, d_x, d_fg, (hipStream_t)stream, n_x);
     return eval_device_impl(c, d_x, d_fg, stream, n_x);
 }
 
@@ -2905,20 +3077,29 @@ static int fom_issue(grape_ctx *c, const double *x, int n_x)
         HIP_TRY(c, hipMalloc((void **)&c->d_fom_member, sizeof(double) * (size_t)c->cfg.n_ensemble * c->B));
         HIP_TRY(c, hipMalloc((void **)&c->d_fom_rows, sizeof(double) * (size_t)c->NB * c->B));
     }
-    shard_stage_x(c, x, n_x);
+    const bool param = c->basis_M > 0;
+    if (param)                                               // theta: the expansion kernel reads it from the mapped staging buffer
+        std::memcpy(c->h_stage, x, sizeof(double) * KP(c) * n_x);
+    else
+        shard_stage_x(c, x, n_x);
     if (c->dev_pending) {                                   // order behind the last grape_eval_device
         HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_dev, 0));
         c->dev_pending = false;
     }
     KernelLogScope log_scope(&c->kernel_log);
     const double *d_x = c->d_x;
-    if (c->x_upload == 2)
+    const grape::BasisOp bop = basis_op(c, false, n_x);
+    if (param) {
+        grape::DoneSignal bd;
+        bd.basis = &bop;
+        HIP_TRY(c, grape::launch_copy(c->d_h_stage, c->d_x, (int)(kn * n_x), c->stream, bd));
+    } else if (c->x_upload == 2)
         d_x = c->d_x_bar;
     else if (c->x_upload == 1)
         HIP_TRY(c, grape::launch_copy(c->d_h_stage, c->d_x, (int)(kn * n_x), c->stream));
     else
         HIP_TRY(c, hipMemcpyAsync(c->d_x, c->h_stage, sizeof(double) * kn * n_x, hipMemcpyHostToDevice, c->stream));
-    c->kernel_log.clear();                                   // (the names of THIS call's evaluation kernels: not the x upload, as grape_eval)
+    if (!param) c->kernel_log.clear();                       // (the names of THIS call's evaluation kernels: not the x upload, as grape_eval)
     grape::DoneSignal done;
     done.counter = c->d_done_counter;
     done.flag = c->d_h_flag;
@@ -2992,7 +3173,7 @@ extern "C" int grape_eval_fom(grape_ctx *c, int32_t n_x, const double *x, double
     if (n_x < 1 || n_x > c->B)
         return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_fom: n_x must be in 1..max(1, grape_config.max_batch)");
     if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, "grape_eval_fom: operators not set");
-    const size_t kn = KN(c), E = (size_t)c->cfg.n_ensemble;
+    const size_t kn = KP(c), E = (size_t)c->cfg.n_ensemble;
     if (!fom_fast(c)) {
         // fallback: the full evaluation, its F bit for bit; member_F from the member rows, array by array
         if (!member_F)
@@ -3077,6 +3258,7 @@ struct LbfgsRun {
     {
         evals += n_x;
         // (groups: fan-out of x, every shard, the grouped all-reduce / peer sum; communicators: the exchange behind the sweep)
+        if (c->basis_M > 0) return eval_param_device(c, st.xt, st.fgt, lead->stream, n_x);   // trial points are theta
         return eval_device_impl(c, st.xt, st.fgt, lead->stream, n_x);
     }
     // trial slot 0: evaluate, publish phi, phi' (and phi'(0)) behind it -- nothing is waited for
@@ -3313,9 +3495,10 @@ extern "C" int grape_lbfgs(grape_ctx *c, const double *x0, const grape_lbfgs_opt
     if (!c) return GRAPE_ERR_INVALID_ARG;
     if (!x0 || !x_min || !result) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_lbfgs: null argument");
     if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, "grape_lbfgs: operators not set");
-    const size_t kn = KN(c), Q = kn + 1;
+    const size_t kn = KP(c), Q = kn + 1;                     // (parameter mode: every vector is K M long)
     if (kn > (size_t)grape::kLbfgsMaxPer * 1024)
-        return fail(c, GRAPE_ERR_UNSUPPORTED, "grape_lbfgs: n_controls * n_slices > 16384");
+        return fail(c, GRAPE_ERR_UNSUPPORTED, c->basis_M > 0 ? "grape_lbfgs: n_controls * n_params > 16384"
+                                                             : "grape_lbfgs: n_controls * n_slices > 16384");
     grape_lbfgs_options o{};
     if (opts) o = *opts;
     const int m = o.memory > 0 ? o.memory : 10;

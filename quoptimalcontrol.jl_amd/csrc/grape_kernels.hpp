@@ -32,6 +32,17 @@ void log_kernel(const char *expr);
 // members, whose workgroups then set the kernel's run time.)
 constexpr double kTheta8 = 0.08;
 
+// grape_set_basis (basis.hip): what launch_copy does INSTEAD of copying when DoneSignal::basis points at one of these.  The
+// struct is read by the launcher on the host and handed to the kernel by value.
+//   expand:  dst (K, N, n_x) = x0 + sum_m src[c, m, b] phi_b[t, m], m ascending, one FMA per term (basis_expand_kernel)
+//   project: dst n_x blocks of K M + 1 = { sum_t src[c, t, b] phi_b[t, m] (lane stride 64 in t, then a fixed butterfly), F }
+//            from n_x blocks of K N + 1 (basis_project_kernel: one wave per output); it publishes like copy_kernel
+struct BasisOp {
+    int32_t project = 0;                       // 0: expand, 1: project
+    const double *phi = nullptr;               // device (N, M, n_bases) column-major
+    const double *x0 = nullptr;                // device (K, N), nullable
+    int32_t K = 0, N = 0, M = 0, n_bases = 1, n_x = 1;
+};
 // optional host-visible completion signal of an evaluation's FINAL kernel (reduce.hip: signal_done);
 // flag == nullptr: none (device-pointer entry points, intermediate kernels)
 struct DoneSignal {
@@ -57,6 +68,11 @@ struct DoneSignal {
     const double *pen_x = nullptr;             // device: the (K,N) control array(s) of the evaluation; nullptr: no penalty
     const double *pen_w = nullptr;             // device: [amp (K) | var (K)]
     int pen_K = 0, pen_N = 0;
+    // grape_set_basis: HOST pointer to a BasisOp that outlives the launch call only -- set by the host layer immediately in
+    // front of a launch_copy call, read (and cleared before the kernel launch) by launch_copy alone, never forwarded to another
+    // launcher and never dereferenced on the device; with it launch_copy takes its sizes from the BasisOp, not from `n`.
+    // nullptr (every other use of DoneSignal): a plain copy
+    const BasisOp *basis = nullptr;
 };
 constexpr int kMaxMflags = 1000;               // flags behind grape_ctx::h_flag (8 KB: [0] flag, [1] exchange failure, [8..] these)
 // workgroups (= host flags) reduce_rows_mf_kernel publishes with for Q outputs x n_x control arrays; 0: not applicable
@@ -408,5 +424,7 @@ hipError_t launch_lbfgs_step(const LbfgsState &st, int commit, hipStream_t strea
 // dst[i] = src[i], i < n: moves the all-reduced [G, F] into mapped pinned host memory (one small launch
 // instead of a D2H copy node: the host polls the stream)
 hipError_t launch_copy(const double *src, double *dst, int n, hipStream_t stream, DoneSignal done = DoneSignal());
+// basis.hip; reached through launch_copy (DoneSignal::basis) only
+hipError_t launch_basis(const BasisOp &op, const double *src, double *dst, hipStream_t stream, DoneSignal done);
 
 }  // namespace grape

@@ -236,6 +236,8 @@ __global__ __launch_bounds__(256) void copy_kernel(const double *__restrict__ sr
 
 hipError_t launch_copy(const double *src, double *dst, int n, hipStream_t stream, DoneSignal done)
 {
+    if (done.basis)                                          // grape_set_basis: the expansion / projection stands in for the copy
+        return launch_basis(*done.basis, src, dst, stream, done);
     GRAPE_LAUNCH(copy_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, src, dst, n, done);
     return hipGetLastError();
 }
@@ -277,8 +279,10 @@ __global__ __launch_bounds__(256) void reduce_few_kernel(const double *__restric
 }
 
 // the shards of a multi-device context: fg[q] = sum over the shards' rows, in shard order, each row read where it was
-// produced (the devices of a group have peer access to each other) -- no staging copies, one launch
-__global__ __launch_bounds__(256) void reduce_shards_kernel(ShardRows rows, double *__restrict__ fg, int Q, DoneSignal done)
+// produced (the devices of a group have peer access to each other) -- no staging copies, one launch.  fg MAY be one of the
+// rows (the host layer sums into the first shard's row in place): a thread reads index q of every row before it writes
+// index q, and no other thread touches that index -- hence no __restrict__ on fg
+__global__ __launch_bounds__(256) void reduce_shards_kernel(ShardRows rows, double *fg, int Q, DoneSignal done)
 {
     const int q = blockIdx.x * 256 + threadIdx.x;
     double acc = 0.0;

@@ -36,6 +36,7 @@ STATUS = {0: "GRAPE_OK", -1: "GRAPE_ERR_INVALID_ARG", -2: "GRAPE_ERR_UNSUPPORTED
 
 # every symbol include/grape_hip.h declares
 EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_operators", "grape_set_penalties",
+           "grape_set_basis", "grape_get_controls",
            "grape_comm_unique_id", "grape_comm_attach", "grape_ipc_export", "grape_ipc_attach",
            "grape_eval", "grape_eval_device", "grape_eval_batch", "grape_eval_batch_device", "grape_eval_fom", "grape_lbfgs", "grape_lbfgs_get_trace",
            "grape_get_member_results", "grape_get_trajectory",
@@ -121,6 +122,8 @@ def load_library():
     L.grape_destroy.argtypes = [vp]
     L.grape_set_operators.argtypes = [vp] * 6
     L.grape_set_penalties.argtypes = [vp, vp, vp]
+    L.grape_set_basis.argtypes = [vp, i32, i32, vp, vp]
+    L.grape_get_controls.argtypes = [vp, vp, vp]
     L.grape_comm_unique_id.argtypes = [C.POINTER(GrapeCommId)]
     L.grape_comm_attach.argtypes = [vp, C.POINTER(GrapeCommId), i32, i32]
     L.grape_ipc_export.argtypes = [vp, i32, vp]
@@ -163,6 +166,8 @@ class GrapeEngine:
 
     A (E,n,n), B (E,K,n,n), Xi/Xt (E,n,n), wts (E,) -- natural numpy matrices A[k][i,j].
     eval(x) -> (F, G) with x, G of shape (K, N) (x[j, i] as in the reference)."""
+
+    n_params = 0                               # M of set_basis (parameter mode); 0: slice mode
 
     def __init__(self, sys_type, A, B, Xi, Xt, wts, T, n_slices, variant=0, device=-1, flags=0,
                  slices_per_lane=0, waves_per_member=0, expm_squarings=-1, member_results=False, max_batch=1,
@@ -240,6 +245,49 @@ class GrapeEngine:
         a, v = vec(amp), vec(var)
         self._check(self._lib.grape_set_penalties(self._h, _p(a), _p(v)))
 
+    def set_basis(self, phi, x0=None):
+        """grape_set_basis: restrict the pulse to x[c,t] = x0[c,t] + sum_m theta[c,m] phi[t,m] -- "parameter mode".
+        phi: (N, M) (one basis for every control) or (K, N, M) (one per control), 1 <= M <= N; x0: (K, N) or None (0).
+        From now on eval, eval_batch, fom, lbfgs and the device-pointer forms take theta (K, M) where they took x and
+        return the gradient with respect to theta (K, M); F is that of the physical pulse, penalties included.
+        member_results() and trajectory() stay in slice space.  phi=None switches the basis off again."""
+        if phi is None:
+            self._check(self._lib.grape_set_basis(self._h, 0, 1, None, None))
+            self.n_params = 0
+            return
+        phi = np.asarray(phi, dtype=np.float64)
+        if phi.ndim == 2 and phi.shape[0] == self.N:
+            pf, nb = np.ascontiguousarray(phi.T), 1                          # [m][t]
+        elif phi.ndim == 3 and phi.shape[:2] == (self.K, self.N):
+            pf, nb = np.ascontiguousarray(np.swapaxes(phi, 1, 2)), self.K    # [c][m][t]
+        else:
+            raise ValueError(f"phi must be ({self.N}, M) or ({self.K}, {self.N}, M)")
+        M = phi.shape[-1]
+        xf = None
+        if x0 is not None:
+            x0 = np.asarray(x0, dtype=np.float64)
+            if x0.shape != (self.K, self.N):
+                raise ValueError(f"x0 must be ({self.K},{self.N})")
+            xf = np.ascontiguousarray(x0.T)
+        self._check(self._lib.grape_set_basis(self._h, M, nb, _p(pf), _p(xf)))
+        self.n_params = M
+
+    @property
+    def _cols(self):
+        """second dimension of the arrays the evaluation calls take and return: M in parameter mode, else N"""
+        return self.n_params or self.N
+
+    def controls(self, theta):
+        """grape_get_controls: the physical pulse (K, N) of a parameter array (K, M), expanded on the device by the
+        kernel the evaluations use.  Without a basis the parameters are the pulse."""
+        theta = np.asarray(theta, dtype=np.float64)
+        if theta.shape != (self.K, self._cols):
+            raise ValueError(f"theta must be ({self.K},{self._cols})")
+        tf = np.ascontiguousarray(theta.T)
+        x = np.empty((self.N, self.K))
+        self._check(self._lib.grape_get_controls(self._h, _p(tf), _p(x)))
+        return np.ascontiguousarray(x.T)
+
     # ------------------------------------------------------------------ plumbing
     def _check(self, rc):
         if rc:
@@ -301,13 +349,14 @@ class GrapeEngine:
 
     # ------------------------------------------------------------------ evaluation
     def eval(self, x, want_F=True, want_G=True):
-        """grape_eval: host x (K,N) -> (F, G); either may be skipped like Optim's only_fg!."""
+        """grape_eval: host x (K,N) -> (F, G); either may be skipped like Optim's only_fg!.  Parameter mode (set_basis):
+        x is theta (K,M) and G its gradient (K,M) -- here and in eval_cm, bind_eval, eval_batch, fom and lbfgs."""
         x = np.asarray(x, dtype=np.float64)
-        if x.shape != (self.K, self.N):
-            raise ValueError(f"x must be ({self.K},{self.N})")
+        if x.shape != (self.K, self._cols):
+            raise ValueError(f"x must be ({self.K},{self._cols})")
         xf = np.ascontiguousarray(x.T)
         F = C.c_double()
-        G = np.empty((self.N, self.K)) if want_G else None
+        G = np.empty((self._cols, self.K)) if want_G else None
         self._check(self._lib.grape_eval(self._h, _p(xf), C.byref(F) if want_F else None, _p(G)))
         return (F.value if want_F else None), (np.ascontiguousarray(G.T) if want_G else None)
 
@@ -316,8 +365,8 @@ class GrapeEngine:
         memory, i.e. a C-contiguous float64 array of shape (N, K); G_out (same shape, or None to skip G) receives
         the gradient in that layout.  Returns F.  This is what a compiled caller (the Julia ccall) does per
         optimiser step; eval() is the convenience form with natural (K, N) arrays."""
-        if xf.dtype != np.float64 or not xf.flags.c_contiguous or xf.shape != (self.N, self.K):
-            raise ValueError(f"xf must be a C-contiguous float64 array of shape ({self.N},{self.K})")
+        if xf.dtype != np.float64 or not xf.flags.c_contiguous or xf.shape != (self._cols, self.K):
+            raise ValueError(f"xf must be a C-contiguous float64 array of shape ({self._cols},{self.K})")
         if G_out is not None and (G_out.dtype != np.float64 or not G_out.flags.c_contiguous or G_out.shape != xf.shape):
             raise ValueError("G_out must match xf")
         rc = self._lib.grape_eval(self._h, xf.ctypes.data, C.byref(self._F), G_out.ctypes.data if G_out is not None else None)
@@ -329,8 +378,8 @@ class GrapeEngine:
         """Pre-bound grape_eval on fixed caller buffers (layout as eval_cm): returns a zero-argument callable that
         runs one evaluation and returns F.  The ctypes argument objects are built once, so a call costs what the
         foreign-function call itself costs -- the closest Python gets to the Julia `ccall` in julia/GrapeHIP.jl."""
-        if xf.dtype != np.float64 or not xf.flags.c_contiguous or xf.shape != (self.N, self.K):
-            raise ValueError(f"xf must be a C-contiguous float64 array of shape ({self.N},{self.K})")
+        if xf.dtype != np.float64 or not xf.flags.c_contiguous or xf.shape != (self._cols, self.K):
+            raise ValueError(f"xf must be a C-contiguous float64 array of shape ({self._cols},{self.K})")
         if G_out.dtype != np.float64 or not G_out.flags.c_contiguous or G_out.shape != xf.shape:
             raise ValueError("G_out must match xf")
         fn, h, px, pg, F = self._lib.grape_eval, self._h, C.c_void_p(xf.ctypes.data), C.c_void_p(G_out.ctypes.data), self._F
@@ -356,8 +405,8 @@ class GrapeEngine:
         initial step accepted when it satisfies the Wolfe conditions), "optim" (Hager-Zhang exactly as Optim runs it
         behind InitialStatic) or "ladder" (`probes` step lengths per batched launch; needs max_batch >= probes)."""
         x0 = np.asarray(x0, dtype=np.float64)
-        if x0.shape != (self.K, self.N):
-            raise ValueError(f"x0 must be ({self.K},{self.N})")
+        if x0.shape != (self.K, self._cols):
+            raise ValueError(f"x0 must be ({self.K},{self._cols})")
         xf = np.ascontiguousarray(x0.T)
         out = np.empty_like(xf)
         opts = GrapeLbfgsOptions(int(memory), int(iterations), float(g_tol), float(f_tol), int(max_linesearch), int(probes),
@@ -380,12 +429,12 @@ class GrapeEngine:
         """grape_eval_batch: X (n_x, K, N) control arrays -> (F (n_x,), G (n_x, K, N)); entry b equals
         eval(X[b]).  An extension for multi-start optimisation; needs max_batch >= n_x."""
         X = np.asarray(X, dtype=np.float64)
-        if X.ndim != 3 or X.shape[1:] != (self.K, self.N):
-            raise ValueError(f"X must be (n_x, {self.K}, {self.N})")
+        if X.ndim != 3 or X.shape[1:] != (self.K, self._cols):
+            raise ValueError(f"X must be (n_x, {self.K}, {self._cols})")
         n_x = X.shape[0]
         xf = np.ascontiguousarray(np.swapaxes(X, 1, 2))            # each (K,N) column-major
         F = np.empty(n_x)
-        G = np.empty((n_x, self.N, self.K))
+        G = np.empty((n_x, self._cols, self.K))
         self._check(self._lib.grape_eval_batch(self._h, n_x, _p(xf), _p(F), _p(G)))
         return F, np.ascontiguousarray(np.swapaxes(G, 1, 2))
 
@@ -397,8 +446,8 @@ class GrapeEngine:
         runs and its F is returned bit for bit."""
         x = np.asarray(x, dtype=np.float64)
         single = x.ndim == 2
-        if (x.shape if single else x.shape[1:]) != (self.K, self.N) or x.ndim not in (2, 3):
-            raise ValueError(f"x must be ({self.K},{self.N}) or (n_x,{self.K},{self.N})")
+        if (x.shape if single else x.shape[1:]) != (self.K, self._cols) or x.ndim not in (2, 3):
+            raise ValueError(f"x must be ({self.K},{self._cols}) or (n_x,{self.K},{self._cols})")
         n_x = 1 if single else x.shape[0]
         xf = np.ascontiguousarray(np.swapaxes(x, -1, -2))          # each (K,N) column-major
         F = np.empty(n_x)
