@@ -284,6 +284,42 @@ int grape_set_operators(grape_ctx *ctx, const double *A, const double *B, const 
  * grape_set_penalties with the same weights, just as every rank passes the same x. */
 int grape_set_penalties(grape_ctx *ctx, const double *amp_w, const double *var_w);
 
+/* Running costs on the intermediate states: the trajectory functionals of the reference's cost library,
+ * src/cost_functions.jl:44-61 -- C5 (occupation of forbidden states), C6 (evolution time, target gate), C7 (evolution time,
+ * target state) -- in one shared form.  Additive to ABI v8.
+ *   R    host c128 (n, m, E, n_terms) column-major   probe matrices, one per member and term
+ *   rho  host f64  (N, n_terms)                      slice weights; entry [s-1, j] weights the state AFTER s slices
+ *   n_terms = 0 or R == NULL: off.  1 <= n_terms <= 4.
+ * With X_{k,s} member k's state after s slices (X_{k,0} = Xi_k) and y_{k,j,s} = tr(R_{k,j}' X_{k,s}):
+ *   J(x)        = sum_k w_k sum_j sum_{s=1..N} rho[s-1,j] |y_{k,j,s}|^2
+ *   F_tot       = F + J                      (then the penalties, then the basis projection, as without it)
+ *   G_tot[c,t]  = G[c,t] + sum_k w_k sum_j 2 Re tr( Lam_{k,j,t+1}' (-i dt B_{k,c}) X_{k,t+1} ),   t = 0..N-1
+ *   Lam_{k,j,N} = rho[N-1,j] y_{k,j,N} R_{k,j}
+ *   Lam_{k,j,s} = P_{k,s}' Lam_{k,j,s+1} + rho[s-1,j] y_{k,j,s} R_{k,j}      (P_{k,s}: the propagator taking X_s to X_{s+1})
+ * This is the derivative of J with dP_t/dx[c,t] replaced by (-i dt) B_c P_t: FIRST ORDER in dt, the same order as the
+ * reference's grad_func! (src/GRAPE.jl:261-303) that G itself follows; the exact gradient of J is out of scope.
+ * Instances (lambda: the caller's weight):  C5 with forbidden kets psiF_j: R_j = psiF_j (n x 1 states), rho = +lambda;
+ * C6: R = Xt, rho = -lambda / (N D^2), the constant +lambda added by the caller;  C7 for pure states held as n x 1 kets
+ * under UnitaryGate: R = psiT (|psiT' psi|^2 = tr(rhoT rho)), rho = -lambda / N, plus the constant.
+ * Served: kernel family 0 (n = 2, 3, 4), GRAPE_UNITARY_GATE (any m, n x 1 kets included), gradient = 0, objective = 0,
+ * Hermitian and non-Hermitian generators, both variants, single-device contexts (member-chunked ones and max_batch > 1
+ * included).  Everything else -- other n, StateTransfer / CoherenceTransfer (the sandwich needs a second term), gradient =
+ * exact, objective = c1, multi-device contexts, attached communicators or mailboxes (the
+ * one-rank communicator of GRAPE_FLAG_FORCE_COLLECTIVE is one) -- is refused with
+ * GRAPE_ERR_UNSUPPORTED and a message naming the reason; grape_comm_attach / grape_ipc_attach are refused in the same way
+ * while a running cost is set.  Non-finite R or rho, n_terms outside 0..4: GRAPE_ERR_INVALID_ARG.  After any failure the
+ * previous setting stays in force.  Valid any time after grape_create, before or after grape_set_operators (it persists
+ * across it); ordered behind an in-flight grape_eval_device as grape_set_penalties is.
+ * grape_eval, grape_eval_device, the batched forms (every array its own J) and grape_lbfgs return the augmented [G, F];
+ * grape_eval_fom takes its fallback (the forward-only kernel stores no propagators) and returns grape_eval's F bit for
+ * bit.  grape_get_member_results and the member_F of grape_eval_fom stay WITHOUT J, as they stay without penalties.
+ * running_cost_kernel runs behind the sweep of every member block, on its stream, reads the propagators the sweep stored
+ * (in the general flow it also stores the forward states: N n m 16 B per member and control array of extra workspace,
+ * allocated by the first evaluation), and the members' rows join the ensemble sum in a fixed order: results are bitwise
+ * reproducible call to call.  A context that never calls this, or switches it off again, launches exactly the kernels it
+ * always did. */
+int grape_set_running_cost(grape_ctx *ctx, int32_t n_terms, const double *R, const double *rho);
+
 /* Pulses restricted to a basis (Fourier / CRAB series, splines, Slepians, the impulse response of an AWG filter), with the
  * gradient with respect to the coefficients -- "parameter mode".  Additive to ABI v8.
  *   x[c,t] = x0[c,t] + sum_{m<M} theta[c,m] * phi_b[t,m],   b = (n_bases == 1 ? 0 : c)

@@ -136,6 +136,24 @@ function set_penalties!(ctx::GrapeContext, pf)
                      amp === nothing ? C_NULL : amp, var === nothing ? C_NULL : var))
 end
 
+# grape_set_running_cost: costs on the intermediate states (C5 / C6 / C7, src/cost_functions.jl:44-61) added to every evaluation:
+#   J = sum_k w_k sum_j sum_s rho[s,j] |tr(R[:,:,k,j]' X_{k,s})|^2,  X_{k,s} the state after s slices, s = 1..N
+# R (n, m, E, n_terms) ComplexF64, rho (N, n_terms) Float64 -- Julia's column-major arrays are the layout the library reads;
+# n_terms <= 4.  C5: R = forbidden ket, rho = +lambda; C6: R = Xt, rho = -lambda / (N D^2); C7 (kets): R = psiT, rho = -lambda / N
+# (the caller adds the constant lambda).  R = nothing switches the term off.  (Written, NOT executed: no Julia toolchain where
+# this file was written; the Python binding makes the same call and is tested on the GPU.)
+function set_running_cost!(ctx::GrapeContext, R::Union{Nothing,Array{ComplexF64,4}}, rho::Union{Nothing,Matrix{Float64}} = nothing)
+    if R === nothing
+        return check(ctx, ccall((:grape_set_running_cost, libgrape), Cint, (Ptr{Cvoid}, Int32, Ptr{ComplexF64}, Ptr{Float64}),
+                                ctx.handle, Int32(0), C_NULL, C_NULL))
+    end
+    rho === nothing && throw(ArgumentError("set_running_cost!: rho is needed with R"))
+    size(rho) == (ctx.N, size(R, 4)) || throw(DimensionMismatch("rho must be (n_slices, n_terms)"))
+    1 <= size(R, 4) <= 4 || throw(ArgumentError("set_running_cost!: 1 to 4 terms"))
+    GC.@preserve R rho check(ctx, ccall((:grape_set_running_cost, libgrape), Cint, (Ptr{Cvoid}, Int32, Ptr{ComplexF64}, Ptr{Float64}),
+                                        ctx.handle, Int32(size(R, 4)), R, rho))
+end
+
 # grape_set_basis: from here on every x handed to this context is theta (K, M) and every gradient is with respect to theta:
 #   x[c,t] = x0[c,t] + sum_m theta[c,m] phi[t,m];  phi (N, M) for every control or (N, M, K), one basis per control -- Julia's
 # column-major arrays are the layout the library reads.  phi = nothing switches the basis off.  (Not executed where this

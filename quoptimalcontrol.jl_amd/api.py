@@ -11,6 +11,8 @@ the reference's own tests (test/state_transfer_tests.jl, test/unitary_gate_tests
   init_ensemble(ens)                                           src/tools.jl:42-53
   C1(KT, KN)                                                   src/cost_functions.jl:13-17
   C3(u), C4(u), PenaltyFunctionals(weights, functions)         src/cost_functions.jl:29-39, :66-69
+  C5(psiF, psij), C6(KT, KJ, N, D), C7(psiT, psiJ, N)          src/cost_functions.jl:44-61; on the device through
+  ForbiddenStates(states, weight), EvolutionTime(weight)       GRAPE(running_costs=[...]) (grape_set_running_cost)
   dCRAB(n_slices=..., n_freq=2, n_coeff=2)                     src/dCRAB.jl:2-5, :13-89
   fourier_basis(n_slices, duration, freqs), GRAPE(basis=...)   new: gradient-based optimisation over the coefficients of
                                                                dCRAB's ansatz (or any other basis), grape_set_basis
@@ -99,6 +101,9 @@ class GRAPE:
                                    # expanded and projected on the device (grape_set_basis).  The start is the least-squares
                                    # fit of the problem's guess; the result carries the physical pulse and `parameters`
     basis_offset: Any = None       # (K, N) pulse the expansion is added to; None: zero
+    running_costs: Any = None      # list of ForbiddenStates / EvolutionTime (new: the reference's C5 / C6 / C7 are called by none
+                                   # of its solvers): costs on the intermediate states, added to the objective on the device
+                                   # (grape_set_running_cost; n = 2..4, UnitaryGate-type problems, one device)
 
 
 @dataclass
@@ -206,6 +211,90 @@ def C4(u):
     return float(np.sum(np.abs(np.diff(u, axis=1)) ** 2))
 
 
+def C5(psiF, psij):
+    """Occupation of forbidden states, src/cost_functions.jl:44-47: sum(abs2(psiF' * psi) for psi in psij)."""
+    f = np.asarray(psiF, complex).reshape(-1)
+    return float(sum(abs(np.vdot(f, np.asarray(psi, complex).reshape(-1))) ** 2 for psi in psij))
+
+
+def C6(KT, KJ, N, D):
+    """Evolution time (target gate), src/cost_functions.jl:52-54: 1 - 1/N sum(abs2(tr(KT' * Kj) / D) for Kj in KJ)."""
+    KT = np.asarray(KT, complex)
+    return 1.0 - sum(abs(np.trace(KT.conj().T @ np.asarray(Kj, complex)) / D) ** 2 for Kj in KJ) / N
+
+
+def C7(psiT, psiJ, N):
+    """Evolution time (target state), src/cost_functions.jl:59-61: 1 - 1/N sum(abs2(tr(psiT * psij)) for psij in psiJ) --
+    density matrices."""
+    psiT = np.asarray(psiT, complex)
+    return 1.0 - sum(abs(np.trace(psiT @ np.asarray(pj, complex))) ** 2 for pj in psiJ) / N
+
+
+class ForbiddenStates:
+    """weight x C5 on the device: `states` are forbidden kets (a list of length-n vectors, or one vector), at most four; the
+    problem holds its states as n x 1 kets (Xi, Xt of shape (n, 1)) under UnitaryGate.  The cost of a pulse is
+    weight * sum_F C5(psiF, [psi_1 .. psi_N]) over the states after every slice, ensemble-weighted like F."""
+
+    def __init__(self, states, weight=1.0):
+        s = np.asarray(states, dtype=np.complex128)
+        self.states = s.reshape(1, -1) if s.ndim == 1 else s.reshape(s.shape[0], -1)
+        self.weight = float(weight)
+
+    def terms(self, members, N):
+        n, m = np.asarray(members[0].Xi).shape
+        if m != 1 or self.states.shape[1] != n:
+            raise ValueError("ForbiddenStates: the problem must hold n x 1 kets and the forbidden states n entries")
+        R = np.broadcast_to(self.states[:, None, :, None], (self.states.shape[0], len(members), n, 1))
+        return R, np.full((self.states.shape[0], N), self.weight), 0.0
+
+    def to_json(self):
+        return {"kind": "ForbiddenStates", "weight": self.weight,
+                "states": [[[float(v.real), float(v.imag)] for v in s] for s in self.states]}
+
+
+class EvolutionTime:
+    """weight x C6 (n x m operator states, D = n) or, for n x 1 kets, weight x (1 - 1/N sum_s tr(rhoT rho_s)) with
+    tr(rhoT rho) = |psiT' psi|^2 for pure states -- C7's overlap, summed as it is (the reference's one-liner takes abs2 of that
+    trace once more) -- on the device, against every member's own target XtG(k).  The constant `weight` (times the sum of the ensemble weights)
+    is added by solve()."""
+
+    def __init__(self, weight=1.0):
+        self.weight = float(weight)
+
+    def terms(self, members, N):
+        Xt = np.array([np.asarray(p.Xt, complex) for p in members])
+        n, m = Xt.shape[1:]
+        scale = 1.0 / N if m == 1 else 1.0 / (N * n * n)
+        return Xt[None], np.full((1, N), -self.weight * scale), self.weight
+
+    def to_json(self):
+        return {"kind": "EvolutionTime", "weight": self.weight}
+
+
+def running_cost_from_json(d):
+    if d["kind"] == "ForbiddenStates":
+        return ForbiddenStates([[complex(re, im) for re, im in s] for s in d["states"]], d["weight"])
+    if d["kind"] == "EvolutionTime":
+        return EvolutionTime(d["weight"])
+    raise ValueError(f"unknown running cost {d['kind']!r}")
+
+
+def running_cost_terms(members, costs, N, wts=None):
+    """The descriptors of GRAPE(running_costs=...) as grape_set_running_cost takes them: R (n_terms, E, n, m), rho
+    (n_terms, N) and the constant solve() adds to the minimum (C6 / C7: weight x sum of the ensemble weights)."""
+    wsum = float(len(members)) if wts is None else float(np.sum(wts))
+    Rs, rhos, const = [], [], 0.0
+    for c in costs:
+        R, rho, k = c.terms(members, int(N))
+        Rs.append(np.broadcast_to(R, (R.shape[0], len(members)) + R.shape[2:]))
+        rhos.append(rho)
+        const += k * wsum
+    R, rho = np.concatenate(Rs, axis=0), np.concatenate(rhos, axis=0)
+    if R.shape[0] > 4:
+        raise ValueError("running_costs: at most four terms in all (every forbidden state is one)")
+    return np.ascontiguousarray(R), rho, const
+
+
 class PenaltyFunctionals:
     """src/cost_functions.jl:66-69: relative weights and the penalty functionals they scale.  Only C3 and C4 -- the
     functionals of the pulse alone, which the device adds to every evaluation (grape_set_penalties).  A weight is a
@@ -303,6 +392,16 @@ def make_engine(prob, alg, **engine_kw):
         except Exception:
             eng.close()
             raise
+    eng.running_cost_constant = 0.0
+    costs = getattr(alg, "running_costs", None)
+    if costs:
+        try:
+            R, rho, const = running_cost_terms(members, costs, alg.n_slices, wts)
+            eng.set_running_cost(R, rho)
+            eng.running_cost_constant = const
+        except Exception:
+            eng.close()
+            raise
     return eng
 
 
@@ -353,7 +452,9 @@ def save(solres, file_path):
                                             "device": int(alg.device), "optimizer": alg.optimizer,
                                             "devices": None if alg.devices is None else [int(v) for v in alg.devices],
                                             "peer_sum": bool(alg.peer_sum),
-                                            **({"penalties": alg.penalties.to_json()} if alg.penalties is not None else {})},
+                                            **({"penalties": alg.penalties.to_json()} if alg.penalties is not None else {}),
+                                            **({"running_costs": [c.to_json() for c in alg.running_costs]}
+                                               if getattr(alg, "running_costs", None) else {})},
                                            default=_json_default)),
     }
     if ens:
@@ -378,6 +479,8 @@ def load(file_path):
     extra = json.loads(str(d["alg_fields"])) if "alg_fields" in d.files else {}      # (files of earlier rounds: defaults)
     if extra.get("penalties") is not None:
         extra["penalties"] = PenaltyFunctionals.from_json(extra["penalties"])
+    if extra.get("running_costs") is not None:
+        extra["running_costs"] = [running_cost_from_json(c) for c in extra["running_costs"]]
     alg = alg_cls(n_slices=int(d["n_slices"]), **extra) if alg_cls is ADGRAPE else GRAPE(n_slices=int(d["n_slices"]),
                                                                                            isinplace=bool(d["isinplace"]), **extra)
     if str(d["kind"]) == "ensemble":
@@ -492,7 +595,8 @@ def _solve_dcrab(prob, alg, eng):
 
 def solve(prob, alg: Optional[GRAPE] = None, engine=None):
     """solve(::Problem, ::GRAPE) / solve(::EnsembleProblem, ::GRAPE).  With alg.penalties the minimised objective is the
-    figure of merit plus the C3 / C4 penalties, and `fidelity` (res.minimum, as src/solve.jl:139) includes them.
+    figure of merit plus the C3 / C4 penalties, and `fidelity` (res.minimum, as src/solve.jl:139) includes them.  With
+    alg.running_costs the device adds weight x C5 / C6 / C7 without the constant 1 of C6 / C7; solve adds it to res.minimum.
     solve(prob, dCRAB(...)): `result` is the list of the super-iterations' Nelder-Mead results, `fidelity` the list of their
     minima and `opti_pulses` the final (K, N) pulse (src/dCRAB.jl:114)."""
     if alg is None:
@@ -523,6 +627,7 @@ def solve(prob, alg: Optional[GRAPE] = None, engine=None):
                 res = _device_lbfgs(eng, guess, alg.optim_options)
             else:
                 res = _lbfgs(lambda x: eng.eval(x), guess, alg.optim_options)
+            res.minimum = float(res.minimum) + float(getattr(eng, "running_cost_constant", 0.0))
             pulse = res.minimizer
             if basis is not None:                              # the physical pulse, from the kernel the evaluations used
                 params, pulse = res.minimizer, eng.controls(res.minimizer)

@@ -182,6 +182,15 @@ struct grape_ctx {
     bool pen_on = false;                       // some weight > 0
     std::vector<double> pen_w;                 // host copy [amp (K) | var (K)]
     double *d_pen_w = nullptr;                 // device copy of pen_w
+    // running costs on the intermediate states (grape_set_running_cost, src/cost_functions.jl:44-61; running_cost.hip): behind
+    // the sweep of every member block, running_cost_kernel reads the stored propagators and running_cost_fold_kernel adds
+    // w_k [dJ_k/dx, J_k] to the sweep's per-workgroup rows.  Single-device family-0 contexts without an exchange only.
+    int rc_terms = 0;                          // > 0: in force
+    double2 *d_rc_R = nullptr;                 // (n, m, E, rc_terms)
+    double *d_rc_rho = nullptr;                // (N, rc_terms)
+    double2 *d_rc_xs = nullptr;                // general flow: the states behind every slice (allocated by the first evaluation that needs it)
+    double *d_rc_rows = nullptr;               // one row of K N + 1 per (control array, member) of a workspace block
+    size_t rc_xs_bytes = 0, rc_rows_bytes = 0;
     // grape_set_basis ("parameter mode"): the entry points take theta (K, M) and return G_theta; basis_expand_kernel writes the
     // physical controls into d_x in front of the evaluation, basis_project_kernel folds the complete summed rows in d_fg behind
     // it (basis.hip).  Kept by the context the caller holds (a group: device buffers on its first device); shards never see it.
@@ -454,6 +463,7 @@ static void free_all(grape_ctx *c)
     (void)hipFree(c->d_tp_q); (void)hipFree(c->d_tp_r); (void)hipFree(c->d_tp_m); (void)hipFree(c->d_tp_z); (void)hipFree(c->d_tp_vec); (void)hipFree(c->d_tp_a);
     (void)hipFree(c->d_x_bar);
     (void)hipFree(c->d_pen_w);
+    (void)hipFree(c->d_rc_R); (void)hipFree(c->d_rc_rho); (void)hipFree(c->d_rc_xs); (void)hipFree(c->d_rc_rows);
     (void)hipFree(c->d_basis_phi); (void)hipFree(c->d_basis_x0);
     (void)hipFree(c->d_fom_member); (void)hipFree(c->d_fom_rows);
     (void)hipFree(c->d_ha); (void)hipFree(c->d_ha_norm); (void)hipFree(c->d_gc); (void)hipFree(c->d_gcn);
@@ -1001,6 +1011,8 @@ extern "C" int grape_comm_attach(grape_ctx *c, const grape_comm_id *id, int32_t 
         return fail(c, GRAPE_ERR_UNSUPPORTED, "grape_comm_attach: the context already spans devices in-process");
     if (c->comm)
         return fail(c, GRAPE_ERR_INVALID_ARG, "grape_comm_attach: a communicator is already attached");
+    if (c->rc_terms > 0)
+        return fail(c, GRAPE_ERR_UNSUPPORTED, "grape_comm_attach: a running cost is set (grape_set_running_cost serves contexts without an exchange only)");
     RcclApi *api = rccl();
     if (!api) return fail(c, GRAPE_ERR_COMM, "grape_comm_attach: " + g_rccl.err);
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1068,6 +1080,8 @@ extern "C" int grape_ipc_attach(grape_ctx *c, const grape_ipc_handle *handles, i
         return fail(c, GRAPE_ERR_NOT_READY, "grape_ipc_attach: call grape_ipc_export(ctx, n_ranks, ...) first");
     if (c->comm || c->ipc_ranks > 1)
         return fail(c, GRAPE_ERR_INVALID_ARG, "grape_ipc_attach: a communicator is already attached");
+    if (c->rc_terms > 0)
+        return fail(c, GRAPE_ERR_UNSUPPORTED, "grape_ipc_attach: a running cost is set (grape_set_running_cost serves contexts without an exchange only)");
     HIP_TRY(c, hipSetDevice(c->device));
     double *opened[grape::kMaxShards] = {};
     for (int j = 0; j < n_ranks; ++j) {
@@ -1138,6 +1152,68 @@ extern "C" int grape_set_penalties(grape_ctx *c, const double *amp_w, const doub
         return GRAPE_OK;
     }
     return shard_set_penalties(c, w, on);
+}
+
+extern "C" int grape_set_running_cost(grape_ctx *c, int32_t n_terms, const double *R, const double *rho)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_set_running_cost: null context");
+    const bool off = n_terms == 0 || !R;
+    if (!off) {
+        if (n_terms < 0 || n_terms > 4)
+            return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_running_cost: n_terms = " + std::to_string(n_terms) + " (must be in 0..4)");
+        if (!rho) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_running_cost: null rho");
+        const char *why = nullptr;
+        const char *why_comm = "contexts with an attached communicator or mailbox exchange are not served";
+        if (c->is_group)                                     // (one shard: GRAPE_FLAG_FORCE_COLLECTIVE, a communicator of one rank)
+            why = c->sub.size() >= 2 ? "multi-device contexts are not served" : why_comm;
+        else if (c->comm || c->ipc_ranks > 1) why = why_comm;
+        else if (c->family != 0) why = "the operator dimension must be 2, 3 or 4 (the register-resident kernel family)";
+        else if (c->cfg.sys_type != GRAPE_UNITARY_GATE)
+            why = "StateTransfer / CoherenceTransfer (the sandwich needs a second term) are not served; hold the states as n x m columns under UnitaryGate";
+        else if (c->cfg.gradient == GRAPE_GRADIENT_EXACT) why = "gradient = exact is not served (the running cost's gradient is first order in dt)";
+        else if (c->cfg.objective != GRAPE_OBJECTIVE_FOM) why = "objective = c1 is not served";
+        if (why) return fail(c, GRAPE_ERR_UNSUPPORTED, std::string("grape_set_running_cost: ") + why);
+        const size_t nr = 2 * (size_t)c->cfg.n * c->m * c->cfg.n_ensemble * n_terms, nw = (size_t)c->cfg.n_slices * n_terms;
+        for (size_t i = 0; i < nr; ++i)
+            if (!std::isfinite(R[i]))
+                return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_running_cost: R[" + std::to_string(i / 2) + "] is not finite");
+        for (size_t i = 0; i < nw; ++i)
+            if (!std::isfinite(rho[i]))
+                return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_running_cost: rho[" + std::to_string(i) + "] is not finite");
+    }
+    if (c->is_group) {                                       // (switching off what can never be on)
+        c->rc_terms = 0;
+        return GRAPE_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->dev_pending) {                                    // (as grape_set_penalties: the buffers may be in use)
+        HIP_TRY(c, hipEventSynchronize(c->ev_dev));
+        c->dev_pending = false;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    double2 *d_R = nullptr;
+    double *d_rho = nullptr;
+    if (!off) {                                              // new buffers first: a failure leaves the previous setting in force
+        const size_t rb = sizeof(double2) * (size_t)c->cfg.n * c->m * c->cfg.n_ensemble * n_terms;
+        const size_t wb = sizeof(double) * (size_t)c->cfg.n_slices * n_terms;
+        hipError_t e = hipMalloc((void **)&d_R, rb);
+        if (e == hipSuccess) e = hipMemcpy(d_R, R, rb, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMalloc((void **)&d_rho, wb);
+        if (e == hipSuccess) e = hipMemcpy(d_rho, rho, wb, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(d_R);
+            (void)hipFree(d_rho);
+            (void)hipGetLastError();
+            return fail(c, e == hipErrorOutOfMemory ? GRAPE_ERR_ALLOC : GRAPE_ERR_HIP, std::string("grape_set_running_cost: ") + hipGetErrorString(e));
+        }
+    }
+    (void)hipFree(c->d_rc_R);
+    (void)hipFree(c->d_rc_rho);
+    c->d_rc_R = d_R;
+    c->d_rc_rho = d_rho;
+    c->rc_terms = off ? 0 : n_terms;
+    return GRAPE_OK;
 }
 
 static int wait_stream(grape_ctx *c, hipStream_t stream);
@@ -2151,6 +2227,39 @@ static bool states_stored(const grape_ctx *c)
 // this context adds the control penalties to its [G, F] (see grape_ctx::pen_on)
 static bool pen_active(const grape_ctx *c) { return c->pen_on && c->comm_rank == 0; }
 
+// grape_set_running_cost: the buffers an evaluation of n_x arrays needs behind the CURRENT workspace plan (member chunk, batch
+// capacity, flow) -- sized here because grape_set_operators may re-plan the workspace and decides the flow
+static int rc_ensure(grape_ctx *c)
+{
+    const size_t rows = sizeof(double) * (size_t)c->Ec * ws_batch(c) * (KN(c) + 1);
+    const size_t xs = c->unitary ? 0 : sizeof(double2) * (size_t)c->Ec * ws_batch(c) * c->S * c->CH * c->cfg.n * c->m;
+    if (rows > c->rc_rows_bytes) {
+        (void)hipFree(c->d_rc_rows);
+        c->d_rc_rows = nullptr;
+        c->bytes -= c->rc_rows_bytes;
+        c->rc_rows_bytes = 0;
+        if (hipMalloc((void **)&c->d_rc_rows, rows) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, GRAPE_ERR_ALLOC, "grape_set_running_cost: no device memory for the members' running-cost rows");
+        }
+        c->rc_rows_bytes = rows;
+        c->bytes += rows;
+    }
+    if (xs > c->rc_xs_bytes) {
+        (void)hipFree(c->d_rc_xs);
+        c->d_rc_xs = nullptr;
+        c->bytes -= c->rc_xs_bytes;
+        c->rc_xs_bytes = 0;
+        if (hipMalloc((void **)&c->d_rc_xs, xs) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, GRAPE_ERR_ALLOC, "grape_set_running_cost: no device memory for the stored states of the general flow");
+        }
+        c->rc_xs_bytes = xs;
+        c->bytes += xs;
+    }
+    return GRAPE_OK;
+}
+
 static bool tile_folds_reduce(const grape_ctx *c, int n_x)
 {
     if (c->family != 1 || c->cfg.n_ensemble != 1 || n_x != 1 || c->cfg.gradient == GRAPE_GRADIENT_EXACT || !c->direct_publish ||
@@ -2211,6 +2320,11 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
         }
         return GRAPE_OK;
     }
+    const bool rc_on = c->rc_terms > 0 && c->family == 0;
+    if (rc_on) {
+        const int rc = rc_ensure(c);
+        if (rc) return rc;
+    }
     KernelLogScope log_scope(&c->kernel_log);
     c->mf_wait = 0;
     SweepParams p{};
@@ -2264,9 +2378,10 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
     // one workgroup holds the whole ensemble (single problems): its row is [G, F], no reduce launch
     // (done.stage_base: this evaluation is the last array of a batch that runs array by array -- its publication has to
     // copy out the WHOLE staging buffer, which only the reduce kernels do: no self-closing sweep / fold then)
-    // (penalties: the reduce kernel adds them -- the sweep's own row goes through it)
+    // (penalties: the reduce kernel adds them -- the sweep's own row goes through it; a running cost joins that row behind
+    // the sweep, so it cannot be published by the sweep either)
     const bool direct = c->family == 0 && c->NB == 1 && n_x == 1 && !exact && c->direct_publish && !done.probe_out &&
-                        !done.stage_base && !pen_active(c);
+                        !done.stage_base && !pen_active(c) && !rc_on;
     const bool fold = !done.stage_base && tile_folds_reduce(c, n_x);
     if (direct) {
         p.direct_dst = done.flag && done.host_out ? done.host_out : d_fg;
@@ -2292,6 +2407,23 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
                 HIP_TRY(c, grape::launch_sweep_pair(c->cfg.n, c->cfg.sys_type != GRAPE_UNITARY_GATE, mode, q, stream));
             else
                 HIP_TRY(c, grape::launch_sweep_small(c->cfg.n, c->cfg.sys_type != GRAPE_UNITARY_GATE, mode, q, stream));
+            if (rc_on) {                                     // running cost of these members, from the propagators just stored
+                SweepParams r = q;
+                r.rc_only = 1;
+                r.rc_terms = c->rc_terms;
+                r.rc_m = c->m;
+                r.rc_unitary = c->unitary ? 1 : 0;
+                r.rc_CH = c->CH;
+                r.rc_Etot = c->cfg.n_ensemble;
+                r.rc_R = c->d_rc_R + (size_t)lo * c->cfg.n * c->m;
+                r.rc_rho = c->d_rc_rho;
+                r.rc_xs = c->d_rc_xs;
+                r.rc_rows = c->d_rc_rows;
+                if (c->pair)
+                    HIP_TRY(c, grape::launch_sweep_pair(c->cfg.n, 0, mode, r, stream));
+                else
+                    HIP_TRY(c, grape::launch_sweep_small(c->cfg.n, 0, mode, r, stream));
+            }
             if (exact) {                                     // exact gradient + objective from the stored trajectory
                 grape::ExactParams xq{};
                 xq.ops = q.ops;
@@ -3062,7 +3194,8 @@ extern "C" int grape_eval_batch_device(grape_ctx *c, int32_t n_x, const double *
 
 // ---- ABI v8: the figure of merit without the gradient ----------------------------------------------------------------------
 // fast path of grape_eval_fom: single device, no exchange attached, kernel family 0
-static bool fom_fast(const grape_ctx *c) { return !c->is_group && !c->comm && c->ipc_ranks <= 1 && c->family == 0; }
+// (a running cost needs the stored propagators: the full evaluation runs and its F is returned)
+static bool fom_fast(const grape_ctx *c) { return !c->is_group && !c->comm && c->ipc_ranks <= 1 && c->family == 0 && c->rc_terms == 0; }
 
 // The launches of the fast path on the context's stream: x upload, the forward-only kernel (reached through the sweep
 // launchers, SweepParams::fom_only) over the WHOLE ensemble and all n_x arrays at once -- it stores nothing per slice, so

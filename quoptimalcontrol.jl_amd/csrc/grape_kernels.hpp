@@ -129,7 +129,22 @@ struct SweepParams {
     double *fom_rows;     // (BPX, n_x) sum over the workgroup's members of w_k F_k: launch_reduce_rows with Q = 1 sums them
     int32_t fom_only;
     int32_t fom_objective;   // grape_objective: 0 fom_func, 1 C1(Xt, U Xi [U']) for every system type
+    // grape_set_running_cost (running_cost.hip): launch_sweep_small / launch_sweep_pair hand a launch with rc_only set to
+    // running_cost_kernel + running_cost_fold_kernel INSTEAD of the sweep: behind the sweep of the same members they read the
+    // propagators it stored (props, chunk-major with stride rc_CH) and add w_k [dJ_k/dx, J_k] to its block_out rows
+    int32_t rc_only;
+    int32_t rc_terms;        // probe matrices per member, 1..4
+    int32_t rc_m;            // state columns m (R, X are n x m)
+    int32_t rc_unitary;      // every propagator unitary: states are walked back with P'; 0: stored in rc_xs
+    int32_t rc_CH;           // time chunks per member = workspace stride (LT, or LT / 2 behind the pair kernel)
+    int32_t rc_Etot;         // members of the whole ensemble: term stride of rc_R
+    const double2 *rc_R;     // (n, m, rc_Etot, rc_terms) column-major, advanced to this launch's first member
+    const double *rc_rho;    // (N, rc_terms): entry [s - 1, j] weights the state after s slices
+    double2 *rc_xs;          // general flow: X_{t+1} per slice, chunk-major like props with n m elements per slice
+    double *rc_rows;         // (K N + 1) per (control array, member) of this launch: w_k [dJ_k/dx, J_k]
 };
+// running_cost.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::rc_only) only
+hipError_t run_running_cost(int n, const SweepParams &p, hipStream_t stream);
 // fom_small.hip; reached through launch_sweep_small (pair = false) / launch_sweep_pair (pair = true) only
 hipError_t launch_fom_small(int n, int sandwich, int mode, bool pair, const SweepParams &p, hipStream_t stream);
 

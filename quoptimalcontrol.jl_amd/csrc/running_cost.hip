@@ -1,0 +1,467 @@
+// running_cost.hip -- running costs on the intermediate states (grape_set_running_cost; the reference's C5 / C6 / C7,
+// src/cost_functions.jl:44-61) for the small-n family (n = 2, 3, 4; n x m states under left multiplication) on gfx950.
+//
+//   J      = sum_k w_k sum_j sum_{s=1..N} rho[s-1,j] |y_{k,j,s}|^2 ,   y_{k,j,s} = tr(R_{k,j}' X_{k,s})
+//   dJ/dx[c,t] ~ sum_k w_k sum_j 2 Re tr(Lam_{k,j,t+1}' B'_{k,c} X_{k,t+1}) ,   B' = -i dt B  (first order in dt, as grad_func!)
+//   Lam_{j,N} = rho[N-1,j] y_{j,N} R_j ,   Lam_{j,s} = P_s' Lam_{j,s+1} + rho[s-1,j] y_{j,s} R_j
+//
+// It runs behind the sweep of the same launch and reads the propagators P_t that sweep left in the workspace (chunk-major:
+// element e of slice t = c S + jj of member k at ((k S + jj) n^2 + e) CH + c).  One workgroup per (control array, member),
+// one lane per time chunk of S consecutive slices -- the sweep's own decomposition, so every workspace access is
+// lane-contiguous:
+//   1  chunk product Q_c = P_hi-1 ... P_lo                                   (P read once)
+//   2  inclusive/exclusive prefix scan of the Q_c over lanes (wave shuffles, wave totals through LDS): X at the chunk start
+//   3  the states of the chunk: unitary flow (every generator Hermitian): only X at the chunk END = Q_c X_start is kept and
+//      the walks below step back with X_s = P_s' X_s+1; general flow: a forward walk stores X_s+1 per slice in a scratch
+//      array of the chunk-major layout (there is no P' to walk back with)
+//   then per term j (the recurrences of different terms share nothing but P and X):
+//   4  backward walk from Lam = 0: b_c, the chunk's own contribution to the costate that leaves it on the left
+//   5  suffix scan of the affine maps z -> Q_c' z + b_c over lanes, composition (Q1' Q2', Q1' b2 + b1) in a fixed tree
+//      (shuffles inside a wave, wave totals through LDS, combined last wave first)
+//   6  the same backward walk from the true incoming costate: Lam_t+1 at every slice, M = X_t+1 Lam_t+1', and the K traces
+//      2 Re tr(B'_c M) weighted by w_k -- stored to (term 0) or added to (later terms; same lane, program order) the
+//      member's row
+// Ragged decompositions: a lane whose chunk starts at or behind N owns no slice (Q = 1, b = 0), the last chunk may be short.
+// No atomics, plain vector stores; the fold kernel below adds the members' rows to the sweep's per-workgroup rows in member
+// order, so the ensemble sum that follows is the one it always was and results are bitwise reproducible.
+#include "cmat.hpp"
+#include "grape_kernels.hpp"
+
+namespace grape {
+
+// n x m complex block (the states, costates and probe matrices), column-major e = i + j n
+template <int N, int M>
+struct CRect {
+    double re[N * M];
+    double im[N * M];
+};
+
+template <int N, int M>
+GRAPE_DEV void rzero(CRect<N, M> &a)
+{
+#pragma unroll
+    for (int e = 0; e < N * M; ++e) {
+        a.re[e] = 0.0;
+        a.im[e] = 0.0;
+    }
+}
+
+// C = A B  (A n x n, B n x m)
+template <int N, int M>
+GRAPE_DEV void rmul(CRect<N, M> &c, const CMat<N> &a, const CRect<N, M> &b)
+{
+#pragma unroll
+    for (int j = 0; j < M; ++j)
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            double sr = 0.0, si = 0.0;
+#pragma unroll
+            for (int k = 0; k < N; ++k) {
+                const double ar = a.re[i + k * N], ai = a.im[i + k * N];
+                const double br = b.re[k + j * N], bi = b.im[k + j * N];
+                sr = fma(ar, br, sr);
+                sr = fma(-ai, bi, sr);
+                si = fma(ar, bi, si);
+                si = fma(ai, br, si);
+            }
+            c.re[i + j * N] = sr;
+            c.im[i + j * N] = si;
+        }
+}
+
+// C = A^H B
+template <int N, int M>
+GRAPE_DEV void rmul_ah(CRect<N, M> &c, const CMat<N> &a, const CRect<N, M> &b)
+{
+#pragma unroll
+    for (int j = 0; j < M; ++j)
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            double sr = 0.0, si = 0.0;
+#pragma unroll
+            for (int k = 0; k < N; ++k) {
+                const double ar = a.re[k + i * N], ai = -a.im[k + i * N];
+                const double br = b.re[k + j * N], bi = b.im[k + j * N];
+                sr = fma(ar, br, sr);
+                sr = fma(-ai, bi, sr);
+                si = fma(ar, bi, si);
+                si = fma(ai, br, si);
+            }
+            c.re[i + j * N] = sr;
+            c.im[i + j * N] = si;
+        }
+}
+
+// C (n x n) = X Lam^H  (both n x m)
+template <int N, int M>
+GRAPE_DEV void rmul_a_bh(CMat<N> &c, const CRect<N, M> &a, const CRect<N, M> &b)
+{
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            double sr = 0.0, si = 0.0;
+#pragma unroll
+            for (int k = 0; k < M; ++k) {
+                const double ar = a.re[i + k * N], ai = a.im[i + k * N];
+                const double br = b.re[j + k * N], bi = -b.im[j + k * N];
+                sr = fma(ar, br, sr);
+                sr = fma(-ai, bi, sr);
+                si = fma(ar, bi, si);
+                si = fma(ai, br, si);
+            }
+            c.re[i + j * N] = sr;
+            c.im[i + j * N] = si;
+        }
+}
+
+template <int N, int M>
+GRAPE_DEV void rshfl_down(CRect<N, M> &dst, const CRect<N, M> &src, int delta)
+{
+#pragma unroll
+    for (int e = 0; e < N * M; ++e) {
+        dst.re[e] = __shfl_down(src.re[e], delta, 64);
+        dst.im[e] = __shfl_down(src.im[e], delta, 64);
+    }
+}
+
+template <int N, int M>
+GRAPE_DEV void rload_uniform(CRect<N, M> &m, const double2 *__restrict__ src)
+{
+#pragma unroll
+    for (int e = 0; e < N * M; ++e) {
+        const double2 v = src[e];
+        m.re[e] = v.x;
+        m.im[e] = v.y;
+    }
+}
+
+template <int N>
+GRAPE_DEV void rc_load_mat(CMat<N> &m, const double2 *__restrict__ base, size_t stride)
+{
+#pragma unroll
+    for (int e = 0; e < N * N; ++e) {
+        const double2 v = base[e * stride];
+        m.re[e] = v.x;
+        m.im[e] = v.y;
+    }
+}
+
+template <int N>
+GRAPE_DEV void rc_load_lds(CMat<N> &m, const double2 *src)
+{
+#pragma unroll
+    for (int e = 0; e < N * N; ++e) {
+        const double2 v = src[e];
+        m.re[e] = v.x;
+        m.im[e] = v.y;
+    }
+}
+
+template <int N, int M>
+GRAPE_DEV void rload_ws(CRect<N, M> &m, const double2 *__restrict__ base, size_t stride)
+{
+#pragma unroll
+    for (int e = 0; e < N * M; ++e) {
+        const double2 v = base[e * stride];
+        m.re[e] = v.x;
+        m.im[e] = v.y;
+    }
+}
+
+template <int N, int M>
+GRAPE_DEV void rstore_ws(double2 *__restrict__ base, size_t stride, const CRect<N, M> &m)
+{
+#pragma unroll
+    for (int e = 0; e < N * M; ++e)
+        base[e * stride] = make_double2(m.re[e], m.im[e]);
+}
+
+// ops_all / r_all / rho / wts_all are separate `const __restrict__` arguments so that the wave-uniform operator, probe and
+// weight entries can be fetched with scalar loads (as in sweep_small.hip).  UNI: every propagator is unitary.
+template <int N, int M, bool UNI, int MAXT>
+__global__ __launch_bounds__(MAXT) void running_cost_kernel(const double2 *__restrict__ ops_all,
+                                                            const double2 *__restrict__ r_all,
+                                                            const double *__restrict__ rho,
+                                                            const double *__restrict__ wts_all, const SweepParams p)
+{
+    constexpr int NN = N * N, NM = N * M, MAXW = MAXT / 64;
+    __shared__ double2 s_q[MAXW][NN];              // wave totals: prefix products, then the affine maps' matrices ...
+    __shared__ double2 s_v[MAXW][NM];              // ... and their offsets
+    __shared__ double s_j[MAXW];
+
+    const int CH = p.rc_CH, S = p.S, K = p.K, Nsl = p.N;
+    const int L = threadIdx.x, lane = L & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(L >> 6), W = blockDim.x >> 6;
+    const int k = blockIdx.x;                        // row of the workspace and of the output: (control array, member)
+    const int kl = k % p.E;                          // member within the launch
+    // the lane's slices [lo, hi): none for chunks that start at or behind N and for the padding lanes behind chunk CH - 1
+    const int lo = (L < CH && L * S < Nsl) ? L * S : Nsl;
+    const int hi = min(lo + S, Nsl);
+    const int cnt = hi - lo;
+    const size_t stride = (size_t)CH;
+    const double2 *__restrict__ Pw = p.props + (size_t)k * S * NN * stride + L;
+    double2 *__restrict__ Xw = UNI ? nullptr : p.rc_xs + (size_t)k * S * NM * stride + L;
+    const double2 *__restrict__ ops = ops_all + (size_t)kl * (K + 3) * NN;
+    const double2 *__restrict__ opB = ops + NN;
+    const double2 *__restrict__ opXi = ops + (size_t)(1 + K) * NN;
+    double *__restrict__ row = p.rc_rows + (size_t)k * ((size_t)K * Nsl + 1);
+    const double wk = wts_all[kl];
+
+    // ---------------------------------------------------------------- 1: chunk product
+    CMat<N> Q, P, T;
+    set_identity(Q);
+    for (int jj = 0; jj < cnt; ++jj) {
+        rc_load_mat(P, Pw + (size_t)jj * NN * stride, stride);
+        mul(T, P, Q);
+        Q = T;
+    }
+    // ---------------------------------------------------------------- 2: exclusive prefix over lanes -> X at the chunk start
+    CRect<N, M> Xhi;
+    {
+        CMat<N> inc = Q, oth;
+        for (int d = 1; d < 64; d <<= 1) {
+            shfl_up(oth, inc, d);
+            if (lane >= d) {
+                mul(T, inc, oth);
+                inc = T;
+            }
+        }
+        shfl_up(oth, inc, 1);
+        if (lane == 0)
+            set_identity(oth);
+        if (W > 1) {
+            if (lane == 63) {
+#pragma unroll
+                for (int e = 0; e < NN; ++e)
+                    s_q[wave][e] = make_double2(inc.re[e], inc.im[e]);
+            }
+            __syncthreads();
+            CMat<N> pre;
+            set_identity(pre);
+            for (int w = 0; w < wave; ++w) {
+                rc_load_lds(inc, &s_q[w][0]);
+                mul(T, inc, pre);
+                pre = T;
+            }
+            mul(T, oth, pre);
+            oth = T;
+        }
+        CRect<N, M> xi, Xs;
+        rload_uniform(xi, opXi);                     // (the first m columns of the zero-padded n x n block)
+        rmul(Xs, oth, xi);
+        // ------------------------------------------------------------ 3: the chunk's states
+        if (UNI) {
+            rmul(Xhi, Q, Xs);
+        } else {
+            Xhi = Xs;
+            for (int jj = 0; jj < cnt; ++jj) {
+                rc_load_mat(P, Pw + (size_t)jj * NN * stride, stride);
+                rmul(Xs, P, Xhi);
+                Xhi = Xs;
+                rstore_ws(Xw + (size_t)jj * NM * stride, stride, Xhi);      // the state AFTER slice lo + jj
+            }
+        }
+    }
+
+    double jpart = 0.0;
+    for (int j = 0; j < p.rc_terms; ++j) {
+        CRect<N, M> R;
+        rload_uniform(R, r_all + ((size_t)j * p.rc_Etot + kl) * NM);
+        const double *__restrict__ rho_j = rho + (size_t)j * Nsl;
+        // one backward walk over the chunk from the costate Lam that enters it on the right; EMIT: with the gradient traces
+        auto walk = [&](CRect<N, M> &Lam, const bool emit) {
+            CRect<N, M> X = Xhi, Tm;
+            for (int jj = cnt - 1; jj >= 0; --jj) {
+                const int t = lo + jj;               // slice index; the state behind it is X_{t+1}, weighted by rho[t]
+                if (!UNI)
+                    rload_ws(X, Xw + (size_t)jj * NM * stride, stride);
+                rc_load_mat(P, Pw + (size_t)jj * NN * stride, stride);
+                double yr = 0.0, yi = 0.0;           // y = tr(R' X)
+#pragma unroll
+                for (int e = 0; e < NM; ++e) {
+                    yr = fma(R.re[e], X.re[e], yr);
+                    yr = fma(R.im[e], X.im[e], yr);
+                    yi = fma(R.re[e], X.im[e], yi);
+                    yi = fma(-R.im[e], X.re[e], yi);
+                }
+                const double r = rho_j[t];
+                const double cr = r * yr, ci = r * yi;
+                if (!emit)
+                    jpart = fma(r, fma(yr, yr, yi * yi), jpart);
+#pragma unroll
+                for (int e = 0; e < NM; ++e) {       // Lam_{t+1} = (what came from the right) + rho y R
+                    Lam.re[e] = fma(cr, R.re[e], fma(-ci, R.im[e], Lam.re[e]));
+                    Lam.im[e] = fma(cr, R.im[e], fma(ci, R.re[e], Lam.im[e]));
+                }
+                if (emit) {
+                    CMat<N> Mx;
+                    rmul_a_bh(Mx, X, Lam);           // X Lam'
+                    for (int c = 0; c < K; ++c) {
+                        double re = 0.0;
+#pragma unroll
+                        for (int b2 = 0; b2 < N; ++b2)
+#pragma unroll
+                            for (int a2 = 0; a2 < N; ++a2) {
+                                const double2 b = opB[c * NN + a2 + b2 * N];
+                                re = fma(b.x, Mx.re[b2 + a2 * N], re);
+                                re = fma(-b.y, Mx.im[b2 + a2 * N], re);
+                            }
+                        const double g = 2.0 * wk * re;
+                        double *dst = row + (size_t)t * K + c;
+                        *dst = (j == 0) ? g : *dst + g;
+                    }
+                }
+                rmul_ah(Tm, P, Lam);                 // pull the costate back over slice t
+                Lam = Tm;
+                if (UNI) {
+                    rmul_ah(Tm, P, X);
+                    X = Tm;
+                }
+            }
+        };
+        // ------------------------------------------------------------ 4: the chunk's affine map
+        CRect<N, M> bvec;
+        rzero(bvec);
+        walk(bvec, false);
+        // ------------------------------------------------------------ 5: suffix scan of (Q', b)
+        CRect<N, M> Lin;
+        {
+            CMat<N> G = Q, Go;
+            CRect<N, M> v = bvec, vo, Tm;
+            for (int d = 1; d < 64; d <<= 1) {
+                shfl_down(Go, G, d);
+                rshfl_down(vo, v, d);
+                if (lane + d < 64) {                 // [L, L+d) then [L+d, L+2d):  (Go G)' z + (G' vo + v)
+                    rmul_ah(Tm, G, vo);
+#pragma unroll
+                    for (int e = 0; e < NM; ++e) {
+                        v.re[e] += Tm.re[e];
+                        v.im[e] += Tm.im[e];
+                    }
+                    mul(T, Go, G);
+                    G = T;
+                }
+            }
+            shfl_down(Go, G, 1);                     // the lanes behind this one, inside the wave
+            rshfl_down(vo, v, 1);
+            if (lane == 63) {
+                set_identity(Go);
+                rzero(vo);
+            }
+            if (W > 1) {
+                __syncthreads();                     // (the previous readers of s_q / s_v are done)
+                if (lane == 0) {
+#pragma unroll
+                    for (int e = 0; e < NN; ++e)
+                        s_q[wave][e] = make_double2(G.re[e], G.im[e]);
+#pragma unroll
+                    for (int e = 0; e < NM; ++e)
+                        s_v[wave][e] = make_double2(v.re[e], v.im[e]);
+                }
+                __syncthreads();
+                CRect<N, M> z;
+                rzero(z);
+                for (int w = W - 1; w > wave; --w) { // what enters this wave on the right, last wave first
+                    rc_load_lds(G, &s_q[w][0]);
+                    rmul_ah(Tm, G, z);
+#pragma unroll
+                    for (int e = 0; e < NM; ++e) {
+                        const double2 vv = s_v[w][e];
+                        z.re[e] = Tm.re[e] + vv.x;
+                        z.im[e] = Tm.im[e] + vv.y;
+                    }
+                }
+                rmul_ah(Tm, Go, z);
+#pragma unroll
+                for (int e = 0; e < NM; ++e) {
+                    Lin.re[e] = Tm.re[e] + vo.re[e];
+                    Lin.im[e] = Tm.im[e] + vo.im[e];
+                }
+            } else {
+                Lin = vo;
+            }
+        }
+        // ------------------------------------------------------------ 6: the true costates, the traces
+        walk(Lin, true);
+    }
+
+    // J of this member: lanes in a fixed butterfly, waves in order
+    for (int d = 32; d >= 1; d >>= 1)
+        jpart += __shfl_xor(jpart, d, 64);
+    if (W > 1)
+        __syncthreads();
+    if (lane == 0)
+        s_j[wave] = jpart;
+    __syncthreads();
+    if (L == 0) {
+        double tot = 0.0;
+        for (int w = 0; w < W; ++w)
+            tot += s_j[w];
+        row[(size_t)K * Nsl] = wk * tot;
+    }
+}
+
+// block_out[b][q] += sum over the members m of sweep workgroup b, ascending, of rows[member][q]: the running cost joins the
+// sweep's weighted per-workgroup rows, and the ensemble reduction behind them stays what it was
+__global__ __launch_bounds__(256) void running_cost_fold_kernel(const double *__restrict__ rows, double *__restrict__ block_out,
+                                                                int MPB, int E, int BPX, int Q)
+{
+    const int q = blockIdx.y * 256 + threadIdx.x;
+    if (q >= Q)
+        return;
+    const int xi = blockIdx.x / BPX, bi = blockIdx.x - xi * BPX;
+    const int m0 = bi * MPB, nmem = min(MPB, E - m0);
+    double acc = block_out[(size_t)blockIdx.x * Q + q];
+    for (int m = 0; m < nmem; ++m)
+        acc += rows[((size_t)xi * E + m0 + m) * Q + q];
+    block_out[(size_t)blockIdx.x * Q + q] = acc;
+}
+
+template <int N>
+struct RcTraits;
+template <> struct RcTraits<2> { static constexpr int MAXT = 1024; };
+template <> struct RcTraits<3> { static constexpr int MAXT = 512; };
+template <> struct RcTraits<4> { static constexpr int MAXT = 256; };
+
+template <int N, int M>
+static hipError_t rc_launch_nm(const SweepParams &p, hipStream_t stream)
+{
+    constexpr int MAXT = RcTraits<N>::MAXT;
+    const int threads = (p.rc_CH + 63) & ~63;
+    if (threads > MAXT || p.rc_CH < 1 || (long long)p.S * p.rc_CH < p.N || !p.rc_rows || !p.rc_R || !p.rc_rho ||
+        (!p.rc_unitary && !p.rc_xs) || p.rc_terms < 1)
+        return hipErrorInvalidConfiguration;
+    const dim3 grid(p.E * p.n_x), block(threads);
+    if (p.rc_unitary)
+        GRAPE_LAUNCH_AS("running_cost_kernel", (running_cost_kernel<N, M, true, MAXT>), grid, block, 0, stream, p.ops, p.rc_R,
+                        p.rc_rho, p.wts, p);
+    else
+        GRAPE_LAUNCH_AS("running_cost_kernel", (running_cost_kernel<N, M, false, MAXT>), grid, block, 0, stream, p.ops, p.rc_R,
+                        p.rc_rho, p.wts, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return e;
+    const int Qr = p.K * p.N + 1;
+    GRAPE_LAUNCH(running_cost_fold_kernel, dim3(p.BPX * p.n_x, (Qr + 255) / 256), dim3(256), 0, stream, p.rc_rows, p.block_out,
+                 p.MPB, p.E, p.BPX, Qr);
+    return hipGetLastError();
+}
+
+hipError_t run_running_cost(int n, const SweepParams &p, hipStream_t stream)
+{
+    switch (n * 8 + p.rc_m) {
+    case 2 * 8 + 1: return rc_launch_nm<2, 1>(p, stream);
+    case 2 * 8 + 2: return rc_launch_nm<2, 2>(p, stream);
+    case 3 * 8 + 1: return rc_launch_nm<3, 1>(p, stream);
+    case 3 * 8 + 2: return rc_launch_nm<3, 2>(p, stream);
+    case 3 * 8 + 3: return rc_launch_nm<3, 3>(p, stream);
+    case 4 * 8 + 1: return rc_launch_nm<4, 1>(p, stream);
+    case 4 * 8 + 2: return rc_launch_nm<4, 2>(p, stream);
+    case 4 * 8 + 3: return rc_launch_nm<4, 3>(p, stream);
+    case 4 * 8 + 4: return rc_launch_nm<4, 4>(p, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace grape

@@ -1260,6 +1260,8 @@ hipError_t launch_sweep_pair(int n, int sandwich, int mode, const SweepParams &p
 {
     if (p.fom_only)                                  // grape_eval_fom: the forward-only kernel (fom_small.hip)
         return launch_fom_small(n, sandwich, mode, true, p, stream);
+    if (p.rc_only)                                   // grape_set_running_cost: the kernels behind the sweep (running_cost.hip)
+        return run_running_cost(n, p, stream);
     switch (n * 2 + (sandwich ? 1 : 0)) {
     case 4: return plaunch_ns<2, 0>(mode, p, stream);
     case 5: return plaunch_ns<2, 1>(mode, p, stream);

@@ -36,6 +36,7 @@ STATUS = {0: "GRAPE_OK", -1: "GRAPE_ERR_INVALID_ARG", -2: "GRAPE_ERR_UNSUPPORTED
 
 # every symbol include/grape_hip.h declares
 EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_operators", "grape_set_penalties",
+           "grape_set_running_cost",
            "grape_set_basis", "grape_get_controls",
            "grape_comm_unique_id", "grape_comm_attach", "grape_ipc_export", "grape_ipc_attach",
            "grape_eval", "grape_eval_device", "grape_eval_batch", "grape_eval_batch_device", "grape_eval_fom", "grape_lbfgs", "grape_lbfgs_get_trace",
@@ -122,6 +123,7 @@ def load_library():
     L.grape_destroy.argtypes = [vp]
     L.grape_set_operators.argtypes = [vp] * 6
     L.grape_set_penalties.argtypes = [vp, vp, vp]
+    L.grape_set_running_cost.argtypes = [vp, i32, vp, vp]
     L.grape_set_basis.argtypes = [vp, i32, i32, vp, vp]
     L.grape_get_controls.argtypes = [vp, vp, vp]
     L.grape_comm_unique_id.argtypes = [C.POINTER(GrapeCommId)]
@@ -244,6 +246,35 @@ class GrapeEngine:
             return w
         a, v = vec(amp), vec(var)
         self._check(self._lib.grape_set_penalties(self._h, _p(a), _p(v)))
+
+    def set_running_cost(self, R, rho=None):
+        """grape_set_running_cost: running costs on the intermediate states (the reference's C5 / C6 / C7,
+        src/cost_functions.jl:44-61).  R: probe matrices (n_terms, E, n, m) or anything that broadcasts to it -- (n, m): one
+        term, the same for every member; (E, n, m): one term per member; (n_terms, 1, n, m): shared by the members; at most 4
+        terms.  rho: slice weights (n_terms, N), or (N,) / a scalar for every term; rho[j, s-1] weights the state after s
+        slices.  From now on every evaluation returns F + sum_k w_k sum_j sum_s rho[j, s-1] |tr(R_kj' X_ks)|^2 and its
+        first-order gradient (include/grape_hip.h).  R=None switches the term off.  n = 2..4, UnitaryGate-type states,
+        single-device contexts; member_results() stays without it."""
+        if R is None:
+            self._check(self._lib.grape_set_running_cost(self._h, 0, None, None))
+            return
+        if rho is None:
+            raise ValueError("set_running_cost: rho is needed with R")
+        R = np.asarray(R, dtype=np.complex128)
+        rho = np.asarray(rho, dtype=np.float64)
+        if R.ndim < 2 or R.ndim > 4 or rho.ndim > 2:
+            raise ValueError("set_running_cost: R must broadcast to (n_terms, E, n, m) and rho to (n_terms, N)")
+        J = R.shape[0] if R.ndim == 4 else (rho.shape[0] if rho.ndim == 2 else 1)
+        if not 1 <= J <= 4:
+            raise ValueError("set_running_cost: 1 to 4 terms")
+        try:
+            Rf = np.broadcast_to(R, (J, self.E, self.n, self.m))
+            rf = np.broadcast_to(rho, (J, self.N))
+        except ValueError:
+            raise ValueError(f"set_running_cost: R must broadcast to ({J}, {self.E}, {self.n}, {self.m}) and rho to "
+                             f"({J}, {self.N})") from None
+        rf = np.ascontiguousarray(rf)
+        self._check(self._lib.grape_set_running_cost(self._h, J, _p(_cm(Rf)), _p(rf)))
 
     def set_basis(self, phi, x0=None):
         """grape_set_basis: restrict the pulse to x[c,t] = x0[c,t] + sum_m theta[c,m] phi[t,m] -- "parameter mode".
