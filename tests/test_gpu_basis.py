@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, assert_parity
+from settings_sequences import compare_lbfgs_iterates
 from test_gpu_fom import random_problem as fom_problem
 from test_gpu_tile import _random_problem
 
@@ -356,31 +357,7 @@ def test_lbfgs_iterates_match_the_host_restatement_in_parameter_mode(qoc, case):
         ref = optim_lbfgs.lbfgs(composed, theta0, iterations=n_it)
     with qoc.GrapeEngine(*args) as eng:
         eng.set_basis(phi, x0)
-        xs = []
-        for k in range(1, n_it + 1):
-            xk, info = eng.lbfgs(theta0, iterations=k, line_search="optim")
-            xs.append(xk)
-            if info["status"] != 2:
-                break
-        al, ev = eng.lbfgs_trace()
-    tr = ref["trace"]
-    assert len(al) == len(xs) and len(al) >= min(len(tr), n_it) and len(al) > 3
-    per_dev = np.diff(np.concatenate([[1], ev]))
-    per_ref = np.diff([1] + [t["evaluations"] for t in tr])
-    compared = 0
-    for i in range(len(al)):
-        a_ref, x_ref = tr[i]["alpha"], tr[i]["x"].reshape(theta0.shape)
-        print(f"{case} iteration {i}: alpha {al[i]!r} vs {a_ref!r}, |dtheta| = {np.abs(xs[i] - x_ref).max():.3e}, "
-              f"evaluations {per_dev[i]} vs {per_ref[i]}")
-        assert abs(al[i] - a_ref) <= 1e-6 * abs(a_ref), (case, i, al[i], a_ref)
-        assert xs[i].shape == theta0.shape and np.abs(xs[i] - x_ref).max() <= 1e-9 * max(1.0, np.abs(x_ref).max()), (case, i)
-        compared += 1
-        if per_ref[i] <= 15:
-            assert per_dev[i] == per_ref[i], (case, i, list(per_dev), list(per_ref))
-        else:
-            assert per_dev[i] > 30 and abs(int(per_dev[i]) - int(per_ref[i])) <= 12, (case, i, list(per_dev), list(per_ref))
-            break
-    assert compared >= 8, (case, compared)
+        compare_lbfgs_iterates(eng, ref, theta0, n_it, case, min_compared=8)
 
 
 # ---- 6. solve() over Fourier coefficients ---------------------------------------------------------------------------------
