@@ -345,8 +345,44 @@ int grape_set_basis(grape_ctx *ctx, int32_t n_params, int32_t n_bases, const dou
 
 /* The physical pulse of a parameter array, expanded ON THE DEVICE by the kernel the evaluations use:
  *   theta host f64 (K, M)      x host f64 (K, N)
- * Blocking; ordered behind an in-flight grape_eval_device.  Without a basis x = theta ((K, N) both). */
+ * Blocking; ordered behind an in-flight grape_eval_device.  Without a basis x = theta ((K, N) both).  With
+ * grape_set_bounds in force x is the saturated pulse (of theta's expansion, or of the raw (K, N) array without a basis). */
 int grape_get_controls(grape_ctx *ctx, const double *theta, double *x);
+
+/* Smooth amplitude bounds: a pointwise, differentiable map from a raw pulse u to the physical pulse, so that
+ * lo_c < x[c,t] < hi_c holds for every finite u and every optimiser of the library works unchanged.  Additive to ABI v8.
+ *   lo, hi  host f64[K] each (K = n_controls); both NULL: bounds off
+ * For a control with finite lo_c < hi_c, mid = (lo + hi) / 2 and half = (hi - lo) / 2:
+ *   x[c,t]   = mid_c + half_c * tanh((u[c,t] - mid_c) / half_c)
+ *   s[c,t]   = 1 - tanh^2(...)          (dx/du: 1 at u = mid, so pulses small against half are unchanged to first order)
+ *   G_u[c,t] = G_tot[c,t] * s[c,t]
+ * A control with lo = -inf and hi = +inf is the identity (s = 1).  Everything else -- a one-sided pair, lo >= hi, NaN, one
+ * pointer NULL -- is GRAPE_ERR_INVALID_ARG.  When EVERY control is (-inf, +inf) the call is the same as switching the bounds
+ * off: the context behaves exactly like one that never called this (same kernels, same bits).
+ * With bounds in force every `x` argument of grape_eval, grape_eval_device, grape_eval_batch, grape_eval_batch_device,
+ * grape_eval_fom and grape_lbfgs (x0 and x_min) is the raw u, every returned G is G_u, and F is the F of the physical pulse.
+ * The penalties of grape_set_penalties and the running costs of grape_set_running_cost are evaluated on the physical x;
+ * their gradients are part of G_tot, in front of the slope.
+ * With a basis: expand, saturate, evaluate, ..., slope, project --
+ *   x = sat(x0 + theta phi^T),   G_theta[c,m] = sum_t G_tot[c,t] s[c,t] phi_b[t,m]
+ * (a bounded Fourier / CRAB pulse; the entry points take theta as grape_set_basis describes).  The saturation is fused into
+ * basis_expand_kernel, the slope into basis_project_kernel's multiply-add, whose order does not change; without a basis
+ * bounds_saturate_kernel stands in for the upload of x and bounds_slope_kernel is the evaluation's last kernel.  Results
+ * are bitwise reproducible call to call, and F is bit for bit what a context without bounds returns through the
+ * device-pointer entry points for the pulse grape_get_controls returns.  grape_lbfgs probes as it does in parameter mode
+ * (the evaluation does not end in a reduce kernel).  grape_get_controls returns the physical (saturated) pulse;
+ * grape_get_member_results, grape_get_trajectory and the member_F of grape_eval_fom stay in physical slice space, without
+ * the slope.  The fast path of grape_eval_fom saturates in place of its upload and needs no slope.
+ * The slope vanishes in saturation: where tanh has rounded to +-1 (|u - mid| above ~19 half) x is held at the last double
+ * inside the interval, s = 0 and the gradient entry is exactly 0 -- a gradient method started there does not move that
+ * entry.  Start inside (the Python layer clips a guess to mid +- 0.999 half before it inverts the map).
+ * Valid any time after grape_create, before or after grape_set_operators (the bounds persist across it); ordered behind an
+ * in-flight grape_eval_device as grape_set_operators is.  After any failure the previous setting stays in force.  Switching
+ * the bounds off restores the previous behaviour exactly; a context that never calls this launches the kernels it always
+ * did.  Multi-device contexts saturate once on the first device, in front of the fan-out of x.  With grape_comm_attach /
+ * grape_ipc_attach every rank sets the same bounds and saturates its own copy; every rank applies the slope to the
+ * exchanged row. */
+int grape_set_bounds(grape_ctx *ctx, const double *lo, const double *hi);
 
 /* The closure body, src/solve.jl:164-196 (E>1) / :75-100 (E=1):
  *   F = sum_k w_k F_k ,  G[c,t] = sum_k w_k g_k[c,t]   with (F_k, g_k) = _fom_and_gradient_GRAPE!.

@@ -171,7 +171,23 @@ function set_basis!(ctx::GrapeContext, phi::Union{Nothing,Array{Float64}}, x0::U
                                          x0 === nothing ? C_NULL : x0))
 end
 
-"grape_get_controls: the physical pulse (K, N) of a parameter array theta (K, M), expanded on the device."
+# grape_set_bounds: smooth amplitude bounds.  lo, hi: one entry per control, finite lo < hi, or -Inf / Inf for a control that
+# stays free; from here on every x handed to this context is the raw pulse u (theta with a basis), the evaluation runs on
+# x = mid + half tanh((u - mid) / half) and every gradient is with respect to u.  lo = nothing switches the bounds off.
+# (Not executed where this file was written: no Julia toolchain there; the Python binding makes the same call and is tested
+# on the GPU.)
+function set_bounds!(ctx::GrapeContext, lo::Union{Nothing,Vector{Float64}}, hi::Union{Nothing,Vector{Float64}} = nothing)
+    if lo === nothing
+        return check(ctx, ccall((:grape_set_bounds, libgrape), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}),
+                                ctx.handle, C_NULL, C_NULL))
+    end
+    hi === nothing && throw(ArgumentError("set_bounds!: hi is needed with lo"))
+    length(lo) == ctx.K && length(hi) == ctx.K || throw(DimensionMismatch("lo and hi must have n_controls entries"))
+    GC.@preserve lo hi check(ctx, ccall((:grape_set_bounds, libgrape), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}),
+                                        ctx.handle, lo, hi))
+end
+
+"grape_get_controls: the physical pulse (K, N) of a parameter array theta (K, M), expanded (and, with bounds, saturated) on the device."
 function controls(ctx::GrapeContext, theta::Matrix{Float64})
     x = Matrix{Float64}(undef, ctx.K, ctx.N)
     GC.@preserve theta x check(ctx, ccall((:grape_get_controls, libgrape), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}),

@@ -30,6 +30,7 @@ import json
 
 import numpy as np
 
+from .bounds import bounds_start
 from .engine import GrapeEngine
 
 
@@ -101,6 +102,13 @@ class GRAPE:
                                    # expanded and projected on the device (grape_set_basis).  The start is the least-squares
                                    # fit of the problem's guess; the result carries the physical pulse and `parameters`
     basis_offset: Any = None       # (K, N) pulse the expansion is added to; None: zero
+    bounds: Any = None             # (lo, hi), scalars or K-vectors (new): smooth amplitude bounds on the device
+                                   # (grape_set_bounds).  The optimiser -- host or device -- runs over raw variables u with
+                                   # x = mid + half tanh((u - mid) / half) strictly inside (lo, hi).  The start is the inverse
+                                   # map of the problem's guess, first clipped to mid +- 0.999 half (a start in saturation has
+                                   # a vanishing gradient; the guess object is not modified).  With a basis the bounds apply to
+                                   # the expanded pulse and the start is the fit of that raw pulse.  `opti_pulses` is the
+                                   # physical pulse, `parameters` the raw variables (theta with a basis)
     running_costs: Any = None      # list of ForbiddenStates / EvolutionTime (new: the reference's C5 / C6 / C7 are called by none
                                    # of its solvers): costs on the intermediate states, added to the objective on the device
                                    # (grape_set_running_cost; n = 2..4, UnitaryGate-type problems, one device)
@@ -453,6 +461,8 @@ def save(solres, file_path):
                                             "devices": None if alg.devices is None else [int(v) for v in alg.devices],
                                             "peer_sum": bool(alg.peer_sum),
                                             **({"penalties": alg.penalties.to_json()} if alg.penalties is not None else {}),
+                                            **({"bounds": [np.asarray(b, dtype=np.float64).tolist() for b in alg.bounds]}
+                                               if getattr(alg, "bounds", None) is not None else {}),
                                             **({"running_costs": [c.to_json() for c in alg.running_costs]}
                                                if getattr(alg, "running_costs", None) else {})},
                                            default=_json_default)),
@@ -617,23 +627,29 @@ def solve(prob, alg: Optional[GRAPE] = None, engine=None):
         alg.optim_options.get("line_search") == "ladder"          # the ladder search probes several step lengths per launch
     eng = engine or make_engine(prob, alg, **({"max_batch": 4} if batched else {}))
     basis = getattr(alg, "basis", None)
+    bounds = getattr(alg, "bounds", None)
     params = None
     try:
         guess = np.asarray((prob.prob if isinstance(prob, EnsembleProblem) else prob).guess, float)
-        if basis is not None:
-            guess = _basis_start(eng, guess, basis, getattr(alg, "basis_offset", None))
+        if bounds is not None:                                 # the optimiser's variables are the raw pulse from here on
+            guess = bounds_start(guess, *bounds)
+            eng.set_bounds(*bounds)
         try:
+            if basis is not None:
+                guess = _basis_start(eng, guess, basis, getattr(alg, "basis_offset", None))
             if device_opt:
                 res = _device_lbfgs(eng, guess, alg.optim_options)
             else:
                 res = _lbfgs(lambda x: eng.eval(x), guess, alg.optim_options)
             res.minimum = float(res.minimum) + float(getattr(eng, "running_cost_constant", 0.0))
             pulse = res.minimizer
-            if basis is not None:                              # the physical pulse, from the kernel the evaluations used
+            if basis is not None or bounds is not None:        # the physical pulse, from the kernel the evaluations used
                 params, pulse = res.minimizer, eng.controls(res.minimizer)
         finally:
             if basis is not None and not own:                  # a caller's engine goes back as it came
                 eng.set_basis(None)
+            if bounds is not None and not own:
+                eng.set_bounds(None)
     finally:
         if own:
             eng.close()

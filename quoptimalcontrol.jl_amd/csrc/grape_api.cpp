@@ -198,6 +198,12 @@ struct grape_ctx {
     int basis_nb = 1;                          // bases: 1 (shared) or K (one per control)
     double *d_basis_phi = nullptr;             // (N, M, n_bases)
     double *d_basis_x0 = nullptr;              // (K, N), or null
+    // grape_set_bounds: the entry points take the raw pulse u (or theta) and the evaluation runs on the saturated one; the
+    // saturation rides on the expansion, its slope on the projection (basis.hip; without a basis: M = 0, two kernels of their
+    // own).  Kept where the basis is kept.
+    bool bounds_on = false;                    // some control has finite bounds
+    double *d_bounds = nullptr;                // [lo (K) | hi (K)]
+    double *d_slope = nullptr;                 // (K, N, max_batch): dx/du of the last expansion
     bool mf_publish = true;                    // GRAPE_MF_PUBLISH=0: reduce_rows_kernel's staged publication instead of per-workgroup host flags
     unsigned long long seq = 0;
     std::string kernel_log;                    // names of the kernels the last evaluation launched (grape_get_kernel_names)
@@ -415,6 +421,8 @@ static bool env_off(const char *name)
 static size_t KN(const grape_ctx *c) { return (size_t)c->cfg.n_controls * c->cfg.n_slices; }
 // length of the vector the entry points take and return the gradient of: K M with a basis in force (grape_set_basis), else K N
 static size_t KP(const grape_ctx *c) { return c->basis_M > 0 ? (size_t)c->cfg.n_controls * c->basis_M : KN(c); }
+// a pulse map is in force (a basis, bounds, or both): the evaluation runs between basis.hip's two kernels (eval_param_device)
+static bool pulse_map(const grape_ctx *c) { return c->basis_M > 0 || c->bounds_on; }
 
 static void free_all(grape_ctx *c)
 {
@@ -436,6 +444,7 @@ static void free_all(grape_ctx *c)
         if (c->d_gather) { (void)hipSetDevice(c->device); (void)hipFree(c->d_gather); }
         if (c->d_arrive) { (void)hipSetDevice(c->device); (void)hipFree(c->d_arrive); }
         if (c->d_basis_phi) { (void)hipSetDevice(c->device); (void)hipFree(c->d_basis_phi); (void)hipFree(c->d_basis_x0); }
+        if (c->d_bounds || c->d_slope) { (void)hipSetDevice(c->device); (void)hipFree(c->d_bounds); (void)hipFree(c->d_slope); }
         delete c;
         return;
     }
@@ -465,6 +474,7 @@ static void free_all(grape_ctx *c)
     (void)hipFree(c->d_pen_w);
     (void)hipFree(c->d_rc_R); (void)hipFree(c->d_rc_rho); (void)hipFree(c->d_rc_xs); (void)hipFree(c->d_rc_rows);
     (void)hipFree(c->d_basis_phi); (void)hipFree(c->d_basis_x0);
+    (void)hipFree(c->d_bounds); (void)hipFree(c->d_slope);
     (void)hipFree(c->d_fom_member); (void)hipFree(c->d_fom_rows);
     (void)hipFree(c->d_ha); (void)hipFree(c->d_ha_norm); (void)hipFree(c->d_gc); (void)hipFree(c->d_gcn);
     (void)hipFree(c->d_act_a); (void)hipFree(c->d_act_b); (void)hipFree(c->d_act_bf); (void)hipFree(c->d_act_g);
@@ -1267,6 +1277,47 @@ extern "C" int grape_set_basis(grape_ctx *c, int32_t n_params, int32_t n_bases, 
     return GRAPE_OK;
 }
 
+extern "C" int grape_set_bounds(grape_ctx *c, const double *lo, const double *hi)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_set_bounds: null context");
+    const int K = c->cfg.n_controls;
+    if (!lo != !hi) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_bounds: lo and hi must both be given, or both be null");
+    bool on = false;
+    for (int k = 0; lo && k < K; ++k) {
+        const bool free_k = lo[k] == -INFINITY && hi[k] == INFINITY;
+        if (!free_k && !(std::isfinite(lo[k]) && std::isfinite(hi[k]) && lo[k] < hi[k]))
+            return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_bounds: control " + std::to_string(k) + ": need finite lo < hi, or lo = -inf and hi = +inf");
+        on = on || !free_k;
+    }
+    grape_ctx *lead = c->is_group ? c->sub[0] : c;
+    HIP_TRY(c, hipSetDevice(lead->device));
+    if (lead->dev_pending) {                                 // (as grape_set_basis: the buffers may be in use)
+        HIP_TRY(c, hipEventSynchronize(lead->ev_dev));
+        lead->dev_pending = false;
+    }
+    HIP_TRY(c, hipStreamSynchronize(lead->stream));
+    if (on) {                                                // everything that can fail first: a failure leaves the previous bounds in force
+        double *d_b = nullptr, *d_s = c->d_slope;
+        std::vector<double> lh(2 * (size_t)K);
+        std::copy(lo, lo + K, lh.begin());
+        std::copy(hi, hi + K, lh.begin() + K);
+        hipError_t e = hipMalloc((void **)&d_b, sizeof(double) * 2 * K);
+        if (e == hipSuccess) e = hipMemcpy(d_b, lh.data(), sizeof(double) * 2 * K, hipMemcpyHostToDevice);
+        if (e == hipSuccess && !d_s) e = hipMalloc((void **)&d_s, sizeof(double) * KN(c) * (size_t)c->B);   // (first use; kept from then on)
+        if (e != hipSuccess) {
+            (void)hipFree(d_b);
+            (void)hipGetLastError();
+            return fail(c, e == hipErrorOutOfMemory ? GRAPE_ERR_ALLOC : GRAPE_ERR_HIP, std::string("grape_set_bounds: ") + hipGetErrorString(e));
+        }
+        (void)hipFree(c->d_bounds);
+        c->d_bounds = d_b;
+        c->d_slope = d_s;
+    }
+    c->bounds_on = on;
+    return GRAPE_OK;
+}
+
 // what launch_copy needs to run one of basis.hip's kernels in place of the copy
 static grape::BasisOp basis_op(const grape_ctx *c, bool project, int n_x)
 {
@@ -1279,6 +1330,12 @@ static grape::BasisOp basis_op(const grape_ctx *c, bool project, int n_x)
     op.M = c->basis_M;
     op.n_bases = c->basis_nb;
     op.n_x = n_x;
+    if (c->bounds_on) {
+        op.bounded = 1;
+        op.lo = c->d_bounds;
+        op.hi = c->d_bounds + c->cfg.n_controls;
+        op.slope = c->d_slope;
+    }
     return op;
 }
 
@@ -1287,7 +1344,7 @@ extern "C" int grape_get_controls(grape_ctx *c, const double *theta, double *x)
     DeviceGuard guard;
     if (!c) return GRAPE_ERR_INVALID_ARG;
     if (!theta || !x) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_get_controls: null argument");
-    if (c->basis_M <= 0) {                                   // no basis: the parameters ARE the controls
+    if (!pulse_map(c)) {                                     // no basis, no bounds: the parameters ARE the controls
         std::memmove(x, theta, sizeof(double) * KN(c));
         return GRAPE_OK;
     }
@@ -2273,7 +2330,7 @@ static bool tile_folds_reduce(const grape_ctx *c, int n_x)
 static bool eval_ends_in_reduce(const grape_ctx *c)
 {
     if (c->is_group || c->comm || c->ipc_ranks > 1) return false;
-    if (c->basis_M > 0) return false;                        // parameter mode ends in basis_project_kernel
+    if (pulse_map(c)) return false;                          // a pulse map ends in basis_project_kernel / bounds_slope_kernel
     return c->family == 0 ? true : !tile_folds_reduce(c, 1);
 }
 
@@ -2912,7 +2969,8 @@ static int eval_device_impl(grape_ctx *c, const double *d_x, double *d_fg, void 
     return GRAPE_OK;
 }
 
-// Parameter mode (grape_set_basis), every kind of context: theta (K, M, n_x; device memory, or mapped host memory of the
+// A pulse map in force (grape_set_basis: parameter mode; grape_set_bounds: the saturation fused into the same two kernels, or
+// with M = 0 its own two), every kind of context: theta (K, M, n_x; device memory, or mapped host memory of the
 // blocking entry points) -> basis_expand_kernel -> the first device's d_x -> the evaluation exactly as the device-pointer entry
 // points run it (groups fan x out, communicators / mailboxes exchange; the penalties are added by the final reduction) ->
 // the complete summed rows in the first device's d_fg -> basis_project_kernel -> `out`, n_x blocks of K M + 1 (device, or
@@ -2951,7 +3009,7 @@ extern "C" int grape_eval_device(grape_ctx *c, const double *d_x, double *d_fg, 
     if (!c) return GRAPE_ERR_INVALID_ARG;
     if (!d_x || !d_fg) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_device: null argument");
     if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, "grape_eval_device: operators not set");
-    if (c->basis_M > 0) return eval_param_device(c, d_x, d_fg, (hipStream_t)stream, 1);
+    if (pulse_map(c)) return eval_param_device(c, d_x, d_fg, (hipStream_t)stream, 1);
     return eval_device_impl(c, d_x, d_fg, stream, 1);
 }
 
@@ -3004,8 +3062,8 @@ static int eval_host(grape_ctx *c, int n_x, const double *x, double *F, double *
     grape_ctx *lead = c->is_group ? c->sub[0] : c;
     int rc = ipc_check(c);
     if (rc) return rc;
-    if (c->basis_M > 0) {
-        // parameter mode: theta is staged in mapped host memory, where the expansion kernel reads it (the expansion is the
+    if (pulse_map(c)) {
+        // parameter mode / bounds: theta (u) is staged in mapped host memory, where the expansion kernel reads it (the expansion is the
         // upload); the projection kernel writes [G_theta, F] to the mapped host buffer and publishes -- one host flag, as ever
         const size_t kp = KP(c), Qp = kp + 1;
         HIP_TRY(c, hipSetDevice(lead->device));
@@ -3188,7 +3246,7 @@ extern "C" int grape_eval_batch_device(grape_ctx *c, int32_t n_x, const double *
     if (n_x < 1 || n_x > c->B)
         return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_batch_device: n_x must be in 1..grape_config.max_batch");
     if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, "grape_eval_batch_device: operators not set");
-    if (c->basis_M > 0) return eval_param_device(c, d_x, d_fg, (hipStream_t)stream, n_x);
+    if (pulse_map(c)) return eval_param_device(c, d_x, d_fg, (hipStream_t)stream, n_x);
     return eval_device_impl(c, d_x, d_fg, stream, n_x);
 }
 
@@ -3210,8 +3268,8 @@ static int fom_issue(grape_ctx *c, const double *x, int n_x)
         HIP_TRY(c, hipMalloc((void **)&c->d_fom_member, sizeof(double) * (size_t)c->cfg.n_ensemble * c->B));
         HIP_TRY(c, hipMalloc((void **)&c->d_fom_rows, sizeof(double) * (size_t)c->NB * c->B));
     }
-    const bool param = c->basis_M > 0;
-    if (param)                                               // theta: the expansion kernel reads it from the mapped staging buffer
+    const bool param = pulse_map(c);
+    if (param)                                               // theta / u: the expansion kernel reads it from the mapped staging buffer
         std::memcpy(c->h_stage, x, sizeof(double) * KP(c) * n_x);
     else
         shard_stage_x(c, x, n_x);
@@ -3391,7 +3449,7 @@ struct LbfgsRun {
     {
         evals += n_x;
         // (groups: fan-out of x, every shard, the grouped all-reduce / peer sum; communicators: the exchange behind the sweep)
-        if (c->basis_M > 0) return eval_param_device(c, st.xt, st.fgt, lead->stream, n_x);   // trial points are theta
+        if (pulse_map(c)) return eval_param_device(c, st.xt, st.fgt, lead->stream, n_x);   // trial points are theta / u
         return eval_device_impl(c, st.xt, st.fgt, lead->stream, n_x);
     }
     // trial slot 0: evaluate, publish phi, phi' (and phi'(0)) behind it -- nothing is waited for

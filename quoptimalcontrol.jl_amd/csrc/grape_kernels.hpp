@@ -37,11 +37,20 @@ constexpr double kTheta8 = 0.08;
 //   expand:  dst (K, N, n_x) = x0 + sum_m src[c, m, b] phi_b[t, m], m ascending, one FMA per term (basis_expand_kernel)
 //   project: dst n_x blocks of K M + 1 = { sum_t src[c, t, b] phi_b[t, m] (lane stride 64 in t, then a fixed butterfly), F }
 //            from n_x blocks of K N + 1 (basis_project_kernel: one wave per output); it publishes like copy_kernel
+//
+// grape_set_bounds rides on the same seam (bounded != 0): the expansion ends in the smooth saturation
+//   x = mid_c + half_c tanh((acc - mid_c) / half_c),  slope[c, t, b] = 1 - tanh^2(...)      (mid = (lo+hi)/2, half = (hi-lo)/2;
+//   a control with lo = -inf, hi = +inf keeps x = acc, slope = 1)
+// and the projection multiplies every gradient entry by its slope in front of the sum.  M = 0 is the identity expansion
+// (no basis in force: acc = src, bounds_saturate_kernel; dst rows = src rows x slope, bounds_slope_kernel).
 struct BasisOp {
     int32_t project = 0;                       // 0: expand, 1: project
     const double *phi = nullptr;               // device (N, M, n_bases) column-major
     const double *x0 = nullptr;                // device (K, N), nullable
     int32_t K = 0, N = 0, M = 0, n_bases = 1, n_x = 1;
+    int32_t bounded = 0;                       // 1: grape_set_bounds is in force
+    const double *lo = nullptr, *hi = nullptr; // device (K) each
+    double *slope = nullptr;                   // device (K, N, n_x): written by the expansion, read by the projection
 };
 // optional host-visible completion signal of an evaluation's FINAL kernel (reduce.hip: signal_done);
 // flag == nullptr: none (device-pointer entry points, intermediate kernels)

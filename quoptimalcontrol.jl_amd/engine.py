@@ -37,7 +37,7 @@ STATUS = {0: "GRAPE_OK", -1: "GRAPE_ERR_INVALID_ARG", -2: "GRAPE_ERR_UNSUPPORTED
 # every symbol include/grape_hip.h declares
 EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_operators", "grape_set_penalties",
            "grape_set_running_cost",
-           "grape_set_basis", "grape_get_controls",
+           "grape_set_basis", "grape_get_controls", "grape_set_bounds",
            "grape_comm_unique_id", "grape_comm_attach", "grape_ipc_export", "grape_ipc_attach",
            "grape_eval", "grape_eval_device", "grape_eval_batch", "grape_eval_batch_device", "grape_eval_fom", "grape_lbfgs", "grape_lbfgs_get_trace",
            "grape_get_member_results", "grape_get_trajectory",
@@ -126,6 +126,7 @@ def load_library():
     L.grape_set_running_cost.argtypes = [vp, i32, vp, vp]
     L.grape_set_basis.argtypes = [vp, i32, i32, vp, vp]
     L.grape_get_controls.argtypes = [vp, vp, vp]
+    L.grape_set_bounds.argtypes = [vp, vp, vp]
     L.grape_comm_unique_id.argtypes = [C.POINTER(GrapeCommId)]
     L.grape_comm_attach.argtypes = [vp, C.POINTER(GrapeCommId), i32, i32]
     L.grape_ipc_export.argtypes = [vp, i32, vp]
@@ -170,6 +171,7 @@ class GrapeEngine:
     eval(x) -> (F, G) with x, G of shape (K, N) (x[j, i] as in the reference)."""
 
     n_params = 0                               # M of set_basis (parameter mode); 0: slice mode
+    bounds = None                              # (lo, hi) of set_bounds while some control is bounded
 
     def __init__(self, sys_type, A, B, Xi, Xt, wts, T, n_slices, variant=0, device=-1, flags=0,
                  slices_per_lane=0, waves_per_member=0, expm_squarings=-1, member_results=False, max_batch=1,
@@ -303,6 +305,20 @@ class GrapeEngine:
         self._check(self._lib.grape_set_basis(self._h, M, nb, _p(pf), _p(xf)))
         self.n_params = M
 
+    def set_bounds(self, lo, hi=None):
+        """grape_set_bounds: smooth amplitude bounds.  lo, hi: scalars (every control) or length-K vectors with finite
+        lo < hi, or lo = -inf with hi = +inf for a control that stays free.  From now on eval, eval_batch, fom, lbfgs and
+        the device-pointer forms take the RAW pulse u (theta with a basis) and evaluate the physical pulse
+        x = mid + half tanh((u - mid) / half), which lies strictly inside (lo, hi); the returned gradient is that with
+        respect to u (theta), F that of the physical pulse, penalties and running costs evaluated on it.  controls(u)
+        returns the physical pulse.  The gradient vanishes where the pulse saturates: start inside (bounds.bounds_start).
+        set_bounds(None) switches the bounds off; bounds that leave every control free do the same.  A refused call
+        (ValueError here, GrapeError from the library) leaves the previous bounds in force."""
+        from .bounds import bounds_vectors
+        lo, hi = bounds_vectors(lo, hi, self.K)
+        self._check(self._lib.grape_set_bounds(self._h, _p(lo), _p(hi)))
+        self.bounds = None if lo is None or not np.isfinite(lo).any() else (lo, hi)
+
     @property
     def _cols(self):
         """second dimension of the arrays the evaluation calls take and return: M in parameter mode, else N"""
@@ -310,7 +326,7 @@ class GrapeEngine:
 
     def controls(self, theta):
         """grape_get_controls: the physical pulse (K, N) of a parameter array (K, M), expanded on the device by the
-        kernel the evaluations use.  Without a basis the parameters are the pulse."""
+        kernel the evaluations use.  Without a basis the parameters are the pulse -- saturated, if set_bounds is in force."""
         theta = np.asarray(theta, dtype=np.float64)
         if theta.shape != (self.K, self._cols):
             raise ValueError(f"theta must be ({self.K},{self._cols})")
