@@ -443,6 +443,44 @@ int grape_eval_batch_device(grape_ctx *ctx, int32_t n_x, const double *d_x, doub
  * of a member combine in a tree fixed by the decomposition, the member sum has a fixed order. */
 int grape_eval_fom(grape_ctx *ctx, int32_t n_x, const double *x, double *F, double *member_F);
 
+/* ABI v8 (additive).  Expectation values along the trajectory and the final states of every member: what the reference names
+ * and leaves undone -- test_pulse, src/tools.jl:32-36 ("simulate the pulse again returning the output so you can check the
+ * gate is correct"; its body is `@show "not implemented"`), and visualise_expt_val / visualise_expt_vals,
+ * src/visualisation.jl:13-51 (real(tr(op * X_s)) for every slice; commented out).
+ *   y[s + (N+1) (j + n_obs k)] = tr(O_kj' X_{k,s}) ,  s = 0..N ,  X_{k,0} = Xi_k
+ *   UnitaryGate (n x m states, kets included):   X_{k,s+1} = P_{k,s} X_{k,s}
+ *   StateTransfer / CoherenceTransfer:           X_{k,s+1} = P_{k,s} X_{k,s} P_{k,s}'
+ *   x          host f64 (K,N): what grape_eval takes -- theta / u with grape_set_basis / grape_set_bounds in force; the
+ *              observables are those of the physical pulse
+ *   n_obs      0..16 probes (the matrix units of a 4 x 4 state, or the 16 Pauli strings of two qubits, in one call)
+ *   O          host c128, column-major: per_member = 0: (n, m, n_obs), shared by the members; per_member = 1:
+ *              (n, m, E, n_obs), the layout of R in grape_set_running_cost.  Needed when n_obs > 0
+ *   y          host c128 (N+1, n_obs, E), column-major; nullable
+ *   X_final    host c128 (n, m, E): X_{k,N}, test_pulse's output; nullable
+ *   F          host f64, nullable
+ * The call runs ONE evaluation of x, exactly the one grape_eval runs (same kernels, same flow): F is bit for bit grape_eval's
+ * F, penalties and running cost included.  Behind the sweep of every member block (and behind the running-cost kernels, if a
+ * running cost is set) observe_kernel reads the propagators that sweep stored, walks the states and stores the traces.  It is
+ * an evaluation in every other respect too: blocking, ordered behind an in-flight grape_eval_device like grape_eval;
+ * afterwards grape_get_member_results, grape_get_trajectory and grape_get_kernel_names refer to it (the names include
+ * observe_kernel).  y and X_final do not depend on penalties, running cost or ensemble weights.  Results are bitwise
+ * reproducible call to call, and a member-chunked context returns the unchunked context's bits.  A context that never calls
+ * this launches the kernels it always did; an eval -> observables -> eval sequence returns the first evaluation's [G, F] bit
+ * for bit.
+ * Served: kernel family 0 (n = 2, 3, 4), all three system types, both variants, Hermitian and non-Hermitian generators,
+ * any m under UnitaryGate, gradient = 0 and objective = 0, single-device contexts without communicator or mailbox --
+ * member-chunked contexts, max_batch > 1 (the call takes one array), GRAPE_FLAG_KEEP_COSTATES and forced slices_per_lane /
+ * waves_per_member included.
+ * Refused before anything runs, GRAPE_ERR_UNSUPPORTED with the reason in the message: n = 1 and n >= 5 ("dimension": those
+ * workspaces hold P_t in other layouts or not at all), gradient = exact, objective = c1, multi-device contexts, an attached
+ * communicator or mailbox.  GRAPE_ERR_INVALID_ARG: null x; y and X_final both NULL; n_obs outside 0..16; n_obs = 0 with a
+ * non-NULL y; n_obs > 0 with a NULL O; per_member other than 0 or 1; a non-finite entry of O ("not finite"; with n_obs > 0 O
+ * is read and checked even when y is NULL and the probes go unused).  The context's refusals are checked first.  Before
+ * grape_set_operators: GRAPE_ERR_NOT_READY.  After any refusal the context evaluates exactly as before.  Non-finite x
+ * propagates NaN. */
+int grape_eval_observables(grape_ctx *ctx, const double *x, int32_t n_obs, int32_t per_member, const double *O, double *y,
+                           double *X_final, double *F);
+
 /* Device-resident L-BFGS: stands in for
  *     Optim.optimize(Optim.only_fg!(topt), x0, Optim.LBFGS(), optim_options)       src/solve.jl:138, :244
  * with x, g, the (s, y) history and the line-search trial points kept on the GPU; per evaluation the host

@@ -87,6 +87,9 @@ mutable struct GrapeContext
     handle::Ptr{Cvoid}
     K::Int
     N::Int
+    E::Int                                 # members of the context: sizes the per-member outputs (observables)
+    n::Int
+    m::Int
     function GrapeContext(members::Vector{<:Problem}, wts::Vector{Float64}, alg)
         p1 = members[1]
         n = size(p1.A, 1)
@@ -101,7 +104,7 @@ mutable struct GrapeContext
         h = Ref{Ptr{Cvoid}}(C_NULL)
         rc = ccall((:grape_create, libgrape), Cint, (Ref{GrapeConfig}, Ref{Ptr{Cvoid}}), cfg, h)
         rc == 0 || error("grape_create: ", unsafe_string(ccall((:grape_last_error, libgrape), Cstring, (Ptr{Cvoid},), C_NULL)))
-        ctx = new(h[], K, N)
+        ctx = new(h[], K, N, E, n, m)
         finalizer(c -> ccall((:grape_destroy, libgrape), Cint, (Ptr{Cvoid},), c.handle), ctx)
         # pack what init_ensemble produced (src/tools.jl:42-53) into contiguous column-major arrays
         A  = Array{ComplexF64}(undef, n, n, E)
@@ -219,6 +222,29 @@ function grape_fom(ctx::GrapeContext, x::Matrix{Float64})
     GC.@preserve x check(ctx, ccall((:grape_eval_fom, libgrape), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ref{Float64}, Ptr{Float64}),
                                     ctx.handle, Int32(1), x, F, C_NULL))
     F[]
+end
+
+# grape_eval_observables: one evaluation of x and, behind it, the expectation values along the trajectory -- what test_pulse
+# (src/tools.jl:32-36) and visualise_expt_vals (src/visualisation.jl:13-51) name:
+#   y[s+1, j, k] = tr(O_kj' X_{k,s}),  s = 0..N,  X_{k,0} = Xi_k;   real.(y[:, j, k]) is what visualise_expt_vals plots
+# O (n, m, n_obs): probes shared by the members; O (n, m, E, n_obs): one set per member -- Julia's column-major arrays are the
+# layout the library reads; n_obs <= 16.  The library writes every member of the context: y and X_final are sized from the
+# context's own E, n, m, and an O of another shape is rejected before the call.  Returns (y (N+1, n_obs, E), X_final (n, m, E), F)
+# with F bit for bit fom_and_gradient!'s.  n = 2..4, single-device contexts.  (Written, NOT executed: no Julia toolchain where
+# this file was written; the Python binding makes the same call and is tested on the GPU.)
+function observables(ctx::GrapeContext, x::Matrix{Float64}, O::Array{ComplexF64})
+    size(x) == (ctx.K, ctx.N) || throw(DimensionMismatch("x must be (n_controls, n_slices)"))
+    n_obs = size(O, ndims(O))
+    (ndims(O) == 3 && size(O) == (ctx.n, ctx.m, n_obs)) || (ndims(O) == 4 && size(O) == (ctx.n, ctx.m, ctx.E, n_obs)) ||
+        throw(DimensionMismatch("O must be (n, m, n_obs) or (n, m, E, n_obs) with the context's n, m and E"))
+    1 <= n_obs <= 16 || throw(ArgumentError("observables: 1 to 16 probes"))
+    y = Array{ComplexF64}(undef, ctx.N + 1, n_obs, ctx.E)
+    Xf = Array{ComplexF64}(undef, ctx.n, ctx.m, ctx.E)
+    F = Ref{Float64}(NaN)
+    GC.@preserve x O y Xf check(ctx, ccall((:grape_eval_observables, libgrape), Cint,
+                                           (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Ref{Float64}),
+                                           ctx.handle, x, Int32(n_obs), Int32(ndims(O) == 4 ? 1 : 0), O, y, Xf, F))
+    y, Xf, F[]
 end
 
 "The kernels the last evaluation launched, in launch order (grape_get_kernel_names, ABI v4)."

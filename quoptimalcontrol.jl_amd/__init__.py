@@ -12,10 +12,12 @@ from .engine import GrapeEngine, GrapeError, library_path, load_library  # noqa:
 from .api import (  # noqa: F401
     ADGRAPE, GRAPE, dCRAB, dcrab_pulse, fourier_basis, CoherenceTransfer, EnsembleProblem, EnsembleSolutionResult, Problem, SolutionResult,
     StateTransfer, UnitaryGate, C1, C3, C4, C5, C6, C7, ForbiddenStates, EvolutionTime, PenaltyFunctionals, init_ensemble, solve, fom_and_gradient, pulse_to_file, pulse_from_file, save, load,
+    test_pulse, expectation_values,
 )
 
 __all__ = [
     "workloads", "bounds", "GrapeEngine", "GrapeError", "library_path", "load_library", "GRAPE", "ADGRAPE", "dCRAB", "dcrab_pulse", "fourier_basis",
     "CoherenceTransfer", "EnsembleProblem", "EnsembleSolutionResult", "Problem", "SolutionResult",
     "StateTransfer", "UnitaryGate", "C1", "C3", "C4", "C5", "C6", "C7", "ForbiddenStates", "EvolutionTime", "PenaltyFunctionals", "init_ensemble", "solve", "fom_and_gradient", "pulse_to_file", "pulse_from_file", "save", "load",
+    "test_pulse", "expectation_values",
 ]

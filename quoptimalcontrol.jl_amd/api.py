@@ -424,6 +424,63 @@ def fom_and_gradient(prob, alg, x, engine=None):
             eng.close()
 
 
+def _observe_setup(prob, pulse_or_solres, engine):
+    """(engine, owned, pulse, weights) for the read-out functions: a plain engine of the problem (no penalties, basis, bounds or
+    running costs: the pulse is the physical one) unless the caller brings one, whose evaluations then take `pulse` as it is"""
+    if isinstance(pulse_or_solres, (SolutionResult, EnsembleSolutionResult)):
+        pulse, base = pulse_or_solres.opti_pulses, pulse_or_solres.alg
+    else:
+        pulse, base = pulse_or_solres, None
+    pulse = np.asarray(pulse, dtype=np.float64)
+    if pulse.ndim != 2:
+        raise ValueError("the pulse must be a (K, N) array")
+    wts = np.asarray(prob.wts, dtype=np.float64) if isinstance(prob, EnsembleProblem) else np.ones(1)
+    if engine is not None:
+        return engine, False, pulse, wts
+    alg = GRAPE(n_slices=pulse.shape[1], isinplace=getattr(base, "isinplace", True), device=getattr(base, "device", -1))
+    return make_engine(prob, alg), True, pulse, wts
+
+
+def test_pulse(prob, pulse_or_solres, engine=None):
+    """What src/tools.jl:32-36 names and leaves unimplemented: simulate the pulse again and return the output, so that the
+    gate can be checked.  prob: a Problem or an EnsembleProblem; pulse_or_solres: a (K, N) pulse or what solve() returned
+    (its opti_pulses).  Returns (X_final (E, n, m), member_F (E,), F): the final state of every member from the device
+    (grape_eval_observables), its figure of merit computed here from X_final and Xt with fom_func's formulas
+    (src/cost_functions.jl:99-111: Re z^2 for UnitaryGate, 1 - |z / n|^2 for the sandwich types, z = tr(Xt' X_final)) and
+    their weighted sum."""
+    eng, own, pulse, wts = _observe_setup(prob, pulse_or_solres, engine)
+    try:
+        _, Xf = eng.observe(pulse, None, final=True)
+    finally:
+        if own:
+            eng.close()
+    members = init_ensemble(prob) if isinstance(prob, EnsembleProblem) else [prob]
+    Xt = np.array([np.asarray(p.Xt, complex).reshape(Xf.shape[1:]) for p in members])
+    z = np.einsum("kab,kab->k", Xt.conj(), Xf)
+    if isinstance(members[0].sys_type, UnitaryGate):
+        member_F = np.real(z * z)
+    else:
+        member_F = 1.0 - np.abs(z / Xf.shape[1]) ** 2
+    return Xf, member_F, float(wts @ member_F)
+
+
+test_pulse.__test__ = False                    # (a library function, not a test: keep pytest from collecting it)
+
+
+def expectation_values(prob, pulse, ops, engine=None):
+    """What src/visualisation.jl:13-51 computes (commented out there): the expectation values of `ops` along the pulse.
+    ops: (n_obs, n, m) matrices (or one (n, m) matrix), at most 16.  Returns (times (N+1,), y (E, n_obs, N+1)) with
+    y[k, j, s] = tr(ops[j]' X_ks) from the device; y.real is what visualise_expt_vals plots against the times."""
+    eng, own, pulse, _ = _observe_setup(prob, pulse, engine)
+    try:
+        y = eng.observe(pulse, ops)
+        times = np.linspace(0.0, eng.T, eng.N + 1)
+    finally:
+        if own:
+            eng.close()
+    return times, y
+
+
 def _json_default(v):
     """Values `json` does not know inside alg.optim_options: NumPy scalars / arrays become numbers / lists, anything else
     (callables, objects) its repr -- a solve that succeeded must stay savable (the reference's BSON takes any value)."""

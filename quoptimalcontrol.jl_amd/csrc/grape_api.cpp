@@ -191,6 +191,16 @@ struct grape_ctx {
     double2 *d_rc_xs = nullptr;                // general flow: the states behind every slice (allocated by the first evaluation that needs it)
     double *d_rc_rows = nullptr;               // one row of K N + 1 per (control array, member) of a workspace block
     size_t rc_xs_bytes = 0, rc_rows_bytes = 0;
+    // grape_eval_observables (observe.hip): behind the sweep (and the running-cost kernels) of every member block of ONE
+    // evaluation, observe_kernel reads the stored propagators and writes tr(O_kj' X_ks) and X_N.  obs_on is set by the entry
+    // point around that evaluation only; the buffers are allocated by the first call that needs them and only ever grow.
+    bool obs_on = false;
+    int obs_n = 0, obs_per_member = 0;
+    bool obs_want_y = false, obs_want_xf = false;
+    double2 *d_obs_O = nullptr;                // the probes of the call
+    double2 *d_obs_y = nullptr;                // (N + 1, n_obs, E)
+    double2 *d_obs_xf = nullptr;               // (n, m, E)
+    size_t obs_O_bytes = 0, obs_y_bytes = 0, obs_xf_bytes = 0;
     // grape_set_basis ("parameter mode"): the entry points take theta (K, M) and return G_theta; basis_expand_kernel writes the
     // physical controls into d_x in front of the evaluation, basis_project_kernel folds the complete summed rows in d_fg behind
     // it (basis.hip).  Kept by the context the caller holds (a group: device buffers on its first device); shards never see it.
@@ -473,6 +483,7 @@ static void free_all(grape_ctx *c)
     (void)hipFree(c->d_x_bar);
     (void)hipFree(c->d_pen_w);
     (void)hipFree(c->d_rc_R); (void)hipFree(c->d_rc_rho); (void)hipFree(c->d_rc_xs); (void)hipFree(c->d_rc_rows);
+    (void)hipFree(c->d_obs_O); (void)hipFree(c->d_obs_y); (void)hipFree(c->d_obs_xf);
     (void)hipFree(c->d_basis_phi); (void)hipFree(c->d_basis_x0);
     (void)hipFree(c->d_bounds); (void)hipFree(c->d_slope);
     (void)hipFree(c->d_fom_member); (void)hipFree(c->d_fom_rows);
@@ -2481,6 +2492,23 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
                 else
                     HIP_TRY(c, grape::launch_sweep_small(c->cfg.n, 0, mode, r, stream));
             }
+            if (c->obs_on) {                                 // grape_eval_observables: the read-out of these members
+                SweepParams o = q;
+                o.obs_only = 1;
+                o.obs_n = c->obs_want_y ? c->obs_n : 0;
+                o.obs_m = c->m;
+                o.obs_per_member = c->obs_per_member;
+                o.obs_CH = c->CH;
+                o.obs_Etot = c->cfg.n_ensemble;
+                o.obs_E0 = lo;
+                o.obs_O = c->d_obs_O;
+                o.obs_y = c->obs_want_y ? c->d_obs_y : nullptr;
+                o.obs_xf = c->obs_want_xf ? c->d_obs_xf : nullptr;
+                if (c->pair)
+                    HIP_TRY(c, grape::launch_sweep_pair(c->cfg.n, c->cfg.sys_type != GRAPE_UNITARY_GATE, mode, o, stream));
+                else
+                    HIP_TRY(c, grape::launch_sweep_small(c->cfg.n, c->cfg.sys_type != GRAPE_UNITARY_GATE, mode, o, stream));
+            }
             if (exact) {                                     // exact gradient + objective from the stored trajectory
                 grape::ExactParams xq{};
                 xq.ops = q.ops;
@@ -3248,6 +3276,85 @@ extern "C" int grape_eval_batch_device(grape_ctx *c, int32_t n_x, const double *
     if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, "grape_eval_batch_device: operators not set");
     if (pulse_map(c)) return eval_param_device(c, d_x, d_fg, (hipStream_t)stream, n_x);
     return eval_device_impl(c, d_x, d_fg, stream, n_x);
+}
+
+// ---- grape_eval_observables: one evaluation + the read-out along its trajectory --------------------------------------------
+// grows one of the read-out's device buffers (never shrinks it); counted in grape_info.workspace_bytes
+template <class T>
+static int obs_grow(grape_ctx *c, T **buf, size_t *have, size_t want, const char *what)
+{
+    if (want <= *have) return GRAPE_OK;
+    (void)hipFree(*buf);
+    *buf = nullptr;
+    c->bytes -= *have;
+    *have = 0;
+    if (hipMalloc((void **)buf, want) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, GRAPE_ERR_ALLOC, std::string("grape_eval_observables: no device memory for ") + what);
+    }
+    *have = want;
+    c->bytes += want;
+    return GRAPE_OK;
+}
+
+extern "C" int grape_eval_observables(grape_ctx *c, const double *x, int32_t n_obs, int32_t per_member, const double *O,
+                                      double *y, double *X_final, double *F)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_observables: null context");
+    // what the context cannot serve first, as the header lists it; then the arguments
+    const char *why = nullptr;
+    const char *why_comm = "contexts with an attached communicator or mailbox exchange are not served";
+    if (c->is_group)                                         // (one shard: GRAPE_FLAG_FORCE_COLLECTIVE, a communicator of one rank)
+        why = c->sub.size() >= 2 ? "multi-device contexts are not served" : why_comm;
+    else if (c->comm || c->ipc_ranks > 1) why = why_comm;
+    else if (c->family != 0) why = "the operator dimension must be 2, 3 or 4 (the sweeps that leave every propagator in the workspace)";
+    else if (c->cfg.objective != GRAPE_OBJECTIVE_FOM) why = "objective = c1 is not served";
+    else if (c->cfg.gradient == GRAPE_GRADIENT_EXACT) why = "gradient = exact is not served";
+    if (why) return fail(c, GRAPE_ERR_UNSUPPORTED, std::string("grape_eval_observables: ") + why);
+    if (!x) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_observables: x is null");
+    if (!y && !X_final) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_observables: y and X_final are both null");
+    if (n_obs < 0 || n_obs > 16)
+        return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_observables: n_obs = " + std::to_string(n_obs) + " (must be in 0..16)");
+    if (n_obs == 0 && y) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_observables: n_obs = 0 with a non-null y");
+    if (n_obs > 0 && !O) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_observables: n_obs > 0 with a null O");
+    if (per_member != 0 && per_member != 1)
+        return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_observables: per_member = " + std::to_string(per_member) + " (must be 0 or 1)");
+    if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, "grape_eval_observables: operators not set");
+    const size_t n = (size_t)c->cfg.n, m = (size_t)c->m, E = (size_t)c->cfg.n_ensemble, N = (size_t)c->cfg.n_slices;
+    const size_t n_O = n * m * (per_member ? E : 1) * (size_t)n_obs;
+    for (size_t i = 0; i < 2 * n_O; ++i)
+        if (!std::isfinite(O[i]))
+            return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_observables: O[" + std::to_string(i / 2) + "] is not finite");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const bool want_y = y != nullptr && n_obs > 0;
+    int rc = GRAPE_OK;
+    if (want_y) {
+        rc = obs_grow(c, &c->d_obs_O, &c->obs_O_bytes, sizeof(double2) * n_O, "the probes");
+        if (rc) return rc;
+        rc = obs_grow(c, &c->d_obs_y, &c->obs_y_bytes, sizeof(double2) * (N + 1) * (size_t)n_obs * E, "the expectation values");
+        if (rc) return rc;
+        // (the buffer belongs to this entry point alone, which is blocking: no launch in flight reads it)
+        HIP_TRY(c, hipMemcpy(c->d_obs_O, O, sizeof(double2) * n_O, hipMemcpyHostToDevice));
+    }
+    if (X_final) {
+        rc = obs_grow(c, &c->d_obs_xf, &c->obs_xf_bytes, sizeof(double2) * n * m * E, "the final states");
+        if (rc) return rc;
+    }
+    c->obs_n = n_obs;
+    c->obs_per_member = per_member;
+    c->obs_want_y = want_y;
+    c->obs_want_xf = X_final != nullptr;
+    c->obs_on = true;                                        // enqueue_eval's member blocks end in observe_kernel
+    rc = eval_host(c, 1, x, F, nullptr, "grape_eval_observables");
+    c->obs_on = false;
+    if (rc) return rc;
+    // F is published by the evaluation's own last kernel (or by the sweep itself); the read-out's last launch may sit behind it
+    rc = wait_stream(c, c->stream);
+    if (rc) return rc;
+    if (want_y) HIP_TRY(c, hipMemcpy(y, c->d_obs_y, sizeof(double2) * (N + 1) * (size_t)n_obs * E, hipMemcpyDeviceToHost));
+    if (X_final) HIP_TRY(c, hipMemcpy(X_final, c->d_obs_xf, sizeof(double2) * n * m * E, hipMemcpyDeviceToHost));
+    return GRAPE_OK;
 }
 
 // ---- ABI v8: the figure of merit without the gradient ----------------------------------------------------------------------

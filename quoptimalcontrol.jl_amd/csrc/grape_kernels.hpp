@@ -151,7 +151,22 @@ struct SweepParams {
     const double *rc_rho;    // (N, rc_terms): entry [s - 1, j] weights the state after s slices
     double2 *rc_xs;          // general flow: X_{t+1} per slice, chunk-major like props with n m elements per slice
     double *rc_rows;         // (K N + 1) per (control array, member) of this launch: w_k [dJ_k/dx, J_k]
+    // grape_eval_observables (observe.hip): launch_sweep_small / launch_sweep_pair hand a launch with obs_only set to
+    // observe_kernel INSTEAD of the sweep: behind the sweep of the same members (one control array) it reads the propagators
+    // that sweep stored (props, chunk-major with stride obs_CH), walks the states X_s and stores tr(O_kj' X_ks) and X_N
+    int32_t obs_only;
+    int32_t obs_n;           // probes per member, 0..16 (0: only X_N is wanted)
+    int32_t obs_m;           // state columns m (O, X are n x m; the sandwich types: m = n)
+    int32_t obs_per_member;  // 0: obs_O is (n, m, obs_n), shared; 1: (n, m, obs_Etot, obs_n)
+    int32_t obs_CH;          // time chunks per member = workspace stride (LT, or LT / 2 behind the pair kernel)
+    int32_t obs_Etot;        // members of the whole ensemble
+    int32_t obs_E0;          // this launch's first member: offset into the probes and the outputs
+    const double2 *obs_O;    // the probes, column-major (from member 0 on)
+    double2 *obs_y;          // (N + 1, obs_n, obs_Etot) column-major, nullable
+    double2 *obs_xf;         // (n, m, obs_Etot) X_N, nullable
 };
+// observe.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::obs_only) only
+hipError_t run_observe(int n, int sandwich, const SweepParams &p, hipStream_t stream);
 // running_cost.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::rc_only) only
 hipError_t run_running_cost(int n, const SweepParams &p, hipStream_t stream);
 // fom_small.hip; reached through launch_sweep_small (pair = false) / launch_sweep_pair (pair = true) only

@@ -1,0 +1,207 @@
+// observe.hip -- expectation values along the trajectory (grape_eval_observables; what the reference names and leaves
+// undone: test_pulse, src/tools.jl:32-36, and visualise_expt_val(s), src/visualisation.jl:13-51) for the small-n family
+// (n = 2, 3, 4) on gfx950.
+//
+//   y[s, j, k] = tr(O_kj' X_{k,s}) ,  s = 0..N ,  X_{k,0} = Xi_k
+//   UnitaryGate (n x m states, kets included):  X_{s+1} = P_s X_s          StateTransfer / CoherenceTransfer:  X_{s+1} = P_s X_s P_s'
+//
+// It runs behind the sweep of the same launch (and behind the running-cost kernels, if any) and reads the propagators P_t
+// that sweep left in the workspace (chunk-major: element e of slice t = c S + jj of member k at ((k S + jj) n^2 + e) CH + c).
+// The decomposition is running_cost_kernel's: one workgroup per member of the launch, one lane per time chunk of S
+// consecutive slices, so every workspace access is lane-contiguous:
+//   1  chunk product Q_c = P_hi-1 ... P_lo
+//   2  exclusive prefix scan of the Q_c over lanes (wave shuffles in a fixed tree, wave totals through LDS, combined in wave
+//      order): U_start, the cumulative propagator at the chunk start
+//   3  X = U_start Xi [U_start'], then the walk X <- P_t X [P_t'] over the chunk (P read a second time)
+//   4  behind every slice the n_obs traces, one probe at a time (the probes are wave-uniform: scalar loads), stored to y
+//   5  lane 0 also stores the s = 0 entry, the lane that owns slice N - 1 stores X_N
+// Ragged decompositions: a lane whose chunk starts at or behind N, and the padding lanes behind chunk CH - 1, own no slice
+// (Q = 1, nothing stored); the last chunk may be short.  Plain vector stores, no atomics; every number has one fixed
+// evaluation order, so results are bitwise reproducible and a member-chunked launch gives the bits of an unchunked one.
+#include "cmat.hpp"
+#include "grape_kernels.hpp"
+#include "rc_mat.hpp"
+
+namespace grape {
+
+// C = X P^H  (the right half of the sandwich; all n x n)
+template <int N>
+GRAPE_DEV void rmul_x_ph(CRect<N, N> &c, const CRect<N, N> &x, const CMat<N> &p)
+{
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            double sr = 0.0, si = 0.0;
+#pragma unroll
+            for (int k = 0; k < N; ++k) {
+                const double ar = x.re[i + k * N], ai = x.im[i + k * N];
+                const double br = p.re[j + k * N], bi = -p.im[j + k * N];
+                sr = fma(ar, br, sr);
+                sr = fma(-ai, bi, sr);
+                si = fma(ar, bi, si);
+                si = fma(ai, br, si);
+            }
+            c.re[i + j * N] = sr;
+            c.im[i + j * N] = si;
+        }
+}
+
+// X <- U X (UnitaryGate) or U X U' (sandwich; M == N)
+template <int N, int M, bool SAND>
+GRAPE_DEV void obs_apply(CRect<N, M> &X, const CMat<N> &U)
+{
+    CRect<N, M> Tm;
+    rmul(Tm, U, X);
+    if constexpr (SAND)
+        rmul_x_ph(X, Tm, U);
+    else
+        X = Tm;
+}
+
+// ops_all / o_all are separate `const __restrict__` arguments so that the wave-uniform operator and probe entries can be
+// fetched with scalar loads (as in sweep_small.hip and running_cost.hip)
+template <int N, int M, bool SAND, int MAXT>
+__global__ __launch_bounds__(MAXT) void observe_kernel(const double2 *__restrict__ ops_all, const double2 *__restrict__ o_all,
+                                                       const SweepParams p)
+{
+    static_assert(!SAND || M == N, "the sandwich acts on n x n states");
+    constexpr int NN = N * N, NM = N * M, MAXW = MAXT / 64;
+    __shared__ double2 s_q[MAXW][NN];              // wave totals of the prefix scan
+
+    const int CH = p.obs_CH, S = p.S, K = p.K, Nsl = p.N, n_obs = p.obs_n;
+    const int L = threadIdx.x, lane = L & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(L >> 6), W = blockDim.x >> 6;
+    const int k = blockIdx.x;                        // member within the launch: row of the workspace
+    const int kg = k + p.obs_E0;                     // member of the ensemble: row of the probes and of the outputs
+    // the lane's slices [lo, hi): none for chunks that start at or behind N and for the padding lanes behind chunk CH - 1
+    const int lo = (L < CH && L * S < Nsl) ? L * S : Nsl;
+    const int hi = min(lo + S, Nsl);
+    const int cnt = hi - lo;
+    const size_t stride = (size_t)CH;
+    const double2 *__restrict__ Pw = p.props + (size_t)k * S * NN * stride + L;
+    const double2 *__restrict__ opXi = ops_all + (size_t)k * (K + 3) * NN + (size_t)(1 + K) * NN;
+    // probe j of this member: shared (n, m, n_obs) or per member (n, m, Etot, n_obs)
+    const size_t o_step = p.obs_per_member ? (size_t)p.obs_Etot * NM : (size_t)NM;
+    const double2 *__restrict__ o_mem = o_all + (p.obs_per_member ? (size_t)kg * NM : (size_t)0);
+    double2 *__restrict__ yk = p.obs_y ? p.obs_y + (size_t)kg * n_obs * ((size_t)Nsl + 1) : nullptr;
+
+    // ---------------------------------------------------------------- 1: chunk product
+    CMat<N> P, T, oth;
+    {
+        CMat<N> Q;
+        set_identity(Q);
+        for (int jj = 0; jj < cnt; ++jj) {
+            rc_load_mat(P, Pw + (size_t)jj * NN * stride, stride);
+            mul(T, P, Q);
+            Q = T;
+        }
+        // ------------------------------------------------------------ 2: exclusive prefix over lanes -> U at the chunk start
+        CMat<N> inc = Q;
+        for (int d = 1; d < 64; d <<= 1) {
+            shfl_up(oth, inc, d);
+            if (lane >= d) {
+                mul(T, inc, oth);
+                inc = T;
+            }
+        }
+        shfl_up(oth, inc, 1);
+        if (lane == 0)
+            set_identity(oth);
+        if (W > 1) {
+            if (lane == 63) {
+#pragma unroll
+                for (int e = 0; e < NN; ++e)
+                    s_q[wave][e] = make_double2(inc.re[e], inc.im[e]);
+            }
+            __syncthreads();
+            CMat<N> pre;
+            set_identity(pre);
+            for (int w = 0; w < wave; ++w) {
+                rc_load_lds(inc, &s_q[w][0]);
+                mul(T, inc, pre);
+                pre = T;
+            }
+            mul(T, oth, pre);
+            oth = T;
+        }
+    }
+    // ---------------------------------------------------------------- 3: the state at the chunk start
+    CRect<N, M> X;
+    rload_uniform(X, opXi);                          // (the first m columns of the zero-padded n x n block)
+    obs_apply<N, M, SAND>(X, oth);
+
+    // the n_obs traces y_j = tr(O_j' X) of the state behind s slices, one probe at a time
+    auto emit = [&](int s) {
+        for (int j = 0; j < n_obs; ++j) {
+            const double2 *__restrict__ o = o_mem + (size_t)j * o_step;
+            double yr = 0.0, yi = 0.0;
+#pragma unroll
+            for (int e = 0; e < NM; ++e) {
+                const double2 v = o[e];
+                yr = fma(v.x, X.re[e], yr);
+                yr = fma(v.y, X.im[e], yr);
+                yi = fma(v.x, X.im[e], yi);
+                yi = fma(-v.y, X.re[e], yi);
+            }
+            yk[(size_t)s + (size_t)j * ((size_t)Nsl + 1)] = make_double2(yr, yi);
+        }
+    };
+    if (yk && L == 0)
+        emit(0);                                     // (U_start = 1: X is Xi)
+    // ---------------------------------------------------------------- 4: the walk
+    for (int jj = 0; jj < cnt; ++jj) {
+        rc_load_mat(P, Pw + (size_t)jj * NN * stride, stride);
+        obs_apply<N, M, SAND>(X, P);
+        if (yk)
+            emit(lo + jj + 1);
+    }
+    // ---------------------------------------------------------------- 5: X_N
+    if (p.obs_xf && cnt > 0 && hi == Nsl) {
+        double2 *__restrict__ xf = p.obs_xf + (size_t)kg * NM;
+#pragma unroll
+        for (int e = 0; e < NM; ++e)
+            xf[e] = make_double2(X.re[e], X.im[e]);
+    }
+}
+
+template <int N, int M, bool SAND>
+static hipError_t obs_launch_nm(const SweepParams &p, hipStream_t stream)
+{
+    constexpr int MAXT = RcTraits<N>::MAXT;
+    const int threads = (p.obs_CH + 63) & ~63;
+    if (threads > MAXT || p.obs_CH < 1 || (long long)p.S * p.obs_CH < p.N || p.N < 1 || p.E < 1 || p.obs_E0 < 0 ||
+        p.obs_E0 + p.E > p.obs_Etot || p.obs_n < 0 || p.obs_n > 16 || (!p.obs_y && !p.obs_xf) ||
+        (p.obs_y && p.obs_n > 0 && !p.obs_O) || !p.props || !p.ops)
+        return hipErrorInvalidConfiguration;
+    GRAPE_LAUNCH_AS("observe_kernel", (observe_kernel<N, M, SAND, MAXT>), dim3(p.E), dim3(threads), 0, stream, p.ops, p.obs_O, p);
+    return hipGetLastError();
+}
+
+hipError_t run_observe(int n, int sandwich, const SweepParams &p, hipStream_t stream)
+{
+    if (sandwich) {
+        if (p.obs_m != n)
+            return hipErrorInvalidValue;
+        switch (n) {
+        case 2: return obs_launch_nm<2, 2, true>(p, stream);
+        case 3: return obs_launch_nm<3, 3, true>(p, stream);
+        case 4: return obs_launch_nm<4, 4, true>(p, stream);
+        default: return hipErrorInvalidValue;
+        }
+    }
+    switch (n * 8 + p.obs_m) {
+    case 2 * 8 + 1: return obs_launch_nm<2, 1, false>(p, stream);
+    case 2 * 8 + 2: return obs_launch_nm<2, 2, false>(p, stream);
+    case 3 * 8 + 1: return obs_launch_nm<3, 1, false>(p, stream);
+    case 3 * 8 + 2: return obs_launch_nm<3, 2, false>(p, stream);
+    case 3 * 8 + 3: return obs_launch_nm<3, 3, false>(p, stream);
+    case 4 * 8 + 1: return obs_launch_nm<4, 1, false>(p, stream);
+    case 4 * 8 + 2: return obs_launch_nm<4, 2, false>(p, stream);
+    case 4 * 8 + 3: return obs_launch_nm<4, 3, false>(p, stream);
+    case 4 * 8 + 4: return obs_launch_nm<4, 4, false>(p, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace grape

@@ -26,156 +26,9 @@
 // order, so the ensemble sum that follows is the one it always was and results are bitwise reproducible.
 #include "cmat.hpp"
 #include "grape_kernels.hpp"
+#include "rc_mat.hpp"
 
 namespace grape {
-
-// n x m complex block (the states, costates and probe matrices), column-major e = i + j n
-template <int N, int M>
-struct CRect {
-    double re[N * M];
-    double im[N * M];
-};
-
-template <int N, int M>
-GRAPE_DEV void rzero(CRect<N, M> &a)
-{
-#pragma unroll
-    for (int e = 0; e < N * M; ++e) {
-        a.re[e] = 0.0;
-        a.im[e] = 0.0;
-    }
-}
-
-// C = A B  (A n x n, B n x m)
-template <int N, int M>
-GRAPE_DEV void rmul(CRect<N, M> &c, const CMat<N> &a, const CRect<N, M> &b)
-{
-#pragma unroll
-    for (int j = 0; j < M; ++j)
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            double sr = 0.0, si = 0.0;
-#pragma unroll
-            for (int k = 0; k < N; ++k) {
-                const double ar = a.re[i + k * N], ai = a.im[i + k * N];
-                const double br = b.re[k + j * N], bi = b.im[k + j * N];
-                sr = fma(ar, br, sr);
-                sr = fma(-ai, bi, sr);
-                si = fma(ar, bi, si);
-                si = fma(ai, br, si);
-            }
-            c.re[i + j * N] = sr;
-            c.im[i + j * N] = si;
-        }
-}
-
-// C = A^H B
-template <int N, int M>
-GRAPE_DEV void rmul_ah(CRect<N, M> &c, const CMat<N> &a, const CRect<N, M> &b)
-{
-#pragma unroll
-    for (int j = 0; j < M; ++j)
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            double sr = 0.0, si = 0.0;
-#pragma unroll
-            for (int k = 0; k < N; ++k) {
-                const double ar = a.re[k + i * N], ai = -a.im[k + i * N];
-                const double br = b.re[k + j * N], bi = b.im[k + j * N];
-                sr = fma(ar, br, sr);
-                sr = fma(-ai, bi, sr);
-                si = fma(ar, bi, si);
-                si = fma(ai, br, si);
-            }
-            c.re[i + j * N] = sr;
-            c.im[i + j * N] = si;
-        }
-}
-
-// C (n x n) = X Lam^H  (both n x m)
-template <int N, int M>
-GRAPE_DEV void rmul_a_bh(CMat<N> &c, const CRect<N, M> &a, const CRect<N, M> &b)
-{
-#pragma unroll
-    for (int j = 0; j < N; ++j)
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            double sr = 0.0, si = 0.0;
-#pragma unroll
-            for (int k = 0; k < M; ++k) {
-                const double ar = a.re[i + k * N], ai = a.im[i + k * N];
-                const double br = b.re[j + k * N], bi = -b.im[j + k * N];
-                sr = fma(ar, br, sr);
-                sr = fma(-ai, bi, sr);
-                si = fma(ar, bi, si);
-                si = fma(ai, br, si);
-            }
-            c.re[i + j * N] = sr;
-            c.im[i + j * N] = si;
-        }
-}
-
-template <int N, int M>
-GRAPE_DEV void rshfl_down(CRect<N, M> &dst, const CRect<N, M> &src, int delta)
-{
-#pragma unroll
-    for (int e = 0; e < N * M; ++e) {
-        dst.re[e] = __shfl_down(src.re[e], delta, 64);
-        dst.im[e] = __shfl_down(src.im[e], delta, 64);
-    }
-}
-
-template <int N, int M>
-GRAPE_DEV void rload_uniform(CRect<N, M> &m, const double2 *__restrict__ src)
-{
-#pragma unroll
-    for (int e = 0; e < N * M; ++e) {
-        const double2 v = src[e];
-        m.re[e] = v.x;
-        m.im[e] = v.y;
-    }
-}
-
-template <int N>
-GRAPE_DEV void rc_load_mat(CMat<N> &m, const double2 *__restrict__ base, size_t stride)
-{
-#pragma unroll
-    for (int e = 0; e < N * N; ++e) {
-        const double2 v = base[e * stride];
-        m.re[e] = v.x;
-        m.im[e] = v.y;
-    }
-}
-
-template <int N>
-GRAPE_DEV void rc_load_lds(CMat<N> &m, const double2 *src)
-{
-#pragma unroll
-    for (int e = 0; e < N * N; ++e) {
-        const double2 v = src[e];
-        m.re[e] = v.x;
-        m.im[e] = v.y;
-    }
-}
-
-template <int N, int M>
-GRAPE_DEV void rload_ws(CRect<N, M> &m, const double2 *__restrict__ base, size_t stride)
-{
-#pragma unroll
-    for (int e = 0; e < N * M; ++e) {
-        const double2 v = base[e * stride];
-        m.re[e] = v.x;
-        m.im[e] = v.y;
-    }
-}
-
-template <int N, int M>
-GRAPE_DEV void rstore_ws(double2 *__restrict__ base, size_t stride, const CRect<N, M> &m)
-{
-#pragma unroll
-    for (int e = 0; e < N * M; ++e)
-        base[e * stride] = make_double2(m.re[e], m.im[e]);
-}
 
 // ops_all / r_all / rho / wts_all are separate `const __restrict__` arguments so that the wave-uniform operator, probe and
 // weight entries can be fetched with scalar loads (as in sweep_small.hip).  UNI: every propagator is unitary.
@@ -417,12 +270,6 @@ __global__ __launch_bounds__(256) void running_cost_fold_kernel(const double *__
         acc += rows[((size_t)xi * E + m0 + m) * Q + q];
     block_out[(size_t)blockIdx.x * Q + q] = acc;
 }
-
-template <int N>
-struct RcTraits;
-template <> struct RcTraits<2> { static constexpr int MAXT = 1024; };
-template <> struct RcTraits<3> { static constexpr int MAXT = 512; };
-template <> struct RcTraits<4> { static constexpr int MAXT = 256; };
 
 template <int N, int M>
 static hipError_t rc_launch_nm(const SweepParams &p, hipStream_t stream)

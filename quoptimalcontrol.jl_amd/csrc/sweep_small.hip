@@ -619,6 +619,8 @@ hipError_t launch_sweep_small(int n, int sandwich, int mode, const SweepParams &
         return launch_fom_small(n, sandwich, mode, false, p, stream);
     if (p.rc_only)                                   // grape_set_running_cost: the kernels behind the sweep (running_cost.hip)
         return run_running_cost(n, p, stream);
+    if (p.obs_only)                                  // grape_eval_observables: the kernel behind the sweep (observe.hip)
+        return run_observe(n, sandwich, p, stream);
     switch (n * 2 + (sandwich ? 1 : 0)) {
     case 4: return launch_ns<2, 0>(mode, p, stream);
     case 5: return launch_ns<2, 1>(mode, p, stream);

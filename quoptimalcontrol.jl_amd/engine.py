@@ -39,7 +39,8 @@ EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_oper
            "grape_set_running_cost",
            "grape_set_basis", "grape_get_controls", "grape_set_bounds",
            "grape_comm_unique_id", "grape_comm_attach", "grape_ipc_export", "grape_ipc_attach",
-           "grape_eval", "grape_eval_device", "grape_eval_batch", "grape_eval_batch_device", "grape_eval_fom", "grape_lbfgs", "grape_lbfgs_get_trace",
+           "grape_eval", "grape_eval_device", "grape_eval_batch", "grape_eval_batch_device", "grape_eval_fom", "grape_eval_observables",
+           "grape_lbfgs", "grape_lbfgs_get_trace",
            "grape_get_member_results", "grape_get_trajectory",
            "grape_get_kernel_time", "grape_get_kernel_samples", "grape_get_kernel_names", "grape_get_group_timing", "grape_get_phase_stamps",
            "grape_get_info",
@@ -136,6 +137,7 @@ def load_library():
     L.grape_eval_batch.argtypes = [vp, i32, vp, vp, vp]
     L.grape_eval_batch_device.argtypes = [vp, i32, vp, vp, vp]
     L.grape_eval_fom.argtypes = [vp, i32, vp, vp, vp]
+    L.grape_eval_observables.argtypes = [vp, vp, i32, i32, vp, vp, vp, dp]
     L.grape_lbfgs.argtypes = [vp, vp, C.POINTER(GrapeLbfgsOptions), vp, C.POINTER(GrapeLbfgsResult)]
     L.grape_get_member_results.argtypes = [vp, vp, vp]
     L.grape_get_trajectory.argtypes = [vp, i32, vp, vp, vp]
@@ -503,6 +505,45 @@ class GrapeEngine:
         if single:
             return (float(F[0]), mF[0]) if members else float(F[0])
         return (F, mF) if members else F
+
+    def observe(self, x, ops, per_member=False, final=False, want_F=False):
+        """grape_eval_observables: one evaluation of x (K,N) (theta / u with a basis / bounds in force) and, behind it, the
+        expectation values y[k, j, s] = tr(O_kj' X_ks) of the probes along the trajectory, s = 0..N (X_k0 = Xi_k; the states
+        of the physical pulse).  ops: (n_obs, n, m) probes shared by the members -- or one (n, m) matrix -- and with
+        per_member=True (E, n_obs, n, m); at most 16 probes; None (with final=True) for the final states alone.
+        Returns y (E, n_obs, N+1) complex128 -- then X_final (E, n, m) with final=True -- then F, bit for bit eval(x)'s,
+        with want_F=True.  n = 2..4, single-device contexts (include/grape_hip.h)."""
+        x = np.asarray(x, dtype=np.float64)
+        if x.shape != (self.K, self._cols):
+            raise ValueError(f"x must be ({self.K},{self._cols})")
+        n, m, E, N = self.n, self.m, self.E, self.N
+        if ops is None:
+            if not final:
+                raise ValueError("observe: nothing asked for (ops=None needs final=True)")
+            n_obs, Of, y = 0, None, None
+        else:
+            O = np.asarray(ops, dtype=np.complex128)
+            if not per_member and O.ndim == 2:
+                O = O[None]
+            want = (E, O.shape[1] if O.ndim == 4 else 0, n, m) if per_member else (O.shape[0] if O.ndim == 3 else 0, n, m)
+            if O.shape != want or not 1 <= O.shape[-3] <= 16:
+                raise ValueError(f"observe: ops must be {'(E, n_obs, n, m)' if per_member else '(n_obs, n, m)'} with E = {E}, "
+                                 f"n = {n}, m = {m} and 1 <= n_obs <= 16")
+            n_obs = O.shape[-3]
+            # column-major (n, m, [E,] n_obs): the probe index slowest, then the member
+            Of = _cm(np.swapaxes(O, 0, 1) if per_member else O)
+            y = np.empty((E, n_obs, N + 1), np.complex128)
+        Xf = np.empty((E, m, n), np.complex128) if final else None
+        F = C.c_double()
+        xf = np.ascontiguousarray(x.T)
+        self._check(self._lib.grape_eval_observables(self._h, _p(xf), n_obs, 1 if per_member else 0, _p(Of), _p(y), _p(Xf),
+                                                     C.byref(F) if want_F else None))
+        out = [y]
+        if final:
+            out.append(np.ascontiguousarray(np.swapaxes(Xf, -1, -2)))
+        if want_F:
+            out.append(F.value)
+        return out[0] if len(out) == 1 else tuple(out)
 
     def eval_device(self, d_x_ptr, d_fg_ptr, stream=0):
         """grape_eval_device with raw device pointers (e.g. torch tensor .data_ptr())."""
