@@ -139,7 +139,7 @@ struct grape_ctx {
     double2 *d_vecs = nullptr;                 // thin: per member [v0 | wT], 16 complex each
     bool sparse_ctrl = false;                  // tile family: every B_c has <= kSparseMax non-zeros (sparse gradient traces)
     int sp_nz = 64;                            // list length of the sparse control lists (64 .. 256)
-    size_t sp_cap = 0;                         // entries behind d_sp_coef / d_sp_addr
+    size_t sp_coef_bytes = 0, sp_addr_bytes = 0;   // capacities of d_sp_coef / d_sp_addr
     double2 *d_sp_coef = nullptr;              // [E][K][sp_nz]
     int32_t *d_sp_addr = nullptr;
     int hoist = 0;                             // tile family, prop_hoist.hip kernels: 1 member-invariant controls (control sum formed once per slice), 2 per-member controls
@@ -160,7 +160,7 @@ struct grape_ctx {
     bool ctrl_shared = false;                  // the members' control operators are identical (memcmp)
     int32_t *d_any_sp_i = nullptr;             // size-generic family, sparse shared controls: [eptr | ectl | cptr | caddr]
     double2 *d_any_sp_c = nullptr;             //                                              [ecoef | ccoef]
-    size_t any_sp_i_cap = 0, any_sp_c_cap = 0, any_sp_nnz = 0, any_sp_ntouch = 0;   // capacities (elements); non-zeros of the current operators (0: dense), elements they touch
+    size_t any_sp_i_bytes = 0, any_sp_c_bytes = 0, any_sp_nnz = 0, any_sp_ntouch = 0;   // capacities (bytes); non-zeros of the current operators (0: dense), elements they touch
     bool ctrl_scaled = false;                  // B_{k,c} = s_k B_{0,c} with some s_k != 1 (d_ctrl_scale: s_k per member): the
     double *d_ctrl_scale = nullptr;            //   hoisted flows' pre-pass runs on member 0's operators, members scale Gc_t
     size_t act_var_bytes = 0;                  // device bytes of the vector flow's operator buffers (re-sized per upload)
@@ -289,6 +289,107 @@ static int fail(const grape_ctx *ctx, int code, const std::string &msg)
                         std::string(#call) + ": " + hipGetErrorString(e__));                   \
     } while (0)
 
+// seconds on the monotonic clock (timeouts, the group's phase timing, grape_lbfgs_result.seconds)
+static double now_s()
+{
+    timespec t;
+    clock_gettime(CLOCK_MONOTONIC, &t);
+    return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec;
+}
+
+// the context that holds the first device's buffers, stream and host flag: shard 0 of a group, else the context itself
+static const grape_ctx *lead_of(const grape_ctx *c) { return c->is_group ? c->sub[0] : c; }
+static grape_ctx *lead_of(grape_ctx *c) { return c->is_group ? c->sub[0] : c; }
+
+// Grows a device buffer to `want` bytes and keeps grape_info.workspace_bytes (c->bytes) honest.  *cap >= want: nothing
+// happens (buffers only ever grow; the contents are not kept).  Otherwise the buffer is freed and c->bytes loses its
+// capacity, and only an allocation that stands adds the new one: after a failure *ptr is null, *cap is 0, c->bytes holds
+// nothing of this buffer and the status is GRAPE_ERR_ALLOC, "<who>: no device memory for <what>".
+// (Not every device buffer is counted: the basis, the bounds, the running cost's R / rho and grape_eval_fom's rows never were.)
+template <class T>
+static int grow(grape_ctx *c, T **ptr, size_t *cap, size_t want, const char *who, const char *what)
+{
+    if (want <= *cap) return GRAPE_OK;
+    (void)hipFree(*ptr);
+    *ptr = nullptr;
+    c->bytes -= *cap;
+    *cap = 0;
+    if (hipMalloc((void **)ptr, want) != hipSuccess) {
+        (void)hipGetLastError();
+        *ptr = nullptr;
+        return fail(c, GRAPE_ERR_ALLOC, std::string(who) + ": no device memory for " + what);
+    }
+    *cap = want;
+    c->bytes += want;
+    return GRAPE_OK;
+}
+
+// Blocks the host until nothing issued for the device context `s` is in flight: the last grape_eval_device, which may
+// still run on a caller's stream (ev_dev), and the private stream.  Every setter calls it BEFORE it replaces or rewrites a
+// device buffer that an evaluation reads.  Errors are reported on `c` (the group, when `s` is its first shard).
+static int drain(grape_ctx *c, grape_ctx *s)
+{
+    HIP_TRY(c, hipSetDevice(s->device));
+    if (s->dev_pending) {
+        HIP_TRY(c, hipEventSynchronize(s->ev_dev));
+        s->dev_pending = false;
+    }
+    HIP_TRY(c, hipStreamSynchronize(s->stream));
+    return GRAPE_OK;
+}
+
+// Orders the private stream of `s` behind the last grape_eval_device (it reads and writes d_x / d_fg on a caller's stream):
+// a stream wait on ev_dev, the host does not block.  The device of `s` is current.
+static int order_behind_device_call(grape_ctx *c, grape_ctx *s)
+{
+    if (s->dev_pending) {
+        HIP_TRY(c, hipStreamWaitEvent(s->stream, s->ev_dev, 0));
+        s->dev_pending = false;
+    }
+    return GRAPE_OK;
+}
+
+// Device copies of a setter's host arrays, all or nothing: *d0 = b0 bytes of h0, and -- b1 > 0 -- *d1 = b1 bytes of h1 (h1
+// null: allocated, not filled).  New buffers first, so that a failure leaves the previous setting in force: the caller frees
+// the old ones and swaps only after GRAPE_OK.  On failure nothing stays allocated; the status is GRAPE_ERR_ALLOC for out of
+// memory, else GRAPE_ERR_HIP.
+static int device_copies(grape_ctx *c, const char *who, const void *h0, size_t b0, void **d0, const void *h1, size_t b1, void **d1)
+{
+    *d0 = *d1 = nullptr;
+    hipError_t e = hipMalloc(d0, b0);
+    if (e == hipSuccess) e = hipMemcpy(*d0, h0, b0, hipMemcpyHostToDevice);
+    if (e == hipSuccess && b1) e = hipMalloc(d1, b1);
+    if (e == hipSuccess && b1 && h1) e = hipMemcpy(*d1, h1, b1, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(*d0);
+        (void)hipFree(*d1);
+        *d0 = *d1 = nullptr;
+        (void)hipGetLastError();
+        return fail(c, e == hipErrorOutOfMemory ? GRAPE_ERR_ALLOC : GRAPE_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    return GRAPE_OK;
+}
+
+// GRAPE_ERR_INVALID_ARG "<who>: <name>[i / per] is not finite" for the first non-finite of v[0 .. count)
+// (per = 2: interleaved complex entries, reported by entry)
+static int check_finite(const grape_ctx *c, const double *v, size_t count, const char *who, const char *name, size_t per = 1)
+{
+    for (size_t i = 0; i < count; ++i)
+        if (!std::isfinite(v[i]))
+            return fail(c, GRAPE_ERR_INVALID_ARG, std::string(who) + ": " + name + "[" + std::to_string(i / per) + "] is not finite");
+    return GRAPE_OK;
+}
+
+// Why a context that spans devices or has an exchange attached is not served by the features that read one device's stored
+// propagators (grape_set_running_cost, grape_eval_observables); null: it is neither
+static const char *why_exchange_not_served(const grape_ctx *c)
+{
+    const char *why_comm = "contexts with an attached communicator or mailbox exchange are not served";
+    if (c->is_group)                                         // (one shard: GRAPE_FLAG_FORCE_COLLECTIVE, a communicator of one rank)
+        return c->sub.size() >= 2 ? "multi-device contexts are not served" : why_comm;
+    return c->comm || c->ipc_ranks > 1 ? why_comm : nullptr;
+}
+
 // ------------------------------------------------------------------------------------------
 // RCCL, loaded on demand (573 MB shared object: single-GPU users never touch it)
 struct RcclApi {
@@ -391,17 +492,16 @@ struct GroupWorker {
     {
         const uint64_t want = req.load(std::memory_order_relaxed);
         unsigned spins = 0;
-        timespec t0{0, 0};
+        double t0 = 0.0;
         while (done.load(std::memory_order_acquire) != want) {
 #if defined(__x86_64__)
             __builtin_ia32_pause();
 #endif
             if ((++spins & 0xffff) == 0) {
-                timespec t;
-                clock_gettime(CLOCK_MONOTONIC, &t);
-                if (!t0.tv_sec && !t0.tv_nsec)
+                const double t = now_s();
+                if (t0 == 0.0)
                     t0 = t;
-                else if ((double)(t.tv_sec - t0.tv_sec) + 1e-9 * (double)(t.tv_nsec - t0.tv_nsec) > timeout_s)
+                else if (t - t0 > timeout_s)
                     return GRAPE_ERR_TIMEOUT;
                 {                                             // belt and braces: a sleeping worker with work posted is woken again
                     std::lock_guard<std::mutex> lk(mu);
@@ -1129,12 +1229,7 @@ extern "C" int grape_ipc_attach(grape_ctx *c, const grape_ipc_handle *handles, i
 // one device context: the validated weights w = [amp | var] (on: some weight > 0), behind whatever evaluation is in flight
 static int shard_set_penalties(grape_ctx *c, const std::vector<double> &w, bool on)
 {
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->dev_pending) {                                    // (as grape_set_operators: d_pen_w may be in use)
-        HIP_TRY(c, hipEventSynchronize(c->ev_dev));
-        c->dev_pending = false;
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (int rc = drain(c, c)) return rc;                     // (d_pen_w may be in use)
     if (on && !c->d_pen_w) {
         HIP_TRY(c, hipMalloc((void **)&c->d_pen_w, sizeof(double) * w.size()));
         c->bytes += sizeof(double) * w.size();
@@ -1184,11 +1279,8 @@ extern "C" int grape_set_running_cost(grape_ctx *c, int32_t n_terms, const doubl
         if (n_terms < 0 || n_terms > 4)
             return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_running_cost: n_terms = " + std::to_string(n_terms) + " (must be in 0..4)");
         if (!rho) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_running_cost: null rho");
-        const char *why = nullptr;
-        const char *why_comm = "contexts with an attached communicator or mailbox exchange are not served";
-        if (c->is_group)                                     // (one shard: GRAPE_FLAG_FORCE_COLLECTIVE, a communicator of one rank)
-            why = c->sub.size() >= 2 ? "multi-device contexts are not served" : why_comm;
-        else if (c->comm || c->ipc_ranks > 1) why = why_comm;
+        const char *why = why_exchange_not_served(c);
+        if (why) {}
         else if (c->family != 0) why = "the operator dimension must be 2, 3 or 4 (the register-resident kernel family)";
         else if (c->cfg.sys_type != GRAPE_UNITARY_GATE)
             why = "StateTransfer / CoherenceTransfer (the sandwich needs a second term) are not served; hold the states as n x m columns under UnitaryGate";
@@ -1196,43 +1288,24 @@ extern "C" int grape_set_running_cost(grape_ctx *c, int32_t n_terms, const doubl
         else if (c->cfg.objective != GRAPE_OBJECTIVE_FOM) why = "objective = c1 is not served";
         if (why) return fail(c, GRAPE_ERR_UNSUPPORTED, std::string("grape_set_running_cost: ") + why);
         const size_t nr = 2 * (size_t)c->cfg.n * c->m * c->cfg.n_ensemble * n_terms, nw = (size_t)c->cfg.n_slices * n_terms;
-        for (size_t i = 0; i < nr; ++i)
-            if (!std::isfinite(R[i]))
-                return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_running_cost: R[" + std::to_string(i / 2) + "] is not finite");
-        for (size_t i = 0; i < nw; ++i)
-            if (!std::isfinite(rho[i]))
-                return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_running_cost: rho[" + std::to_string(i) + "] is not finite");
+        if (int rc = check_finite(c, R, nr, "grape_set_running_cost", "R", 2)) return rc;
+        if (int rc = check_finite(c, rho, nw, "grape_set_running_cost", "rho")) return rc;
     }
     if (c->is_group) {                                       // (switching off what can never be on)
         c->rc_terms = 0;
         return GRAPE_OK;
     }
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->dev_pending) {                                    // (as grape_set_penalties: the buffers may be in use)
-        HIP_TRY(c, hipEventSynchronize(c->ev_dev));
-        c->dev_pending = false;
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    double2 *d_R = nullptr;
-    double *d_rho = nullptr;
-    if (!off) {                                              // new buffers first: a failure leaves the previous setting in force
+    if (int rc = drain(c, c)) return rc;                     // (the buffers may be in use)
+    void *d_R = nullptr, *d_rho = nullptr;
+    if (!off) {
         const size_t rb = sizeof(double2) * (size_t)c->cfg.n * c->m * c->cfg.n_ensemble * n_terms;
         const size_t wb = sizeof(double) * (size_t)c->cfg.n_slices * n_terms;
-        hipError_t e = hipMalloc((void **)&d_R, rb);
-        if (e == hipSuccess) e = hipMemcpy(d_R, R, rb, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_rho, wb);
-        if (e == hipSuccess) e = hipMemcpy(d_rho, rho, wb, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(d_R);
-            (void)hipFree(d_rho);
-            (void)hipGetLastError();
-            return fail(c, e == hipErrorOutOfMemory ? GRAPE_ERR_ALLOC : GRAPE_ERR_HIP, std::string("grape_set_running_cost: ") + hipGetErrorString(e));
-        }
+        if (int rc = device_copies(c, "grape_set_running_cost", R, rb, &d_R, rho, wb, &d_rho)) return rc;
     }
     (void)hipFree(c->d_rc_R);
     (void)hipFree(c->d_rc_rho);
-    c->d_rc_R = d_R;
-    c->d_rc_rho = d_rho;
+    c->d_rc_R = (double2 *)d_R;
+    c->d_rc_rho = (double *)d_rho;
     c->rc_terms = off ? 0 : n_terms;
     return GRAPE_OK;
 }
@@ -1250,39 +1323,20 @@ extern "C" int grape_set_basis(grape_ctx *c, int32_t n_params, int32_t n_bases, 
             return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_basis: n_params = " + std::to_string(n_params) + " (must be in 1..n_slices)");
         if (n_bases != 1 && n_bases != K)
             return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_basis: n_bases = " + std::to_string(n_bases) + " (must be 1 or n_controls)");
-        const size_t np = (size_t)N * n_params * n_bases;
-        for (size_t i = 0; i < np; ++i)
-            if (!std::isfinite(phi[i]))
-                return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_basis: phi[" + std::to_string(i) + "] is not finite");
-        for (size_t i = 0; x0 && i < KN(c); ++i)
-            if (!std::isfinite(x0[i]))
-                return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_basis: x0[" + std::to_string(i) + "] is not finite");
+        if (int rc = check_finite(c, phi, (size_t)N * n_params * n_bases, "grape_set_basis", "phi")) return rc;
+        if (int rc = check_finite(c, x0, x0 ? KN(c) : 0, "grape_set_basis", "x0")) return rc;
     }
-    grape_ctx *lead = c->is_group ? c->sub[0] : c;
-    HIP_TRY(c, hipSetDevice(lead->device));
-    if (lead->dev_pending) {                                 // (as grape_set_operators: the buffers may be in use)
-        HIP_TRY(c, hipEventSynchronize(lead->ev_dev));
-        lead->dev_pending = false;
-    }
-    HIP_TRY(c, hipStreamSynchronize(lead->stream));
-    double *d_phi = nullptr, *d_x0 = nullptr;
-    if (!off) {                                              // new buffers first: a failure leaves the previous basis in force
+    if (int rc = drain(c, lead_of(c))) return rc;            // (the buffers may be in use)
+    void *d_phi = nullptr, *d_x0 = nullptr;
+    if (!off) {
         const size_t np = (size_t)N * n_params * n_bases;
-        hipError_t e = hipMalloc((void **)&d_phi, sizeof(double) * np);
-        if (e == hipSuccess) e = hipMemcpy(d_phi, phi, sizeof(double) * np, hipMemcpyHostToDevice);
-        if (e == hipSuccess && x0) e = hipMalloc((void **)&d_x0, sizeof(double) * KN(c));
-        if (e == hipSuccess && x0) e = hipMemcpy(d_x0, x0, sizeof(double) * KN(c), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(d_phi);
-            (void)hipFree(d_x0);
-            (void)hipGetLastError();
-            return fail(c, e == hipErrorOutOfMemory ? GRAPE_ERR_ALLOC : GRAPE_ERR_HIP, std::string("grape_set_basis: ") + hipGetErrorString(e));
-        }
+        if (int rc = device_copies(c, "grape_set_basis", phi, sizeof(double) * np, &d_phi, x0, x0 ? sizeof(double) * KN(c) : 0, &d_x0))
+            return rc;
     }
     (void)hipFree(c->d_basis_phi);
     (void)hipFree(c->d_basis_x0);
-    c->d_basis_phi = d_phi;
-    c->d_basis_x0 = d_x0;
+    c->d_basis_phi = (double *)d_phi;
+    c->d_basis_x0 = (double *)d_x0;
     c->basis_M = off ? 0 : n_params;
     c->basis_nb = off ? 1 : n_bases;
     return GRAPE_OK;
@@ -1301,29 +1355,19 @@ extern "C" int grape_set_bounds(grape_ctx *c, const double *lo, const double *hi
             return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_bounds: control " + std::to_string(k) + ": need finite lo < hi, or lo = -inf and hi = +inf");
         on = on || !free_k;
     }
-    grape_ctx *lead = c->is_group ? c->sub[0] : c;
-    HIP_TRY(c, hipSetDevice(lead->device));
-    if (lead->dev_pending) {                                 // (as grape_set_basis: the buffers may be in use)
-        HIP_TRY(c, hipEventSynchronize(lead->ev_dev));
-        lead->dev_pending = false;
-    }
-    HIP_TRY(c, hipStreamSynchronize(lead->stream));
-    if (on) {                                                // everything that can fail first: a failure leaves the previous bounds in force
-        double *d_b = nullptr, *d_s = c->d_slope;
+    if (int rc = drain(c, lead_of(c))) return rc;            // (the buffers may be in use)
+    if (on) {
+        void *d_b = nullptr, *d_s = nullptr;
         std::vector<double> lh(2 * (size_t)K);
         std::copy(lo, lo + K, lh.begin());
         std::copy(hi, hi + K, lh.begin() + K);
-        hipError_t e = hipMalloc((void **)&d_b, sizeof(double) * 2 * K);
-        if (e == hipSuccess) e = hipMemcpy(d_b, lh.data(), sizeof(double) * 2 * K, hipMemcpyHostToDevice);
-        if (e == hipSuccess && !d_s) e = hipMalloc((void **)&d_s, sizeof(double) * KN(c) * (size_t)c->B);   // (first use; kept from then on)
-        if (e != hipSuccess) {
-            (void)hipFree(d_b);
-            (void)hipGetLastError();
-            return fail(c, e == hipErrorOutOfMemory ? GRAPE_ERR_ALLOC : GRAPE_ERR_HIP, std::string("grape_set_bounds: ") + hipGetErrorString(e));
-        }
+        // (d_slope: allocated on first use, kept from then on)
+        if (int rc = device_copies(c, "grape_set_bounds", lh.data(), sizeof(double) * 2 * K, &d_b, nullptr,
+                                   c->d_slope ? 0 : sizeof(double) * KN(c) * (size_t)c->B, &d_s))
+            return rc;
         (void)hipFree(c->d_bounds);
-        c->d_bounds = d_b;
-        c->d_slope = d_s;
+        c->d_bounds = (double *)d_b;
+        if (d_s) c->d_slope = (double *)d_s;
     }
     c->bounds_on = on;
     return GRAPE_OK;
@@ -1359,12 +1403,9 @@ extern "C" int grape_get_controls(grape_ctx *c, const double *theta, double *x)
         std::memmove(x, theta, sizeof(double) * KN(c));
         return GRAPE_OK;
     }
-    grape_ctx *lead = c->is_group ? c->sub[0] : c;
+    grape_ctx *lead = lead_of(c);
     HIP_TRY(c, hipSetDevice(lead->device));
-    if (lead->dev_pending) {                                 // order behind the last grape_eval_device (it reads d_x)
-        HIP_TRY(c, hipStreamWaitEvent(lead->stream, lead->ev_dev, 0));
-        lead->dev_pending = false;
-    }
+    if (int rc = order_behind_device_call(c, lead)) return rc;
     std::memcpy(lead->h_stage, theta, sizeof(double) * KP(c));
     const grape::BasisOp op = basis_op(c, false, 1);
     grape::DoneSignal d;
@@ -1418,14 +1459,9 @@ extern "C" int grape_set_operators(grape_ctx *c, const double *A, const double *
     // the previous upload's flags over freed or partly rewritten buffers
     c->ops_set = false;
     DeviceGuard guard;
-    HIP_TRY(c, hipSetDevice(c->device));
-    // ordered behind the last evaluation BEFORE any device buffer is touched (the sparse lists, vectors and hoisted
-    // generators below are rewritten in place): an evaluation may still run on a caller's stream
-    if (c->dev_pending) {
-        HIP_TRY(c, hipEventSynchronize(c->ev_dev));
-        c->dev_pending = false;
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // BEFORE any device buffer is touched (the sparse lists, vectors and hoisted generators below are rewritten in place)
+    if (int rc = drain(c, c)) return rc;
+    const char *who = "grape_set_operators";
     const size_t nn = (size_t)c->cfg.n * c->cfg.n, K = c->cfg.n_controls, E = c->cfg.n_ensemble;
     // n x m states with m < n (UnitaryGate-style left multiplication of m column vectors, e.g. m = 1:
     // a vectorised density matrix under Liouvillian superoperators, test/liou.jl:38-48): run zero-padded
@@ -1590,22 +1626,8 @@ extern "C" int grape_set_operators(grape_ctx *c, const double *A, const double *
         if (nnz > 0) {
             const size_t nt = tidx.size();
             const size_t ni = nt + (nt + 1) + (size_t)nnz + (K + 1) + (size_t)nnz, nc = 2 * (size_t)nnz;
-            if (c->any_sp_i_cap < ni) {
-                (void)hipFree(c->d_any_sp_i); c->d_any_sp_i = nullptr;
-                c->bytes -= sizeof(int32_t) * c->any_sp_i_cap;
-                c->any_sp_i_cap = 0;
-                HIP_TRY(c, hipMalloc((void **)&c->d_any_sp_i, sizeof(int32_t) * ni));
-                c->any_sp_i_cap = ni;
-                c->bytes += sizeof(int32_t) * ni;
-            }
-            if (c->any_sp_c_cap < nc) {
-                (void)hipFree(c->d_any_sp_c); c->d_any_sp_c = nullptr;
-                c->bytes -= sizeof(double2) * c->any_sp_c_cap;
-                c->any_sp_c_cap = 0;
-                HIP_TRY(c, hipMalloc((void **)&c->d_any_sp_c, sizeof(double2) * nc));
-                c->any_sp_c_cap = nc;
-                c->bytes += sizeof(double2) * nc;
-            }
+            if (int rc = grow(c, &c->d_any_sp_i, &c->any_sp_i_bytes, sizeof(int32_t) * ni, who, "the sparse control lists")) return rc;
+            if (int rc = grow(c, &c->d_any_sp_c, &c->any_sp_c_bytes, sizeof(double2) * nc, who, "the sparse control lists")) return rc;
             int32_t *di = c->d_any_sp_i;                     // [tidx | tptr | ectl | cptr | caddr]
             HIP_TRY(c, hipMemcpy(di, tidx.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice));
             HIP_TRY(c, hipMemcpy(di + nt, tptr.data(), sizeof(int32_t) * (nt + 1), hipMemcpyHostToDevice));
@@ -1712,16 +1734,9 @@ extern "C" int grape_set_operators(grape_ctx *c, const double *A, const double *
         if (sp) {
             c->sp_nz = SM;
             const size_t need = E * K * (size_t)SM;
-            if (c->sp_cap < need) {                          // (the list length may change between uploads)
-                (void)hipFree(c->d_sp_coef); c->d_sp_coef = nullptr;
-                (void)hipFree(c->d_sp_addr); c->d_sp_addr = nullptr;
-                c->bytes -= (sizeof(double2) + sizeof(int32_t)) * c->sp_cap;
-                c->sp_cap = 0;
-                HIP_TRY(c, hipMalloc((void **)&c->d_sp_coef, sizeof(double2) * need));
-                HIP_TRY(c, hipMalloc((void **)&c->d_sp_addr, sizeof(int32_t) * need));
-                c->sp_cap = need;
-                c->bytes += (sizeof(double2) + sizeof(int32_t)) * need;
-            }
+            // (the list length may change between uploads)
+            if (int rc = grow(c, &c->d_sp_coef, &c->sp_coef_bytes, sizeof(double2) * need, who, "the sparse control lists")) return rc;
+            if (int rc = grow(c, &c->d_sp_addr, &c->sp_addr_bytes, sizeof(int32_t) * need, who, "the sparse control lists")) return rc;
             HIP_TRY(c, hipMemcpy(c->d_sp_coef, coef.data(), sizeof(double) * coef.size(), hipMemcpyHostToDevice));
             HIP_TRY(c, hipMemcpy(c->d_sp_addr, addr.data(), sizeof(int32_t) * addr.size(), hipMemcpyHostToDevice));
         }
@@ -1888,29 +1903,18 @@ extern "C" int grape_set_operators(grape_ctx *c, const double *A, const double *
         if (c->tp_C) {
             const size_t tsz = (size_t)c->NT * c->NT * 256, rows = (size_t)c->EU * c->B;
             const size_t dumps = ((general || dpp_small || c->grid) ? 2 : 1) * (size_t)c->tp_C;     // general flow: [Q_c | Q_c^T] and [R_c | U_c^T]
-            auto ensure = [&](void **ptr, size_t *cap, size_t bytes) -> hipError_t {
-                if (*cap >= bytes)
-                    return hipSuccess;
-                (void)hipFree(*ptr);
-                *ptr = nullptr;
-                c->bytes += bytes - *cap;
-                *cap = 0;
-                const hipError_t e = hipMalloc(ptr, bytes);
-                if (e == hipSuccess)
-                    *cap = bytes;
-                return e;
-            };
-            HIP_TRY(c, ensure((void **)&c->d_tp_q, &c->tp_cap[0], sizeof(double2) * rows * tsz * dumps));
-            HIP_TRY(c, ensure((void **)&c->d_tp_r, &c->tp_cap[1], sizeof(double2) * rows * tsz * dumps));
-            HIP_TRY(c, ensure((void **)&c->d_tp_m, &c->tp_cap[2], sizeof(double2) * rows * tsz));
-            HIP_TRY(c, ensure((void **)&c->d_tp_vec, &c->tp_cap[3], sizeof(double2) * rows * 32 * ((size_t)c->tp_C + 1)));
-            HIP_TRY(c, ensure((void **)&c->d_tp_z, &c->tp_cap[4], sizeof(double) * rows * 128));
+            const char *what = "the time chunks' products";
+            if (int rc = grow(c, &c->d_tp_q, &c->tp_cap[0], sizeof(double2) * rows * tsz * dumps, who, what)) return rc;
+            if (int rc = grow(c, &c->d_tp_r, &c->tp_cap[1], sizeof(double2) * rows * tsz * dumps, who, what)) return rc;
+            if (int rc = grow(c, &c->d_tp_m, &c->tp_cap[2], sizeof(double2) * rows * tsz, who, what)) return rc;
+            if (int rc = grow(c, &c->d_tp_vec, &c->tp_cap[3], sizeof(double2) * rows * 32 * ((size_t)c->tp_C + 1), who, what)) return rc;
+            if (int rc = grow(c, &c->d_tp_z, &c->tp_cap[4], sizeof(double) * rows * 128, who, what)) return rc;
             // unitary flow, many chunks: two-level scan over groups of ~sqrt(C) chunks
             c->tp_G = c->tp_g = 0;
             if (!thin && !c->grid && c->tp_C >= 16 && !env_on("GRAPE_TP_ONE_LEVEL")) {
                 c->tp_g = (int)std::lround(std::ceil(std::sqrt((double)c->tp_C)));
                 c->tp_G = (c->tp_C + c->tp_g - 1) / c->tp_g;
-                HIP_TRY(c, ensure((void **)&c->d_tp_a, &c->tp_cap[5], sizeof(double2) * rows * tsz * (general ? 4 : 2) * c->tp_G));
+                if (int rc = grow(c, &c->d_tp_a, &c->tp_cap[5], sizeof(double2) * rows * tsz * (general ? 4 : 2) * c->tp_G, who, what)) return rc;
             }
         }
     }
@@ -2049,23 +2053,9 @@ extern "C" int grape_set_operators(grape_ctx *c, const double *A, const double *
             if (!c->d_act_gn) HIP_TRY(c, hipMalloc((void **)&c->d_act_gn, sizeof(double) * (size_t)c->B * c->cfg.n_slices));
             if (dpp) {
                 const size_t need = sizeof(double2) * (size_t)c->Ec * ((size_t)c->cfg.n_slices + 1) * VS * ws_batch(c);
-                if (c->wrec_bytes < need) {
-                    (void)hipFree(c->d_wrec);
-                    c->d_wrec = nullptr;
-                    c->bytes += need - c->wrec_bytes;
-                    c->wrec_bytes = 0;
-                    HIP_TRY(c, hipMalloc((void **)&c->d_wrec, need));
-                    c->wrec_bytes = need;
-                }
+                if (int rc = grow(c, &c->d_wrec, &c->wrec_bytes, need, who, "the backward records")) return rc;
                 const size_t need_t = sizeof(double2) * c->ws_elems * ws_batch(c);
-                if (c->props_t_bytes < need_t) {
-                    (void)hipFree(c->d_props_t);
-                    c->d_props_t = nullptr;
-                    c->bytes += need_t - c->props_t_bytes;
-                    c->props_t_bytes = 0;
-                    HIP_TRY(c, hipMalloc((void **)&c->d_props_t, need_t));
-                    c->props_t_bytes = need_t;
-                }
+                if (int rc = grow(c, &c->d_props_t, &c->props_t_bytes, need_t, who, "the transposed propagators")) return rc;
             }
             HIP_TRY(c, hipMemcpy(c->d_act_a, aa.data(), sizeof(double) * aa.size(), hipMemcpyHostToDevice));
             HIP_TRY(c, hipMemcpy(c->d_act_an, an.data(), sizeof(double) * an.size(), hipMemcpyHostToDevice));
@@ -2145,31 +2135,13 @@ extern "C" int grape_set_operators(grape_ctx *c, const double *A, const double *
         }
         if (c->tp_C) {
             const size_t bytes = sizeof(double2) * nn * (size_t)c->cfg.n_ensemble * c->B * (size_t)c->tp_C;
-            auto ensure = [&](double2 **ptr, size_t *capb) -> hipError_t {
-                if (*capb >= bytes)
-                    return hipSuccess;
-                (void)hipFree(*ptr);
-                *ptr = nullptr;
-                c->bytes += bytes - *capb;
-                *capb = 0;
-                const hipError_t e = hipMalloc((void **)ptr, bytes);
-                if (e == hipSuccess)
-                    *capb = bytes;
-                return e;
-            };
-            HIP_TRY(c, ensure(&c->d_tp_q, &c->tp_cap[0]));
-            HIP_TRY(c, ensure(&c->d_tp_r, &c->tp_cap[1]));
-            HIP_TRY(c, ensure(&c->d_tp_m, &c->tp_cap[2]));      // (family 2: the states at the chunks' starts)
+            const char *what = "the time chunks' products";
+            if (int rc = grow(c, &c->d_tp_q, &c->tp_cap[0], bytes, who, what)) return rc;
+            if (int rc = grow(c, &c->d_tp_r, &c->tp_cap[1], bytes, who, what)) return rc;
+            if (int rc = grow(c, &c->d_tp_m, &c->tp_cap[2], bytes, who, what)) return rc;      // (family 2: the states at the chunks' starts)
         }
         const size_t need = per_block * (size_t)std::max(c->any_blocks, std::max(1, c->tp_C));
-        if (c->scratch_bytes < need) {
-            (void)hipFree(c->d_scratch);
-            c->d_scratch = nullptr;
-            c->bytes += need - c->scratch_bytes;
-            c->scratch_bytes = 0;
-            HIP_TRY(c, hipMalloc((void **)&c->d_scratch, need));
-            c->scratch_bytes = need;
-        }
+        if (int rc = grow(c, &c->d_scratch, &c->scratch_bytes, need, who, "the propagator blocks' scratch matrices")) return rc;
     }
     if (thin) {
         c->unitary = false;                                  // the thin chain serves Hermitian generators as well
@@ -2179,22 +2151,10 @@ extern "C" int grape_set_operators(grape_ctx *c, const double *A, const double *
         }
         HIP_TRY(c, hipMemcpy(c->d_vecs, vecs.data(), sizeof(double) * E * 4 * VS, hipMemcpyHostToDevice));
         const size_t rec = sizeof(double2) * (size_t)c->Ec * ((size_t)c->cfg.n_slices + 1) * VS * ws_batch(c);
-        if (c->states_bytes < rec) {                         // the forward pass's vector records: N + 1 per member
-            (void)hipFree(c->d_states);
-            c->d_states = nullptr;
-            c->bytes += rec - c->states_bytes;
-            c->states_bytes = 0;
-            HIP_TRY(c, hipMalloc((void **)&c->d_states, rec));
-            c->states_bytes = rec;
-        }
-    } else if ((!herm || c->exact_w1) && c->states_bytes < sizeof(double2) * c->ws_elems * ws_batch(c)) {
-        const size_t full = sizeof(double2) * c->ws_elems * ws_batch(c);
-        (void)hipFree(c->d_states);
-        c->d_states = nullptr;
-        c->bytes += full - c->states_bytes;
-        c->states_bytes = 0;
-        HIP_TRY(c, hipMalloc((void **)&c->d_states, full));
-        c->states_bytes = full;
+        // the forward pass's vector records: N + 1 per member
+        if (int rc = grow(c, &c->d_states, &c->states_bytes, rec, who, "the forward states")) return rc;
+    } else if (!herm || c->exact_w1) {
+        if (int rc = grow(c, &c->d_states, &c->states_bytes, sizeof(double2) * c->ws_elems * ws_batch(c), who, "the forward states")) return rc;
     }
     HIP_TRY(c, hipMemcpy(c->d_ops, packed.data(), sizeof(double) * packed.size(), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->d_wts, wts, sizeof(double) * E, hipMemcpyHostToDevice));
@@ -2295,37 +2255,110 @@ static bool states_stored(const grape_ctx *c)
 // this context adds the control penalties to its [G, F] (see grape_ctx::pen_on)
 static bool pen_active(const grape_ctx *c) { return c->pen_on && c->comm_rank == 0; }
 
+// the control penalties of the control array at d_x: added once, by the final reduction that takes `d` (reduce.hip) -- never
+// per member block or per shard
+static grape::DoneSignal with_pen(const grape_ctx *c, grape::DoneSignal d, const double *d_x)
+{
+    if (pen_active(c)) {
+        d.pen_x = d_x;
+        d.pen_w = c->d_pen_w;
+        d.pen_K = c->cfg.n_controls;
+        d.pen_N = c->cfg.n_slices;
+    }
+    return d;
+}
+
+// How the last kernel of an evaluation on `s` reports to the host: its last workgroup (d_done_counter) writes the results to
+// `host_out` (mapped host memory; null: the kernel has its own destination) and publishes the next sequence number in the
+// mapped flag that wait_flag polls.
+static grape::DoneSignal host_signal(grape_ctx *s, double *host_out)
+{
+    grape::DoneSignal d;
+    d.counter = s->d_done_counter;
+    d.flag = s->d_h_flag;
+    d.seq = ++s->seq;
+    d.host_out = host_out;
+    return d;
+}
+
+// what every launch of the register-resident family takes: the whole ensemble, n_x control arrays at d_x
+static SweepParams sweep_params(const grape_ctx *c, const double *d_x, int n_x)
+{
+    SweepParams p{};
+    p.ops = c->d_ops;
+    p.x = d_x;
+    p.wts = c->d_wts;
+    p.MPB = c->MPB;
+    p.BPX = c->NB;
+    p.n_x = n_x;
+    p.sk_magic = (uint32_t)((1ull << 32) / ((uint64_t)c->S * c->cfg.n_controls)) + 1u;
+    p.K = c->cfg.n_controls;
+    p.N = c->cfg.n_slices;
+    p.E = c->cfg.n_ensemble;
+    p.S = c->S;
+    p.LT = c->LT;
+    p.s_forced = c->cfg.expm_squarings;
+    p.variant = c->cfg.variant;
+    p.dt = c->cfg.duration / c->cfg.n_slices;                 // src/GRAPE.jl:42
+    return p;
+}
+
+// ... and its two launchers: the lane-pair kernels (sweep_pair.hip) or the lane-per-chunk ones (sweep_small.hip)
+static hipError_t launch_small_family(const grape_ctx *c, int sandwich, int mode, const SweepParams &p, hipStream_t stream)
+{
+    return c->pair ? grape::launch_sweep_pair(c->cfg.n, sandwich, mode, p, stream)
+                   : grape::launch_sweep_small(c->cfg.n, sandwich, mode, p, stream);
+}
+
+// The n_x control arrays that shard_stage_x left for this shard, on their way to the device on the private stream; *d_x:
+// where the kernels read them.
+static int upload_x(grape_ctx *s, int n_x, const double **d_x)
+{
+    const size_t kn = KN(s);
+    *d_x = s->d_x;
+    if (s->x_upload == 2)
+        *d_x = s->d_x_bar;
+    else if (s->x_upload == 1)  // a small kernel pulls x out of the coherent mapped staging buffer
+        HIP_TRY(s, grape::launch_copy(s->d_h_stage, s->d_x, (int)(kn * n_x), s->stream));
+    else
+        HIP_TRY(s, hipMemcpyAsync(s->d_x, s->h_stage, sizeof(double) * kn * n_x, hipMemcpyHostToDevice, s->stream));
+    return GRAPE_OK;
+}
+
+// one grouped all-reduce (sum) of `count` doubles in every shard's d_fg, in place on its private stream -- but for shard 0,
+// whose sum goes to `out0` on `st0` (the device-pointer entry points: the caller's buffer and stream)
+static int group_allreduce(grape_ctx *g, size_t count, double *out0, hipStream_t st0)
+{
+    NCCL_TRY(g, g_rccl.GroupStart());
+    for (size_t i = 0; i < g->sub.size(); ++i) {
+        grape_ctx *s = g->sub[i];
+        const ncclResult_t r = g_rccl.AllReduce(s->d_fg, i == 0 ? out0 : s->d_fg, count, ncclDouble, ncclSum, s->comm, i == 0 ? st0 : s->stream);
+        if (r != ncclSuccess) {
+            (void)g_rccl.GroupEnd();
+            return fail(g, GRAPE_ERR_COMM, std::string("ncclAllReduce: ") + g_rccl.GetErrorString(r));
+        }
+    }
+    NCCL_TRY(g, g_rccl.GroupEnd());
+    return GRAPE_OK;
+}
+
+// the n_x published rows [G (len) | F] in h_fg -> the caller's G (n_x, len) and F (n_x), either nullable
+static void copy_out_rows(const double *h_fg, int n_x, size_t len, double *F, double *G)
+{
+    for (int b = 0; b < n_x; ++b) {
+        if (G) std::memcpy(G + (size_t)b * len, h_fg + (size_t)b * (len + 1), sizeof(double) * len);
+        if (F) F[b] = h_fg[(size_t)b * (len + 1) + len];
+    }
+}
+
 // grape_set_running_cost: the buffers an evaluation of n_x arrays needs behind the CURRENT workspace plan (member chunk, batch
 // capacity, flow) -- sized here because grape_set_operators may re-plan the workspace and decides the flow
 static int rc_ensure(grape_ctx *c)
 {
     const size_t rows = sizeof(double) * (size_t)c->Ec * ws_batch(c) * (KN(c) + 1);
     const size_t xs = c->unitary ? 0 : sizeof(double2) * (size_t)c->Ec * ws_batch(c) * c->S * c->CH * c->cfg.n * c->m;
-    if (rows > c->rc_rows_bytes) {
-        (void)hipFree(c->d_rc_rows);
-        c->d_rc_rows = nullptr;
-        c->bytes -= c->rc_rows_bytes;
-        c->rc_rows_bytes = 0;
-        if (hipMalloc((void **)&c->d_rc_rows, rows) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(c, GRAPE_ERR_ALLOC, "grape_set_running_cost: no device memory for the members' running-cost rows");
-        }
-        c->rc_rows_bytes = rows;
-        c->bytes += rows;
-    }
-    if (xs > c->rc_xs_bytes) {
-        (void)hipFree(c->d_rc_xs);
-        c->d_rc_xs = nullptr;
-        c->bytes -= c->rc_xs_bytes;
-        c->rc_xs_bytes = 0;
-        if (hipMalloc((void **)&c->d_rc_xs, xs) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(c, GRAPE_ERR_ALLOC, "grape_set_running_cost: no device memory for the stored states of the general flow");
-        }
-        c->rc_xs_bytes = xs;
-        c->bytes += xs;
-    }
-    return GRAPE_OK;
+    if (int rc = grow(c, &c->d_rc_rows, &c->rc_rows_bytes, rows, "grape_set_running_cost", "the members' running-cost rows")) return rc;
+    return grow(c, &c->d_rc_xs, &c->rc_xs_bytes, xs, "grape_set_running_cost", "the stored states of the general flow");
 }
 
 static bool tile_folds_reduce(const grape_ctx *c, int n_x)
@@ -2395,29 +2428,14 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
     }
     KernelLogScope log_scope(&c->kernel_log);
     c->mf_wait = 0;
-    SweepParams p{};
-    p.ops = c->d_ops;
-    p.x = d_x;
+    SweepParams p = sweep_params(c, d_x, n_x);
     p.props = c->d_props;
     p.states = c->d_states;
     p.costates = c->d_costates;
     p.member_out = c->d_member_out;
-    p.wts = c->d_wts;
     p.block_out = c->d_block_out;
-    p.MPB = c->MPB;
-    p.BPX = c->NB;
-    p.n_x = n_x;
-    p.sk_magic = (uint32_t)((1ull << 32) / ((uint64_t)c->S * c->cfg.n_controls)) + 1u;
     p.stamps = c->d_stamps;
     p.xg_scratch = c->d_xg_scratch;
-    p.K = c->cfg.n_controls;
-    p.N = c->cfg.n_slices;
-    p.E = c->cfg.n_ensemble;
-    p.S = c->S;
-    p.LT = c->LT;
-    p.s_forced = c->cfg.expm_squarings;
-    p.variant = c->cfg.variant;
-    p.dt = c->cfg.duration / c->cfg.n_slices;                 // src/GRAPE.jl:42
     p.dump_w1 = c->exact_w1 ? 1 : 0;
     p.zphi = c->d_zphi;
     // n x 1 states under left multiplication at n = 4 (vec(rho) of one qubit under a Liouvillian with a dissipator: the general
@@ -2470,11 +2488,8 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
             if (p.zphi) q.zphi = p.zphi + 2 * (size_t)lo;
             q.E = cnt;
             q.BPX = (cnt + c->MPB - 1) / c->MPB;
-            const int mode = c->unitary ? 2 : (c->d_costates ? 1 : 0);
-            if (c->pair)
-                HIP_TRY(c, grape::launch_sweep_pair(c->cfg.n, c->cfg.sys_type != GRAPE_UNITARY_GATE, mode, q, stream));
-            else
-                HIP_TRY(c, grape::launch_sweep_small(c->cfg.n, c->cfg.sys_type != GRAPE_UNITARY_GATE, mode, q, stream));
+            const int mode = c->unitary ? 2 : (c->d_costates ? 1 : 0), sand = c->cfg.sys_type != GRAPE_UNITARY_GATE;
+            HIP_TRY(c, launch_small_family(c, sand, mode, q, stream));
             if (rc_on) {                                     // running cost of these members, from the propagators just stored
                 SweepParams r = q;
                 r.rc_only = 1;
@@ -2487,10 +2502,7 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
                 r.rc_rho = c->d_rc_rho;
                 r.rc_xs = c->d_rc_xs;
                 r.rc_rows = c->d_rc_rows;
-                if (c->pair)
-                    HIP_TRY(c, grape::launch_sweep_pair(c->cfg.n, 0, mode, r, stream));
-                else
-                    HIP_TRY(c, grape::launch_sweep_small(c->cfg.n, 0, mode, r, stream));
+                HIP_TRY(c, launch_small_family(c, 0, mode, r, stream));
             }
             if (c->obs_on) {                                 // grape_eval_observables: the read-out of these members
                 SweepParams o = q;
@@ -2504,10 +2516,7 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
                 o.obs_O = c->d_obs_O;
                 o.obs_y = c->obs_want_y ? c->d_obs_y : nullptr;
                 o.obs_xf = c->obs_want_xf ? c->d_obs_xf : nullptr;
-                if (c->pair)
-                    HIP_TRY(c, grape::launch_sweep_pair(c->cfg.n, c->cfg.sys_type != GRAPE_UNITARY_GATE, mode, o, stream));
-                else
-                    HIP_TRY(c, grape::launch_sweep_small(c->cfg.n, c->cfg.sys_type != GRAPE_UNITARY_GATE, mode, o, stream));
+                HIP_TRY(c, launch_small_family(c, sand, mode, o, stream));
             }
             if (exact) {                                     // exact gradient + objective from the stored trajectory
                 grape::ExactParams xq{};
@@ -2612,26 +2621,15 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
         if (rc) return rc;
     }
     if (timed) HIP_TRY(c, hipEventRecord(e1, stream));
-    // the control penalties of the n_x arrays: added once, by the final reduction below (reduce.hip) -- never per member
-    // block or per shard
-    auto with_pen = [&](grape::DoneSignal d, int b) {
-        if (pen_active(c)) {
-            d.pen_x = d_x + (size_t)b * KN(c);
-            d.pen_w = c->d_pen_w;
-            d.pen_K = c->cfg.n_controls;
-            d.pen_N = c->cfg.n_slices;
-        }
-        return d;
-    };
     if (exact)
         HIP_TRY(c, grape::launch_reduce(c->d_member_out, c->d_wts, c->d_partial, d_fg, p.E, (int)(KN(c) + 1), c->ksplit,
-                                        stream, with_pen(done, 0)));
+                                        stream, with_pen(c, done, d_x)));
     else if (direct || fold)
         ;                                                    // the sweep / forms kernel has written [G, F] (and the flag)
     else if (c->family == 0) {
         if (done.mflags && done.flag && done.host_out && !done.probe_out)
             c->mf_wait = grape::reduce_rows_mflags((int)(KN(c) + 1), n_x);       // (the launch takes the same decision)
-        HIP_TRY(c, grape::launch_reduce_rows(c->d_block_out, d_fg, c->NB, (int)(KN(c) + 1), n_x, stream, with_pen(done, 0)));
+        HIP_TRY(c, grape::launch_reduce_rows(c->d_block_out, d_fg, c->NB, (int)(KN(c) + 1), n_x, stream, with_pen(c, done, d_x)));
     }
     else {
         // one weighted reduction per control array (each reuses d_partial, in stream order); with a host
@@ -2647,7 +2645,7 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
                 }
             }
             HIP_TRY(c, grape::launch_reduce(c->d_member_out + (size_t)b * p.E * Qs, c->d_wts, c->d_partial,
-                                            d_fg + (size_t)b * Qs, p.E, (int)Qs, c->ksplit, stream, with_pen(db, b)));
+                                            d_fg + (size_t)b * Qs, p.E, (int)Qs, c->ksplit, stream, with_pen(c, db, d_x + (size_t)b * KN(c))));
         }
     }
     c->evaluated = true;
@@ -2712,20 +2710,14 @@ static int ipc_check(grape_ctx *c)
 // after c->timeout_s (device presumed hung).
 static int wait_stream(grape_ctx *c, hipStream_t stream)
 {
-    timespec t0;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    auto elapsed = [&]() {
-        timespec t;
-        clock_gettime(CLOCK_MONOTONIC, &t);
-        return (double)(t.tv_sec - t0.tv_sec) + 1e-9 * (double)(t.tv_nsec - t0.tv_nsec);
-    };
+    const double t0 = now_s();
     long nap_ns = 20000;
     for (unsigned it = 0;; ++it) {
         const hipError_t q = hipStreamQuery(stream);
         if (q == hipSuccess) return GRAPE_OK;
         if (q != hipErrorNotReady) HIP_TRY(c, q);
         if ((it & 63) != 63) continue;
-        const double el = elapsed();
+        const double el = now_s() - t0;
         if (el < 500e-6) continue;                          // spin phase
         if (el > c->timeout_s)
             return fail(c, GRAPE_ERR_TIMEOUT, "evaluation did not finish within " + std::to_string(c->timeout_s) +
@@ -2756,24 +2748,12 @@ static void shard_stage_x(grape_ctx *s, const double *x, int n_x)
 static int shard_issue(grape_ctx *s, int n_x, double *target, bool signal)
 {
     HIP_TRY(s, hipSetDevice(s->device));
-    if (s->dev_pending) {                                   // order behind the last grape_eval_device
-        HIP_TRY(s, hipStreamWaitEvent(s->stream, s->ev_dev, 0));
-        s->dev_pending = false;
-    }
-    const size_t kn = KN(s);
-    const double *d_x = s->d_x;
-    if (s->x_upload == 2)
-        d_x = s->d_x_bar;
-    else if (s->x_upload == 1)  // a small kernel pulls x out of the coherent mapped staging buffer
-        HIP_TRY(s, grape::launch_copy(s->d_h_stage, s->d_x, (int)(kn * n_x), s->stream));
-    else
-        HIP_TRY(s, hipMemcpyAsync(s->d_x, s->h_stage, sizeof(double) * kn * n_x, hipMemcpyHostToDevice, s->stream));
+    if (int rc = order_behind_device_call(s, s)) return rc;
+    const double *d_x = nullptr;
+    if (int rc = upload_x(s, n_x, &d_x)) return rc;
     grape::DoneSignal done;
     if (signal) {                  // single GPU: the reduce kernel stages [G, F] in d_fg and its last workgroup
-        done.counter = s->d_done_counter;          // writes them to the mapped host buffer + the completion flag
-        done.flag = s->d_h_flag;
-        done.seq = ++s->seq;
-        done.host_out = target;
+        done = host_signal(s, target);             // writes them to the mapped host buffer + the completion flag
         if (s->mf_publish) done.mflags = s->d_h_flag + 8;
         target = s->d_fg;
     }
@@ -2824,8 +2804,7 @@ void GroupWorker::run()
 {
     (void)hipSetDevice(shard->device);
     uint64_t seen = 0;
-    timespec idle_since;
-    clock_gettime(CLOCK_MONOTONIC, &idle_since);
+    double idle_since = now_s();
     for (;;) {
         unsigned spins = 0;
         while (req.load(std::memory_order_acquire) == seen) {
@@ -2834,10 +2813,7 @@ void GroupWorker::run()
             __builtin_ia32_pause();
 #endif
             if ((++spins & 4095) == 0) {                     // 2 ms without work: sleep until the next post
-                timespec now;
-                clock_gettime(CLOCK_MONOTONIC, &now);
-                const double idle = (double)(now.tv_sec - idle_since.tv_sec) + 1e-9 * (double)(now.tv_nsec - idle_since.tv_nsec);
-                if (idle > 2e-3) {
+                if (now_s() - idle_since > 2e-3) {
                     std::unique_lock<std::mutex> lk(mu);
                     asleep.store(true, std::memory_order_seq_cst);
                     cv.wait(lk, [&] { return req.load(std::memory_order_seq_cst) != seen || stop.load(); });
@@ -2848,7 +2824,7 @@ void GroupWorker::run()
         seen = req.load(std::memory_order_acquire);
         rc = job ? job(shard) : 0;
         done.store(seen, std::memory_order_release);
-        clock_gettime(CLOCK_MONOTONIC, &idle_since);
+        idle_since = now_s();
     }
 }
 
@@ -2865,13 +2841,7 @@ static int wait_flag(grape_ctx *s)
             if (flag[8 + i] != want) return false;
         return true;
     };
-    timespec t0;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    auto elapsed = [&]() {
-        timespec t;
-        clock_gettime(CLOCK_MONOTONIC, &t);
-        return (double)(t.tv_sec - t0.tv_sec) + 1e-9 * (double)(t.tv_nsec - t0.tv_nsec);
-    };
+    const double t0 = now_s();
     bool napped = false;
     auto done = [&](double el, bool first_look) {
         __atomic_thread_fence(__ATOMIC_ACQUIRE);
@@ -2897,11 +2867,11 @@ static int wait_flag(grape_ctx *s)
     for (unsigned it = 0;; ++it) {
         const unsigned long long seen = mf ? (all_flags() ? want : 0ull) : *flag;
         if (seen == want)
-            return done(elapsed(), it == 0);
+            return done(now_s() - t0, it == 0);
         if (seen == (want | grape::kSeqFailed))
             return fail(s, GRAPE_ERR_COMM, "the ranks' rows did not all arrive (mailbox exchange gave up): a peer is gone or stuck");
         if ((it & 1023) != 1023) continue;
-        const double el = elapsed();
+        const double el = now_s() - t0;
         if (el < spin_until) continue;                      // spin phase
         hipError_t q = hipStreamQuery(s->stream);           // a failed kernel never publishes: ask the runtime
         if (q != hipSuccess && q != hipErrorNotReady) HIP_TRY(s, q);
@@ -2979,17 +2949,8 @@ static int eval_device_impl(grape_ctx *c, const double *d_x, double *d_fg, void 
         c->evaluated = true;
         return GRAPE_OK;
     }
-    NCCL_TRY(c, g_rccl.GroupStart());
-    for (size_t i = 0; i < c->sub.size(); ++i) {
-        grape_ctx *s = c->sub[i];
-        const ncclResult_t r = g_rccl.AllReduce(s->d_fg, i == 0 ? d_fg : s->d_fg, (KN(c) + 1) * (size_t)n_x, ncclDouble, ncclSum,
-                                                s->comm, i == 0 ? st : s->stream);
-        if (r != ncclSuccess) {
-            (void)g_rccl.GroupEnd();
-            return fail(c, GRAPE_ERR_COMM, std::string("ncclAllReduce: ") + g_rccl.GetErrorString(r));
-        }
-    }
-    NCCL_TRY(c, g_rccl.GroupEnd());
+    rc = group_allreduce(c, (KN(c) + 1) * (size_t)n_x, d_fg, st);
+    if (rc) return rc;
     HIP_TRY(c, hipSetDevice(s0->device));
     HIP_TRY(c, hipEventRecord(s0->ev_dev, st));
     s0->dev_pending = true;
@@ -3006,7 +2967,7 @@ static int eval_device_impl(grape_ctx *c, const double *d_x, double *d_fg, void 
 static int eval_param_device(grape_ctx *c, const double *theta, double *out, hipStream_t st, int n_x,
                              grape::DoneSignal done = grape::DoneSignal())
 {
-    grape_ctx *lead = c->is_group ? c->sub[0] : c;
+    grape_ctx *lead = lead_of(c);
     HIP_TRY(c, hipSetDevice(lead->device));
     std::string head;                                        // (the evaluation below starts the log afresh)
     {
@@ -3087,24 +3048,18 @@ static int eval_host(grape_ctx *c, int n_x, const double *x, double *F, double *
         return fail(c, GRAPE_ERR_INVALID_ARG, std::string(who) + ": n_x must be in 1..grape_config.max_batch");
     if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, std::string(who) + ": operators not set");
     const size_t kn = KN(c), Q = kn + 1;
-    grape_ctx *lead = c->is_group ? c->sub[0] : c;
+    grape_ctx *lead = lead_of(c);
     int rc = ipc_check(c);
     if (rc) return rc;
     if (pulse_map(c)) {
         // parameter mode / bounds: theta (u) is staged in mapped host memory, where the expansion kernel reads it (the expansion is the
         // upload); the projection kernel writes [G_theta, F] to the mapped host buffer and publishes -- one host flag, as ever
-        const size_t kp = KP(c), Qp = kp + 1;
+        const size_t kp = KP(c);
         HIP_TRY(c, hipSetDevice(lead->device));
-        if (lead->dev_pending) {                             // order behind the last grape_eval_device
-            HIP_TRY(c, hipStreamWaitEvent(lead->stream, lead->ev_dev, 0));
-            lead->dev_pending = false;
-        }
+        rc = order_behind_device_call(c, lead);
+        if (rc) return rc;
         std::memcpy(lead->h_stage, x, sizeof(double) * kp * n_x);
-        grape::DoneSignal done;
-        done.counter = lead->d_done_counter;
-        done.flag = lead->d_h_flag;
-        done.seq = ++lead->seq;
-        rc = eval_param_device(c, lead->d_h_stage, lead->d_h_fg, lead->stream, n_x, done);
+        rc = eval_param_device(c, lead->d_h_stage, lead->d_h_fg, lead->stream, n_x, host_signal(lead, nullptr));
         if (rc) return rc;
         lead->dev_pending = false;                           // (issued on the context's own stream: already in order)
         lead->mf_wait = 0;
@@ -3116,10 +3071,7 @@ static int eval_host(grape_ctx *c, int n_x, const double *x, double *F, double *
         }
         rc = ipc_check(c);                                   // an exchange that gave up poisons the rows instead of the flag here
         if (rc) return rc;
-        for (int b = 0; b < n_x; ++b) {
-            if (G) std::memcpy(G + (size_t)b * kp, lead->h_fg + (size_t)b * Qp, sizeof(double) * kp);
-            if (F) F[b] = lead->h_fg[(size_t)b * Qp + kp];
-        }
+        copy_out_rows(lead->h_fg, n_x, kp, F, G);
         return GRAPE_OK;
     }
     if (!c->is_group && !c->comm && c->ipc_ranks <= 1) {
@@ -3132,11 +3084,10 @@ static int eval_host(grape_ctx *c, int n_x, const double *x, double *F, double *
             // x into every shard's buffer first, then all shards issue AT ONCE: shard 0 from this thread, the others from
             // their own issuing threads (GroupWorker) -- the last shard starts one launch latency behind the first one,
             // not G of them
-            timespec ts0, ts1, ts2, ts3;
-            clock_gettime(CLOCK_MONOTONIC, &ts0);
+            const double ts0 = now_s();
             for (grape_ctx *s : c->sub) shard_stage_x(s, x, n_x);
             c->group_nx = n_x;
-            clock_gettime(CLOCK_MONOTONIC, &ts1);
+            const double ts1 = now_s();
             const bool arrive = c->peer_sum && c->d_arrive && c->peer_all;
             if (arrive) {                                    // how this evaluation is published: the same for every shard
                 c->group_done = grape::DoneSignal();
@@ -3173,45 +3124,28 @@ static int eval_host(grape_ctx *c, int n_x, const double *x, double *F, double *
             }
             if (rc) return group_fail(c, lead, rc);
             if (rc_w) return group_fail(c, bad, rc_w);
-            clock_gettime(CLOCK_MONOTONIC, &ts2);
+            const double ts2 = now_s();
             if (arrive) {
                 // nothing left to issue: the last blocks to arrive sum and publish
-            } else if (c->peer_sum) {
-                grape::DoneSignal done;                      // the reduction kernel publishes like the single-GPU path
-                done.counter = lead->d_done_counter;
-                done.flag = lead->d_h_flag;
-                done.seq = ++lead->seq;
-                done.host_out = lead->d_h_fg;
-                rc = enqueue_peer_sum(c, lead->d_fg, lead->stream, true, done, false, n_x);
+            } else if (c->peer_sum) {                        // the reduction kernel publishes like the single-GPU path
+                rc = enqueue_peer_sum(c, lead->d_fg, lead->stream, true, host_signal(lead, lead->d_h_fg), false, n_x);
                 if (rc) return rc;
             } else {
-                NCCL_TRY(c, g_rccl.GroupStart());
-                for (grape_ctx *s : c->sub) {
-                    const ncclResult_t r = g_rccl.AllReduce(s->d_fg, s->d_fg, Q * (size_t)n_x, ncclDouble, ncclSum, s->comm, s->stream);
-                    if (r != ncclSuccess) {
-                        (void)g_rccl.GroupEnd();
-                        return fail(c, GRAPE_ERR_COMM, std::string("ncclAllReduce: ") + g_rccl.GetErrorString(r));
-                    }
-                }
-                NCCL_TRY(c, g_rccl.GroupEnd());
+                rc = group_allreduce(c, Q * (size_t)n_x, lead->d_fg, lead->stream);
+                if (rc) return rc;
             }
-            clock_gettime(CLOCK_MONOTONIC, &ts3);
-            auto dt = [](const timespec &a, const timespec &b) { return (double)(b.tv_sec - a.tv_sec) + 1e-9 * (double)(b.tv_nsec - a.tv_nsec); };
-            c->group_tm[0] += dt(ts0, ts1);
-            c->group_tm[1] += dt(ts1, ts2);
-            c->group_tm[2] += dt(ts2, ts3);
+            const double ts3 = now_s();
+            c->group_tm[0] += ts1 - ts0;
+            c->group_tm[1] += ts2 - ts1;
+            c->group_tm[2] += ts3 - ts2;
             c->group_tm_n += 1;
-            c->group_tm[4] -= (double)ts0.tv_sec + 1e-9 * (double)ts0.tv_nsec;      // (+ the end time below)
-            c->group_tm[3] -= (double)ts3.tv_sec + 1e-9 * (double)ts3.tv_nsec;
+            c->group_tm[4] -= ts0;                           // (+ the end time below)
+            c->group_tm[3] -= ts3;
         } else if (c->ipc_ranks > 1) {
             rc = shard_enqueue_host(c, x, n_x, c->d_fg, false);
             if (rc) return rc;
-            grape::DoneSignal done;                          // the exchange kernel publishes like the single-GPU path
-            done.counter = c->d_done_counter;
-            done.flag = c->d_h_flag;
-            done.seq = ++c->seq;
-            done.host_out = c->d_h_fg;
-            rc = enqueue_ipc_allreduce(c, c->d_fg, nullptr, c->stream, done, n_x);
+            // the exchange kernel publishes like the single-GPU path
+            rc = enqueue_ipc_allreduce(c, c->d_fg, nullptr, c->stream, host_signal(c, c->d_h_fg), n_x);
             if (rc) return rc;
         } else {
             rc = shard_enqueue_host(c, x, n_x, c->d_fg, false);
@@ -3221,19 +3155,14 @@ static int eval_host(grape_ctx *c, int n_x, const double *x, double *F, double *
         }
         if (!(c->is_group && c->peer_sum) && !(c->ipc_ranks > 1)) {
             HIP_TRY(c, hipSetDevice(lead->device));
-            grape::DoneSignal done;
-            done.counter = lead->d_done_counter;
-            done.flag = lead->d_h_flag;
-            done.seq = ++lead->seq;
+            const grape::DoneSignal done = host_signal(lead, nullptr);
             KernelLogScope log_scope(&lead->kernel_log, true);
             HIP_TRY(c, grape::launch_copy(lead->d_fg, lead->d_h_fg, (int)(Q * (size_t)n_x), lead->stream, done));
         }
     }
     rc = wait_flag(lead);                                    // [G, F] are in host memory
     if (c->is_group) {
-        timespec te;
-        clock_gettime(CLOCK_MONOTONIC, &te);
-        const double tend = (double)te.tv_sec + 1e-9 * (double)te.tv_nsec;
+        const double tend = now_s();
         c->group_tm[3] += tend;
         c->group_tm[4] += tend;
     }
@@ -3249,10 +3178,7 @@ static int eval_host(grape_ctx *c, int n_x, const double *x, double *F, double *
         }
         c->evaluated = true;
     }
-    for (int b = 0; b < n_x; ++b) {
-        if (G) std::memcpy(G + (size_t)b * kn, lead->h_fg + (size_t)b * Q, sizeof(double) * kn);
-        if (F) F[b] = lead->h_fg[(size_t)b * Q + kn];
-    }
+    copy_out_rows(lead->h_fg, n_x, kn, F, G);
     return GRAPE_OK;
 }
 
@@ -3279,35 +3205,14 @@ extern "C" int grape_eval_batch_device(grape_ctx *c, int32_t n_x, const double *
 }
 
 // ---- grape_eval_observables: one evaluation + the read-out along its trajectory --------------------------------------------
-// grows one of the read-out's device buffers (never shrinks it); counted in grape_info.workspace_bytes
-template <class T>
-static int obs_grow(grape_ctx *c, T **buf, size_t *have, size_t want, const char *what)
-{
-    if (want <= *have) return GRAPE_OK;
-    (void)hipFree(*buf);
-    *buf = nullptr;
-    c->bytes -= *have;
-    *have = 0;
-    if (hipMalloc((void **)buf, want) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, GRAPE_ERR_ALLOC, std::string("grape_eval_observables: no device memory for ") + what);
-    }
-    *have = want;
-    c->bytes += want;
-    return GRAPE_OK;
-}
-
 extern "C" int grape_eval_observables(grape_ctx *c, const double *x, int32_t n_obs, int32_t per_member, const double *O,
                                       double *y, double *X_final, double *F)
 {
     DeviceGuard guard;
     if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_observables: null context");
     // what the context cannot serve first, as the header lists it; then the arguments
-    const char *why = nullptr;
-    const char *why_comm = "contexts with an attached communicator or mailbox exchange are not served";
-    if (c->is_group)                                         // (one shard: GRAPE_FLAG_FORCE_COLLECTIVE, a communicator of one rank)
-        why = c->sub.size() >= 2 ? "multi-device contexts are not served" : why_comm;
-    else if (c->comm || c->ipc_ranks > 1) why = why_comm;
+    const char *who = "grape_eval_observables", *why = why_exchange_not_served(c);
+    if (why) {}
     else if (c->family != 0) why = "the operator dimension must be 2, 3 or 4 (the sweeps that leave every propagator in the workspace)";
     else if (c->cfg.objective != GRAPE_OBJECTIVE_FOM) why = "objective = c1 is not served";
     else if (c->cfg.gradient == GRAPE_GRADIENT_EXACT) why = "gradient = exact is not served";
@@ -3323,22 +3228,20 @@ extern "C" int grape_eval_observables(grape_ctx *c, const double *x, int32_t n_o
     if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, "grape_eval_observables: operators not set");
     const size_t n = (size_t)c->cfg.n, m = (size_t)c->m, E = (size_t)c->cfg.n_ensemble, N = (size_t)c->cfg.n_slices;
     const size_t n_O = n * m * (per_member ? E : 1) * (size_t)n_obs;
-    for (size_t i = 0; i < 2 * n_O; ++i)
-        if (!std::isfinite(O[i]))
-            return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_observables: O[" + std::to_string(i / 2) + "] is not finite");
+    int rc = check_finite(c, O, 2 * n_O, who, "O", 2);
+    if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const bool want_y = y != nullptr && n_obs > 0;
-    int rc = GRAPE_OK;
     if (want_y) {
-        rc = obs_grow(c, &c->d_obs_O, &c->obs_O_bytes, sizeof(double2) * n_O, "the probes");
+        rc = grow(c, &c->d_obs_O, &c->obs_O_bytes, sizeof(double2) * n_O, who, "the probes");
         if (rc) return rc;
-        rc = obs_grow(c, &c->d_obs_y, &c->obs_y_bytes, sizeof(double2) * (N + 1) * (size_t)n_obs * E, "the expectation values");
+        rc = grow(c, &c->d_obs_y, &c->obs_y_bytes, sizeof(double2) * (N + 1) * (size_t)n_obs * E, who, "the expectation values");
         if (rc) return rc;
         // (the buffer belongs to this entry point alone, which is blocking: no launch in flight reads it)
         HIP_TRY(c, hipMemcpy(c->d_obs_O, O, sizeof(double2) * n_O, hipMemcpyHostToDevice));
     }
     if (X_final) {
-        rc = obs_grow(c, &c->d_obs_xf, &c->obs_xf_bytes, sizeof(double2) * n * m * E, "the final states");
+        rc = grow(c, &c->d_obs_xf, &c->obs_xf_bytes, sizeof(double2) * n * m * E, who, "the final states");
         if (rc) return rc;
     }
     c->obs_n = n_obs;
@@ -3380,10 +3283,7 @@ static int fom_issue(grape_ctx *c, const double *x, int n_x)
         std::memcpy(c->h_stage, x, sizeof(double) * KP(c) * n_x);
     else
         shard_stage_x(c, x, n_x);
-    if (c->dev_pending) {                                   // order behind the last grape_eval_device
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_dev, 0));
-        c->dev_pending = false;
-    }
+    if (int rc = order_behind_device_call(c, c)) return rc;
     KernelLogScope log_scope(&c->kernel_log);
     const double *d_x = c->d_x;
     const grape::BasisOp bop = basis_op(c, false, n_x);
@@ -3391,35 +3291,13 @@ static int fom_issue(grape_ctx *c, const double *x, int n_x)
         grape::DoneSignal bd;
         bd.basis = &bop;
         HIP_TRY(c, grape::launch_copy(c->d_h_stage, c->d_x, (int)(kn * n_x), c->stream, bd));
-    } else if (c->x_upload == 2)
-        d_x = c->d_x_bar;
-    else if (c->x_upload == 1)
-        HIP_TRY(c, grape::launch_copy(c->d_h_stage, c->d_x, (int)(kn * n_x), c->stream));
-    else
-        HIP_TRY(c, hipMemcpyAsync(c->d_x, c->h_stage, sizeof(double) * kn * n_x, hipMemcpyHostToDevice, c->stream));
-    if (!param) c->kernel_log.clear();                       // (the names of THIS call's evaluation kernels: not the x upload, as grape_eval)
-    grape::DoneSignal done;
-    done.counter = c->d_done_counter;
-    done.flag = c->d_h_flag;
-    done.seq = ++c->seq;
-    done.host_out = c->d_h_fg;
+    } else {
+        if (int rc = upload_x(c, n_x, &d_x)) return rc;
+        c->kernel_log.clear();                               // (the names of THIS call's evaluation kernels: not the x upload, as grape_eval)
+    }
+    grape::DoneSignal done = host_signal(c, c->d_h_fg);
     c->mf_wait = 0;
-    SweepParams p{};
-    p.ops = c->d_ops;
-    p.x = d_x;
-    p.wts = c->d_wts;
-    p.MPB = c->MPB;
-    p.BPX = c->NB;
-    p.n_x = n_x;
-    p.sk_magic = (uint32_t)((1ull << 32) / ((uint64_t)c->S * c->cfg.n_controls)) + 1u;
-    p.K = c->cfg.n_controls;
-    p.N = c->cfg.n_slices;
-    p.E = c->cfg.n_ensemble;
-    p.S = c->S;
-    p.LT = c->LT;
-    p.s_forced = c->cfg.expm_squarings;
-    p.variant = c->cfg.variant;
-    p.dt = c->cfg.duration / c->cfg.n_slices;
+    SweepParams p = sweep_params(c, d_x, n_x);
     p.fom_only = 1;
     p.fom_objective = c->cfg.objective;
     p.fom_member = c->d_fom_member;
@@ -3431,11 +3309,7 @@ static int fom_issue(grape_ctx *c, const double *x, int n_x)
         p.direct_flag = done.flag;
         p.direct_seq = done.seq;
     }
-    const int mode = c->unitary ? 2 : 0;
-    if (c->pair)
-        HIP_TRY(c, grape::launch_sweep_pair(c->cfg.n, c->cfg.sys_type != GRAPE_UNITARY_GATE, mode, p, c->stream));
-    else
-        HIP_TRY(c, grape::launch_sweep_small(c->cfg.n, c->cfg.sys_type != GRAPE_UNITARY_GATE, mode, p, c->stream));
+    HIP_TRY(c, launch_small_family(c, c->cfg.sys_type != GRAPE_UNITARY_GATE, c->unitary ? 2 : 0, p, c->stream));
     if (direct)
         return GRAPE_OK;
     if (!pen_active(c)) {
@@ -3454,11 +3328,8 @@ static int fom_issue(grape_ctx *c, const double *x, int n_x)
             db.stage_base = c->d_fg;
             db.n_total = n_x;
         }
-        db.pen_x = d_x + (size_t)b * kn;
-        db.pen_w = c->d_pen_w;
-        db.pen_K = c->cfg.n_controls;
-        db.pen_N = c->cfg.n_slices;
-        HIP_TRY(c, grape::launch_reduce_rows(c->d_fom_rows + (size_t)b * c->NB, c->d_fg + b, c->NB, 1, 1, c->stream, db));
+        HIP_TRY(c, grape::launch_reduce_rows(c->d_fom_rows + (size_t)b * c->NB, c->d_fg + b, c->NB, 1, 1, c->stream,
+                                             with_pen(c, db, d_x + (size_t)b * kn)));
     }
     return GRAPE_OK;
 }
@@ -3565,8 +3436,7 @@ struct LbfgsRun {
         if (fused_probe) {
             // the evaluation's own reduction publishes the scalars (same bits as lbfgs_select_kernel's): one launch less
             // on the dependent chain of every trial step
-            grape::DoneSignal d = signal();
-            d.counter = lead->d_done_counter;
+            grape::DoneSignal d = host_signal(lead, nullptr);
             d.probe_dir = st.d;
             d.probe_sc = st.sc;
             d.probe_out = st.host_sc + 8;
@@ -3810,7 +3680,7 @@ extern "C" int grape_lbfgs(grape_ctx *c, const double *x0, const grape_lbfgs_opt
     if (multi && o.line_search == 2 && c->B < 2)
         return fail(c, GRAPE_ERR_UNSUPPORTED, "grape_lbfgs: the batched ladder search (line_search = 2) needs max_batch >= 2 "
                                               "(multi-device contexts default to the Hager-Zhang search)");
-    grape_ctx *lead = c->is_group ? c->sub[0] : c;
+    grape_ctx *lead = lead_of(c);
     int B = 1;
     if (o.line_search == 2 || (!multi && o.probes > 1)) {        // (multi-device contexts: batched probes only on request)
         B = o.probes;
@@ -3825,10 +3695,7 @@ extern "C" int grape_lbfgs(grape_ctx *c, const double *x0, const grape_lbfgs_opt
         if (B < 1) B = 1;
     }
     HIP_TRY(c, hipSetDevice(lead->device));
-    if (lead->dev_pending) {
-        HIP_TRY(c, hipStreamWaitEvent(lead->stream, lead->ev_dev, 0));
-        lead->dev_pending = false;
-    }
+    if (int rc0 = order_behind_device_call(c, lead)) return rc0;
     // workspace (freed on return): vectors + history + trial points/results + scalars
     const size_t n_dbl = 3 * kn + 2 * (size_t)m * kn + m + (size_t)B * kn + (size_t)B * Q + grape::kLbfgsMaxProbes + 8 +
                          8 + 2 * (size_t)m * m + (size_t)grape::kLbfgsDotBlocks * grape::kLbfgsDotStride;
@@ -3884,8 +3751,7 @@ extern "C" int grape_lbfgs(grape_ctx *c, const double *x0, const grape_lbfgs_opt
         (void)hipHostFree(h_sc);
         return code;
     };
-    timespec t0;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
+    const double t0 = now_s();
     // f(x0), g(x0): x0 goes to the trial slot, the evaluation's [g, F] to the iterate
     if (hipMemcpyAsync(st.x, x0, sizeof(double) * kn, hipMemcpyHostToDevice, lead->stream) != hipSuccess ||
         hipMemcpyAsync(st.xt, st.x, sizeof(double) * kn, hipMemcpyDeviceToDevice, lead->stream) != hipSuccess)
@@ -4055,11 +3921,9 @@ extern "C" int grape_lbfgs(grape_ctx *c, const double *x0, const grape_lbfgs_opt
         hipStreamSynchronize(lead->stream) != hipSuccess)
         return cleanup(fail(c, GRAPE_ERR_HIP, "grape_lbfgs: download of the minimiser failed"));
     std::memcpy(x_min, lead->h_fg, sizeof(double) * kn);
-    timespec t1;
-    clock_gettime(CLOCK_MONOTONIC, &t1);
     result->minimum = F;
     result->g_norm = gnorm;
-    result->seconds = (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec);
+    result->seconds = now_s() - t0;
     result->iterations = it;
     result->evaluations = run.evals;
     result->status = status;
@@ -4357,24 +4221,20 @@ extern "C" int grape_get_info(const grape_ctx *c, grape_info *info)
     info->waves_per_member = c->W;
     info->expm_squarings = c->cfg.expm_squarings;
     info->kernel_family = c->family;
-    info->unitary_flow = c->unitary ? 1 : 0;
     info->expm_theta = grape::kTheta8;
     info->workspace_bytes = c->bytes;
     std::snprintf(info->arch, sizeof(info->arch), "%s", c->arch);
     info->n_devices = c->is_group ? (int32_t)c->sub.size() : 1;
     info->comm_size = c->comm_size;
     info->comm_rank = c->comm_rank;
-    info->members_first_device = c->is_group ? c->sub[0]->cfg.n_ensemble : c->cfg.n_ensemble;
-    if (c->is_group) info->unitary_flow = c->sub[0]->unitary ? 1 : 0;
-    info->lane_pair = (c->is_group ? c->sub[0]->pair : c->pair) ? 1 : 0;
-    info->states_stored = states_stored(c->is_group ? c->sub[0] : c) ? 1 : 0;
-    info->rank_one_chain = (c->is_group ? c->sub[0]->thin : c->thin) ? 1 : 0;
     {
-        const grape_ctx *s0 = c->is_group ? c->sub[0] : c;
+        const grape_ctx *s0 = lead_of(c);
+        info->members_first_device = s0->cfg.n_ensemble;
+        info->unitary_flow = s0->unitary ? 1 : 0;
+        info->lane_pair = s0->pair ? 1 : 0;
+        info->states_stored = states_stored(s0) ? 1 : 0;
+        info->rank_one_chain = s0->thin ? 1 : 0;
         info->sparse_controls = (s0->sparse_ctrl || s0->any_sp_nnz) ? 1 : 0;
-    }
-    {
-        const grape_ctx *s0 = c->is_group ? c->sub[0] : c;
         info->fused_forward = (s0->thin && !s0->action && tile_fuse_forward(tile_params(s0, nullptr, 1)) == 1) ? 1 : 0;
         info->time_chunks = s0->tp_C;
         info->hoisted_controls = s0->hoist == 1 ? 1 : 0;
