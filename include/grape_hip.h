@@ -384,6 +384,43 @@ int grape_get_controls(grape_ctx *ctx, const double *theta, double *x);
  * exchanged row. */
 int grape_set_bounds(grape_ctx *ctx, const double *lo, const double *hi);
 
+/* Soft worst case over the ensemble in place of its weighted mean.  Additive to ABI v8.
+ *   beta   finite; 0: off (the weighted mean, as ever)
+ * With W = sum_k w_k and F_k, g_k the members' unweighted results (what grape_get_member_results returns):
+ *   F_beta = (W / beta) log( (1 / W) sum_k w_k exp(beta F_k) )
+ *   p_k    = W w_k exp(beta F_k) / sum_j w_j exp(beta F_j)          (sum_k p_k = W)
+ *   G_beta = sum_k p_k g_k
+ * beta -> 0 gives the mean the library returns without a risk; beta -> +inf gives W max_k F_k, beta -> -inf W min_k F_k.
+ * F is whatever the optimisers minimise: for the C1-type objectives (an infidelity) beta > 0 is the soft worst case.  Both
+ * signs are accepted.  G_beta is the chain rule applied to the gradient convention of the context: with gradient = exact it
+ * is the derivative of F_beta; with the reference's first-order grad_func! it is as exact as G is without a risk.
+ * Composition: the penalties of grape_set_penalties are added behind F_beta and G_beta, once, as ever; a basis and bounds sit
+ * in front and behind unchanged -- expand / saturate, evaluate, risk-weighted sum, penalty, slope / projection.  grape_eval,
+ * grape_eval_device, both batched forms (every array gets its own p), grape_lbfgs (its minimum and g_norm are then those
+ * of F_beta) and the F of grape_eval_observables return the risk-weighted [G, F].  grape_eval_fom takes its fallback while a
+ * risk is set, as it does under a running cost, and returns grape_eval's F bit for bit; its member_F stays the unweighted
+ * F_k and is available on every context while a risk is set.  grape_get_member_results, grape_get_trajectory, y and
+ * X_final of grape_eval_observables do not change (a context of n <= 4 without GRAPE_FLAG_MEMBER_RESULTS still answers
+ * GRAPE_ERR_NOT_READY to grape_get_member_results: the rows this feature keeps there are private to it).
+ * On the device: every kernel family leaves the members' unweighted rows in HBM; risk_weights_kernel (one workgroup per
+ * control array) forms M = max beta F_k over the members of positive weight and S = sum_k w_k exp(beta F_k - M) in a
+ * fixed tree, writes p and F_beta = (W / beta)(M + log(S / W)); the final reduction sums the rows with p in place of w and
+ * puts F_beta in front of the penalty.  No atomics: results are bitwise reproducible call to call, and a member-chunked
+ * context returns the unchunked context's bits.  A non-finite F_k makes F and G NaN; a member with w_k = 0 gets p_k = 0.
+ * Served: every operator dimension, system type, variant, gradient and objective, max_batch > 1, member-chunked contexts,
+ * GRAPE_FLAG_KEEP_COSTATES -- on single-device contexts.  GRAPE_ERR_UNSUPPORTED with the reason in grape_last_error:
+ * multi-device contexts; an attached communicator or mailbox (grape_comm_attach / grape_ipc_attach are refused while a risk
+ * is set); a running cost in force (grape_set_running_cost with n_terms > 0 is refused while a risk is set: the members'
+ * J_k are not in the member rows).  GRAPE_ERR_INVALID_ARG: beta NaN or +-inf; with beta != 0, a negative ensemble weight or
+ * W = 0 -- checked here once operators are set, and by grape_set_operators while a risk is in force.
+ * Valid any time after grape_create; persists across grape_set_operators; ordered behind an in-flight grape_eval_device
+ * like the other settings.  After any failure the previous setting stays.  beta = 0, and a context that never calls this,
+ * launch exactly the kernels they always did and return the same bits. */
+int grape_set_risk(grape_ctx *ctx, double beta);
+/* p: host f64[E], the p_k of the last evaluation (array 0 of a batch).  GRAPE_ERR_NOT_READY before an evaluation with a
+ * risk in force. */
+int grape_get_risk_weights(grape_ctx *ctx, double *p);
+
 /* The closure body, src/solve.jl:164-196 (E>1) / :75-100 (E=1):
  *   F = sum_k w_k F_k ,  G[c,t] = sum_k w_k g_k[c,t]   with (F_k, g_k) = _fom_and_gradient_GRAPE!.
  * x: host (K,N) f64.  F (nullable): host f64.  G (nullable): host (K,N) f64 -- Optim passes

@@ -190,6 +190,19 @@ function set_bounds!(ctx::GrapeContext, lo::Union{Nothing,Vector{Float64}}, hi::
                                         ctx.handle, lo, hi))
 end
 
+# grape_set_risk: the soft worst case over the ensemble in place of its weighted mean -- from here on every evaluation returns
+# F_beta = (W / beta) log((1 / W) sum_k w_k exp(beta F_k)) and G_beta = sum_k p_k g_k.  beta = 0 switches it off.
+# (Not executed where this file was written, like set_bounds!.)
+set_risk!(ctx::GrapeContext, beta::Real) =
+    check(ctx, ccall((:grape_set_risk, libgrape), Cint, (Ptr{Cvoid}, Float64), ctx.handle, Float64(beta)))
+
+"grape_get_risk_weights: p_k of the last evaluation under set_risk! (array 0 of a batch); sum(p) == sum(wts)."
+function risk_weights(ctx::GrapeContext)
+    p = Vector{Float64}(undef, ctx.E)
+    GC.@preserve p check(ctx, ccall((:grape_get_risk_weights, libgrape), Cint, (Ptr{Cvoid}, Ptr{Float64}), ctx.handle, p))
+    p
+end
+
 "grape_get_controls: the physical pulse (K, N) of a parameter array theta (K, M), expanded (and, with bounds, saturated) on the device."
 function controls(ctx::GrapeContext, theta::Matrix{Float64})
     x = Matrix{Float64}(undef, ctx.K, ctx.N)

@@ -112,6 +112,9 @@ class GRAPE:
     running_costs: Any = None      # list of ForbiddenStates / EvolutionTime (new: the reference's C5 / C6 / C7 are called by none
                                    # of its solvers): costs on the intermediate states, added to the objective on the device
                                    # (grape_set_running_cost; n = 2..4, UnitaryGate-type problems, one device)
+    risk: float = 0.0              # beta of grape_set_risk (new): the optimiser -- host or device -- minimises the soft worst case
+                                   # F_beta = (W / beta) log((1 / W) sum_k w_k exp(beta F_k)) over the ensemble instead of its
+                                   # weighted mean; res.minimum is F_beta.  0: the mean.  One device, no running costs
 
 
 @dataclass
@@ -521,7 +524,8 @@ def save(solres, file_path):
                                             **({"bounds": [np.asarray(b, dtype=np.float64).tolist() for b in alg.bounds]}
                                                if getattr(alg, "bounds", None) is not None else {}),
                                             **({"running_costs": [c.to_json() for c in alg.running_costs]}
-                                               if getattr(alg, "running_costs", None) else {})},
+                                               if getattr(alg, "running_costs", None) else {}),
+                                            **({"risk": float(alg.risk)} if getattr(alg, "risk", 0.0) else {})},
                                            default=_json_default)),
     }
     if ens:
@@ -685,9 +689,12 @@ def solve(prob, alg: Optional[GRAPE] = None, engine=None):
     eng = engine or make_engine(prob, alg, **({"max_batch": 4} if batched else {}))
     basis = getattr(alg, "basis", None)
     bounds = getattr(alg, "bounds", None)
+    risk = float(getattr(alg, "risk", 0.0) or 0.0)
     params = None
     try:
         guess = np.asarray((prob.prob if isinstance(prob, EnsembleProblem) else prob).guess, float)
+        if risk:                                               # every evaluation below returns the risk-weighted [G, F]
+            eng.set_risk(risk)
         if bounds is not None:                                 # the optimiser's variables are the raw pulse from here on
             guess = bounds_start(guess, *bounds)
             eng.set_bounds(*bounds)
@@ -707,6 +714,8 @@ def solve(prob, alg: Optional[GRAPE] = None, engine=None):
                 eng.set_basis(None)
             if bounds is not None and not own:
                 eng.set_bounds(None)
+            if risk and not own:
+                eng.set_risk(0.0)
     finally:
         if own:
             eng.close()

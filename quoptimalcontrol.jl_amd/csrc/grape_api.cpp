@@ -214,6 +214,17 @@ struct grape_ctx {
     bool bounds_on = false;                    // some control has finite bounds
     double *d_bounds = nullptr;                // [lo (K) | hi (K)]
     double *d_slope = nullptr;                 // (K, N, max_batch): dx/du of the last expansion
+    // grape_set_risk: the soft worst case over the ensemble in place of its weighted mean.  Every family's final reduction is
+    // launch_reduce over the members' unweighted rows with this evaluation's weights p (DoneSignal::risk_p); a family-0
+    // context without member rows of its own gets a private buffer for them, which no accessor reads.  Single-device
+    // contexts without an exchange and without a running cost only.
+    double risk_beta = 0.0;                    // != 0: in force
+    double *d_risk_rows = nullptr;             // family 0 without d_member_out: (K N + 1, E, max_batch)
+    double *d_risk_p = nullptr;                // [p (E, max_batch) | F_beta (max_batch)]
+    size_t risk_rows_bytes = 0, risk_p_bytes = 0;
+    int risk_slot = 0;                         // the array of a batch that runs array by array: which p / F_beta it writes
+    bool risk_evaluated = false;               // d_risk_p holds the weights of an evaluation under the current setting
+    std::vector<double> h_wts;                 // host copy of the ensemble weights (grape_set_risk validates them)
     bool mf_publish = true;                    // GRAPE_MF_PUBLISH=0: reduce_rows_kernel's staged publication instead of per-workgroup host flags
     unsigned long long seq = 0;
     std::string kernel_log;                    // names of the kernels the last evaluation launched (grape_get_kernel_names)
@@ -587,6 +598,7 @@ static void free_all(grape_ctx *c)
     (void)hipFree(c->d_basis_phi); (void)hipFree(c->d_basis_x0);
     (void)hipFree(c->d_bounds); (void)hipFree(c->d_slope);
     (void)hipFree(c->d_fom_member); (void)hipFree(c->d_fom_rows);
+    (void)hipFree(c->d_risk_rows); (void)hipFree(c->d_risk_p);
     (void)hipFree(c->d_ha); (void)hipFree(c->d_ha_norm); (void)hipFree(c->d_gc); (void)hipFree(c->d_gcn);
     (void)hipFree(c->d_act_a); (void)hipFree(c->d_act_b); (void)hipFree(c->d_act_bf); (void)hipFree(c->d_act_g);
     (void)hipFree(c->d_act_an); (void)hipFree(c->d_act_gn); (void)hipFree(c->d_act_bs); (void)hipFree(c->d_act_bo); (void)hipFree(c->d_act_bn); (void)hipFree(c->d_wrec); (void)hipFree(c->d_props_t);
@@ -1134,6 +1146,8 @@ extern "C" int grape_comm_attach(grape_ctx *c, const grape_comm_id *id, int32_t 
         return fail(c, GRAPE_ERR_INVALID_ARG, "grape_comm_attach: a communicator is already attached");
     if (c->rc_terms > 0)
         return fail(c, GRAPE_ERR_UNSUPPORTED, "grape_comm_attach: a running cost is set (grape_set_running_cost serves contexts without an exchange only)");
+    if (c->risk_beta != 0.0)
+        return fail(c, GRAPE_ERR_UNSUPPORTED, "grape_comm_attach: a risk is set (grape_set_risk serves contexts without a communicator or mailbox exchange only)");
     RcclApi *api = rccl();
     if (!api) return fail(c, GRAPE_ERR_COMM, "grape_comm_attach: " + g_rccl.err);
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1203,6 +1217,8 @@ extern "C" int grape_ipc_attach(grape_ctx *c, const grape_ipc_handle *handles, i
         return fail(c, GRAPE_ERR_INVALID_ARG, "grape_ipc_attach: a communicator is already attached");
     if (c->rc_terms > 0)
         return fail(c, GRAPE_ERR_UNSUPPORTED, "grape_ipc_attach: a running cost is set (grape_set_running_cost serves contexts without an exchange only)");
+    if (c->risk_beta != 0.0)
+        return fail(c, GRAPE_ERR_UNSUPPORTED, "grape_ipc_attach: a risk is set (grape_set_risk serves contexts without a communicator or mailbox exchange only)");
     HIP_TRY(c, hipSetDevice(c->device));
     double *opened[grape::kMaxShards] = {};
     for (int j = 0; j < n_ranks; ++j) {
@@ -1286,6 +1302,7 @@ extern "C" int grape_set_running_cost(grape_ctx *c, int32_t n_terms, const doubl
             why = "StateTransfer / CoherenceTransfer (the sandwich needs a second term) are not served; hold the states as n x m columns under UnitaryGate";
         else if (c->cfg.gradient == GRAPE_GRADIENT_EXACT) why = "gradient = exact is not served (the running cost's gradient is first order in dt)";
         else if (c->cfg.objective != GRAPE_OBJECTIVE_FOM) why = "objective = c1 is not served";
+        else if (c->risk_beta != 0.0) why = "a risk is set: grape_set_risk does not serve a running cost (the members' J_k are not in the member rows)";
         if (why) return fail(c, GRAPE_ERR_UNSUPPORTED, std::string("grape_set_running_cost: ") + why);
         const size_t nr = 2 * (size_t)c->cfg.n * c->m * c->cfg.n_ensemble * n_terms, nw = (size_t)c->cfg.n_slices * n_terms;
         if (int rc = check_finite(c, R, nr, "grape_set_running_cost", "R", 2)) return rc;
@@ -1311,6 +1328,53 @@ extern "C" int grape_set_running_cost(grape_ctx *c, int32_t n_terms, const doubl
 }
 
 static int wait_stream(grape_ctx *c, hipStream_t stream);
+
+// grape_set_risk needs ensemble weights that are >= 0 with a positive sum (p_k is a distribution over the members)
+static int risk_check_weights(const grape_ctx *c, const double *wts, const char *who)
+{
+    double W = 0.0;
+    for (int k = 0; k < c->cfg.n_ensemble; ++k) {
+        if (!(wts[k] >= 0.0) || !std::isfinite(wts[k]))
+            return fail(c, GRAPE_ERR_INVALID_ARG, std::string(who) + ": weight[" + std::to_string(k) + "] = " + std::to_string(wts[k]) +
+                                                      " (a risk needs finite ensemble weights >= 0)");
+        W += wts[k];
+    }
+    if (!(W > 0.0))
+        return fail(c, GRAPE_ERR_INVALID_ARG, std::string(who) + ": the ensemble weights sum to 0 (a risk needs a positive sum)");
+    return GRAPE_OK;
+}
+
+extern "C" int grape_set_risk(grape_ctx *c, double beta)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_set_risk: null context");
+    if (!std::isfinite(beta))
+        return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_risk: beta = " + std::to_string(beta) + " (must be finite; 0 switches the risk off)");
+    if (beta != 0.0) {
+        const char *why = why_exchange_not_served(c);
+        if (!why && c->rc_terms > 0) why = "a running cost is in force (the members' J_k are not in the member rows)";
+        if (why) return fail(c, GRAPE_ERR_UNSUPPORTED, std::string("grape_set_risk: ") + why);
+        if (c->ops_set)
+            if (int rc = risk_check_weights(c, c->h_wts.data(), "grape_set_risk")) return rc;
+    }
+    if (c->is_group) return GRAPE_OK;                        // (switching off what can never be on)
+    if (int rc = drain(c, c)) return rc;
+    c->risk_beta = beta;
+    c->risk_evaluated = false;
+    return GRAPE_OK;
+}
+
+extern "C" int grape_get_risk_weights(grape_ctx *c, double *p)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_get_risk_weights: null context");
+    if (!p) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_get_risk_weights: p is null");
+    if (c->risk_beta == 0.0 || !c->risk_evaluated || !c->d_risk_p)
+        return fail(c, GRAPE_ERR_NOT_READY, "grape_get_risk_weights: no evaluation with a risk in force yet");
+    if (int rc = drain(c, c)) return rc;
+    HIP_TRY(c, hipMemcpy(p, c->d_risk_p, sizeof(double) * (size_t)c->cfg.n_ensemble, hipMemcpyDeviceToHost));
+    return GRAPE_OK;
+}
 
 extern "C" int grape_set_basis(grape_ctx *c, int32_t n_params, int32_t n_bases, const double *phi, const double *x0)
 {
@@ -1455,6 +1519,8 @@ extern "C" int grape_set_operators(grape_ctx *c, const double *A, const double *
         c->evaluated = false;
         return GRAPE_OK;
     }
+    if (c->risk_beta != 0.0)                                 // (before anything is touched: the previous upload stays)
+        if (int rc = risk_check_weights(c, wts, "grape_set_operators")) return rc;
     // an upload that fails half way (allocation of a re-planned workspace, a copy) leaves the context NOT READY -- never with
     // the previous upload's flags over freed or partly rewritten buffers
     c->ops_set = false;
@@ -2158,8 +2224,10 @@ extern "C" int grape_set_operators(grape_ctx *c, const double *A, const double *
     }
     HIP_TRY(c, hipMemcpy(c->d_ops, packed.data(), sizeof(double) * packed.size(), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(c->d_wts, wts, sizeof(double) * E, hipMemcpyHostToDevice));
+    c->h_wts.assign(wts, wts + E);
     c->ops_set = true;
     c->evaluated = false;
+    c->risk_evaluated = false;
     return GRAPE_OK;
 }
 
@@ -2361,10 +2429,32 @@ static int rc_ensure(grape_ctx *c)
     return grow(c, &c->d_rc_xs, &c->rc_xs_bytes, xs, "grape_set_running_cost", "the stored states of the general flow");
 }
 
+// grape_set_risk: the buffers an evaluation needs -- the weights and F_beta of max_batch arrays, and the members' rows where the
+// context has none.  Sized by the configuration alone (a re-plan of the workspace does not touch them); allocated by the first
+// evaluation with a risk in force, kept until grape_destroy.
+static int risk_ensure(grape_ctx *c)
+{
+    const size_t E = (size_t)c->cfg.n_ensemble, B = (size_t)c->B;
+    if (c->family == 0 && !c->d_member_out)
+        if (int rc = grow(c, &c->d_risk_rows, &c->risk_rows_bytes, sizeof(double) * E * (KN(c) + 1) * B, "grape_set_risk", "the members' rows")) return rc;
+    return grow(c, &c->d_risk_p, &c->risk_p_bytes, sizeof(double) * (E + 1) * B, "grape_set_risk", "the risk weights");
+}
+
+// the final launch_reduce of control array `slot` under a risk: its weights and F_beta (DoneSignal::risk_p)
+static grape::DoneSignal with_risk(const grape_ctx *c, grape::DoneSignal d, int slot)
+{
+    if (c->risk_beta != 0.0) {
+        d.risk_beta = c->risk_beta;
+        d.risk_p = c->d_risk_p + (size_t)slot * c->cfg.n_ensemble;
+        d.risk_F = c->d_risk_p + (size_t)c->B * c->cfg.n_ensemble + slot;
+    }
+    return d;
+}
+
 static bool tile_folds_reduce(const grape_ctx *c, int n_x)
 {
     if (c->family != 1 || c->cfg.n_ensemble != 1 || n_x != 1 || c->cfg.gradient == GRAPE_GRADIENT_EXACT || !c->direct_publish ||
-        pen_active(c))                                       // (penalties: the reduce kernel adds them)
+        pen_active(c) || c->risk_beta != 0.0)                // (penalties, a risk: the reduce kernel adds / applies them)
         return false;
     return c->action || c->thin_dpp || (c->unitary && !c->thin && !c->d_costates);
 }
@@ -2416,11 +2506,20 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
                 db.n_total = (int)(Qs * n_x);
                 db.mflags = nullptr;                         // (one flag per workgroup covers ONE array's outputs)
             }
+            c->risk_slot = b;
             const int rc = enqueue_eval(c, d_x + (size_t)b * KN(c), d_fg + (size_t)b * Qs, stream, 1, db);
+            c->risk_slot = 0;
             if (rc) return rc;
         }
         return GRAPE_OK;
     }
+    const bool risk = c->risk_beta != 0.0;
+    if (risk) {
+        const int rc = risk_ensure(c);
+        if (rc) return rc;
+    }
+    // the members' unweighted rows: the context's own, or (family 0 under a risk) the private ones
+    double *const rows = c->d_member_out ? c->d_member_out : (risk ? c->d_risk_rows : nullptr);
     const bool rc_on = c->rc_terms > 0 && c->family == 0;
     if (rc_on) {
         const int rc = rc_ensure(c);
@@ -2432,7 +2531,7 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
     p.props = c->d_props;
     p.states = c->d_states;
     p.costates = c->d_costates;
-    p.member_out = c->d_member_out;
+    p.member_out = rows;
     p.block_out = c->d_block_out;
     p.stamps = c->d_stamps;
     p.xg_scratch = c->d_xg_scratch;
@@ -2467,7 +2566,7 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
     // (penalties: the reduce kernel adds them -- the sweep's own row goes through it; a running cost joins that row behind
     // the sweep, so it cannot be published by the sweep either)
     const bool direct = c->family == 0 && c->NB == 1 && n_x == 1 && !exact && c->direct_publish && !done.probe_out &&
-                        !done.stage_base && !pen_active(c) && !rc_on;
+                        !done.stage_base && !pen_active(c) && !rc_on && !risk;
     const bool fold = !done.stage_base && tile_folds_reduce(c, n_x);
     if (direct) {
         p.direct_dst = done.flag && done.host_out ? done.host_out : d_fg;
@@ -2623,10 +2722,10 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
     if (timed) HIP_TRY(c, hipEventRecord(e1, stream));
     if (exact)
         HIP_TRY(c, grape::launch_reduce(c->d_member_out, c->d_wts, c->d_partial, d_fg, p.E, (int)(KN(c) + 1), c->ksplit,
-                                        stream, with_pen(c, done, d_x)));
+                                        stream, with_risk(c, with_pen(c, done, d_x), c->risk_slot)));
     else if (direct || fold)
         ;                                                    // the sweep / forms kernel has written [G, F] (and the flag)
-    else if (c->family == 0) {
+    else if (c->family == 0 && !risk) {
         if (done.mflags && done.flag && done.host_out && !done.probe_out)
             c->mf_wait = grape::reduce_rows_mflags((int)(KN(c) + 1), n_x);       // (the launch takes the same decision)
         HIP_TRY(c, grape::launch_reduce_rows(c->d_block_out, d_fg, c->NB, (int)(KN(c) + 1), n_x, stream, with_pen(c, done, d_x)));
@@ -2644,11 +2743,13 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
                     db.n_total = (int)(Qs * n_x);
                 }
             }
-            HIP_TRY(c, grape::launch_reduce(c->d_member_out + (size_t)b * p.E * Qs, c->d_wts, c->d_partial,
-                                            d_fg + (size_t)b * Qs, p.E, (int)Qs, c->ksplit, stream, with_pen(c, db, d_x + (size_t)b * KN(c))));
+            HIP_TRY(c, grape::launch_reduce(rows + (size_t)b * p.E * Qs, c->d_wts, c->d_partial,
+                                            d_fg + (size_t)b * Qs, p.E, (int)Qs, c->ksplit, stream,
+                                            with_risk(c, with_pen(c, db, d_x + (size_t)b * KN(c)), c->risk_slot + b)));
         }
     }
     c->evaluated = true;
+    if (risk) c->risk_evaluated = true;
     return GRAPE_OK;
 }
 
@@ -3263,7 +3364,7 @@ extern "C" int grape_eval_observables(grape_ctx *c, const double *x, int32_t n_o
 // ---- ABI v8: the figure of merit without the gradient ----------------------------------------------------------------------
 // fast path of grape_eval_fom: single device, no exchange attached, kernel family 0
 // (a running cost needs the stored propagators: the full evaluation runs and its F is returned)
-static bool fom_fast(const grape_ctx *c) { return !c->is_group && !c->comm && c->ipc_ranks <= 1 && c->family == 0 && c->rc_terms == 0; }
+static bool fom_fast(const grape_ctx *c) { return !c->is_group && !c->comm && c->ipc_ranks <= 1 && c->family == 0 && c->rc_terms == 0 && c->risk_beta == 0.0; }
 
 // The launches of the fast path on the context's stream: x upload, the forward-only kernel (reached through the sweep
 // launchers, SweepParams::fom_only) over the WHOLE ensemble and all n_x arrays at once -- it stores nothing per slice, so
@@ -3347,12 +3448,21 @@ extern "C" int grape_eval_fom(grape_ctx *c, int32_t n_x, const double *x, double
         // fallback: the full evaluation, its F bit for bit; member_F from the member rows, array by array
         if (!member_F)
             return eval_host(c, n_x, x, F, nullptr, "grape_eval_fom");
+        const bool risk = c->risk_beta != 0.0;               // (the rows exist on every context then: the private ones)
         for (grape_ctx *s : c->is_group ? c->sub : std::vector<grape_ctx *>{c})
-            if (!s->d_member_out)
+            if (!s->d_member_out && !risk)
                 return fail(c, GRAPE_ERR_NOT_READY, "grape_eval_fom: member_F needs a context created with GRAPE_FLAG_MEMBER_RESULTS");
         for (int b = 0; b < n_x; ++b) {
             int rc = eval_host(c, 1, x + (size_t)b * kn, F + b, nullptr, "grape_eval_fom");
             if (rc) return rc;
+            if (risk && !c->d_member_out) {                  // the F_k column of the private rows
+                rc = wait_stream(c, c->stream);
+                if (rc) return rc;
+                const size_t Q = KN(c) + 1;
+                HIP_TRY(c, hipMemcpy2D(member_F + (size_t)b * E, sizeof(double), c->d_risk_rows + (Q - 1), sizeof(double) * Q,
+                                       sizeof(double), E, hipMemcpyDeviceToHost));
+                continue;
+            }
             rc = grape_get_member_results(c, member_F + (size_t)b * E, nullptr);
             if (rc) return rc;
         }

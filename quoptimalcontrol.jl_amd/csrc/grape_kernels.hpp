@@ -82,6 +82,14 @@ struct DoneSignal {
     // launcher and never dereferenced on the device; with it launch_copy takes its sizes from the BasisOp, not from `n`.
     // nullptr (every other use of DoneSignal): a plain copy
     const BasisOp *basis = nullptr;
+    // grape_set_risk (beta != 0), launch_reduce only: in front of its sum the launcher runs risk_weights_kernel over the F_k
+    // column of the member rows -- it writes p_k = W w_k exp(beta F_k) / sum_j w_j exp(beta F_j) into risk_p and
+    // F_beta = (W / beta) log((1 / W) sum_k w_k exp(beta F_k)) into risk_F[0] -- and sums the rows with risk_p in place of
+    // its `wts` argument; reduce_few_kernel / reduce_stage2 put risk_F[0] where the summed F would go, in front of the
+    // penalty.  risk_p == nullptr (every other use of DoneSignal): the launcher and its kernels do what they always did
+    double risk_beta = 0.0;
+    double *risk_p = nullptr;                  // device: E weights of this control array
+    double *risk_F = nullptr;                  // device: its F_beta
 };
 constexpr int kMaxMflags = 1000;               // flags behind grape_ctx::h_flag (8 KB: [0] flag, [1] exchange failure, [8..] these)
 // workgroups (= host flags) reduce_rows_mf_kernel publishes with for Q outputs x n_x control arrays; 0: not applicable

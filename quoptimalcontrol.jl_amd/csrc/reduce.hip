@@ -89,6 +89,8 @@ __global__ __launch_bounds__(256) void reduce_stage2(const double *__restrict__ 
 #pragma unroll
     for (int d = kMaxSplit / 2; d >= 1; d >>= 1)
         v += __shfl_xor(v, d, 64);
+    if (done.risk_F && q == Q - 1)                   // grape_set_risk: F_beta in place of sum_k p_k F_k
+        v = done.risk_F[0];
     if (done.pen_x) {                                // the control penalties: once, behind the ensemble sum
         const double pf = blockIdx.x == gridDim.x - 1 ? pen_value<256>(done, done.pen_x) : 0.0;
         if (q < Q - 1)
@@ -262,6 +264,8 @@ __global__ __launch_bounds__(256) void reduce_few_kernel(const double *__restric
     if (q < Q)
         for (int k = 0; k < E; ++k)
             acc = fma(member_out[(size_t)k * Q + q], wts[k], acc);
+    if (done.risk_F && q == Q - 1)                   // grape_set_risk: F_beta in place of sum_k p_k F_k
+        acc = done.risk_F[0];
     if (done.pen_x) {                                // the control penalties: once, behind the ensemble sum
         const double pf = blockIdx.x == gridDim.x - 1 ? pen_value<256>(done, done.pen_x) : 0.0;
         if (q < Q - 1)
@@ -451,9 +455,77 @@ hipError_t launch_ipc_allreduce(const IpcParams &p, hipStream_t stream)
     return hipGetLastError();
 }
 
+// ---- soft worst case over the ensemble (grape_set_risk) ------------------------------------------------------------------
+// One workgroup per control array.  With F_k the last entry of member row k:
+//   W = sum_k w_k,  M = max_{w_k > 0} beta F_k,  S = sum_k w_k exp(beta F_k - M)
+//   p_k = W w_k exp(beta F_k - M) / S   (w_k = 0: exactly 0),   F_beta = (W / beta) (M + log(S / W))
+// Every sum and the maximum: thread-strided partials, then a halving tree through LDS (as pen_value) -- plain stores, no
+// atomics, bitwise reproducible call to call.  A non-finite F_k makes F_beta and every p_k NaN.
+constexpr int kRiskNT = 256;
+template <bool MAX>
+__device__ double risk_tree(double *s, double v)
+{
+    __syncthreads();                                 // (the previous tree's result has been read by everybody)
+    s[threadIdx.x] = v;
+    __syncthreads();
+#pragma unroll
+    for (int h = kRiskNT / 2; h >= 1; h >>= 1) {
+        if ((int)threadIdx.x < h)
+            s[threadIdx.x] = MAX ? fmax(s[threadIdx.x], s[threadIdx.x + h]) : s[threadIdx.x] + s[threadIdx.x + h];
+        __syncthreads();
+    }
+    return s[0];
+}
+
+__global__ __launch_bounds__(kRiskNT) void risk_weights_kernel(const double *__restrict__ member_out, const double *__restrict__ wts,
+                                                               double *__restrict__ p, double *__restrict__ F_beta, int E, int Q,
+                                                               double beta)
+{
+    __shared__ double s_red[kRiskNT];
+    double w_sum = 0.0, m = -INFINITY, bad = 0.0;
+    for (int k = threadIdx.x; k < E; k += kRiskNT) {
+        const double w = wts[k], f = member_out[(size_t)k * Q + (Q - 1)];
+        w_sum += w;
+        if (!isfinite(f))
+            bad = 1.0;
+        else if (w > 0.0)
+            m = fmax(m, beta * f);
+    }
+    const double W = risk_tree<false>(s_red, w_sum);
+    const double M = risk_tree<true>(s_red, m);
+    const bool nan_out = risk_tree<true>(s_red, bad) != 0.0;
+    double s = 0.0;
+    for (int k = threadIdx.x; k < E; k += kRiskNT) {
+        const double w = wts[k];
+        if (w > 0.0 && !nan_out)
+            s += w * exp(beta * member_out[(size_t)k * Q + (Q - 1)] - M);
+    }
+    const double S = risk_tree<false>(s_red, s);
+    const double scale = W / S, qnan = __builtin_nan("");
+    for (int k = threadIdx.x; k < E; k += kRiskNT) {
+        const double w = wts[k];
+        double pk = 0.0;
+        if (nan_out)
+            pk = qnan;
+        else if (w > 0.0)
+            pk = scale * (w * exp(beta * member_out[(size_t)k * Q + (Q - 1)] - M));
+        p[k] = pk;
+    }
+    if (threadIdx.x == 0)
+        F_beta[0] = nan_out ? qnan : (W / beta) * (M + log(S / W));
+}
+
 hipError_t launch_reduce(const double *member_out, const double *wts, double *partial, double *fg,
                          int E, int Q, int ksplit, hipStream_t stream, DoneSignal done)
 {
+    if (done.risk_p) {                               // grape_set_risk: this evaluation's weights in place of the ensemble's
+        GRAPE_LAUNCH(risk_weights_kernel, dim3(1), dim3(kRiskNT), 0, stream, member_out, wts, done.risk_p, done.risk_F, E, Q,
+                     done.risk_beta);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+        wts = done.risk_p;
+    }
     if (ksplit == 1 && E <= 32) {
         GRAPE_LAUNCH(reduce_few_kernel, dim3((Q + 255) / 256), dim3(256), 0, stream, member_out, wts, fg, E, Q, done);
         return hipGetLastError();

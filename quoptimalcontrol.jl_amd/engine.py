@@ -37,7 +37,7 @@ STATUS = {0: "GRAPE_OK", -1: "GRAPE_ERR_INVALID_ARG", -2: "GRAPE_ERR_UNSUPPORTED
 # every symbol include/grape_hip.h declares
 EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_operators", "grape_set_penalties",
            "grape_set_running_cost",
-           "grape_set_basis", "grape_get_controls", "grape_set_bounds",
+           "grape_set_basis", "grape_get_controls", "grape_set_bounds", "grape_set_risk", "grape_get_risk_weights",
            "grape_comm_unique_id", "grape_comm_attach", "grape_ipc_export", "grape_ipc_attach",
            "grape_eval", "grape_eval_device", "grape_eval_batch", "grape_eval_batch_device", "grape_eval_fom", "grape_eval_observables",
            "grape_lbfgs", "grape_lbfgs_get_trace",
@@ -128,6 +128,8 @@ def load_library():
     L.grape_set_basis.argtypes = [vp, i32, i32, vp, vp]
     L.grape_get_controls.argtypes = [vp, vp, vp]
     L.grape_set_bounds.argtypes = [vp, vp, vp]
+    L.grape_set_risk.argtypes = [vp, C.c_double]
+    L.grape_get_risk_weights.argtypes = [vp, vp]
     L.grape_comm_unique_id.argtypes = [C.POINTER(GrapeCommId)]
     L.grape_comm_attach.argtypes = [vp, C.POINTER(GrapeCommId), i32, i32]
     L.grape_ipc_export.argtypes = [vp, i32, vp]
@@ -320,6 +322,21 @@ class GrapeEngine:
         lo, hi = bounds_vectors(lo, hi, self.K)
         self._check(self._lib.grape_set_bounds(self._h, _p(lo), _p(hi)))
         self.bounds = None if lo is None or not np.isfinite(lo).any() else (lo, hi)
+
+    def set_risk(self, beta):
+        """grape_set_risk: the soft worst case over the ensemble in place of its weighted mean.  With W = sum_k w_k every
+        evaluation returns F_beta = (W / beta) log((1 / W) sum_k w_k exp(beta F_k)) and G_beta = sum_k p_k g_k,
+        p_k = W w_k exp(beta F_k) / sum_j w_j exp(beta F_j): beta -> 0 is the mean, beta -> +inf W max_k F_k, beta -> -inf
+        W min_k F_k.  Penalties are added behind it, a basis and bounds stay around it; member_results() and the
+        member_F of fom() stay the unweighted F_k.  beta = 0 (or None) switches it off.  Single-device contexts without
+        a running cost (include/grape_hip.h)."""
+        self._check(self._lib.grape_set_risk(self._h, 0.0 if beta is None else float(beta)))
+
+    def risk_weights(self):
+        """grape_get_risk_weights: p (E,) of the last evaluation under set_risk (array 0 of a batch); sum p = sum w."""
+        p = np.empty(self.E)
+        self._check(self._lib.grape_get_risk_weights(self._h, _p(p)))
+        return p
 
     @property
     def _cols(self):
