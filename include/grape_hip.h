@@ -518,6 +518,49 @@ int grape_eval_fom(grape_ctx *ctx, int32_t n_x, const double *x, double *F, doub
 int grape_eval_observables(grape_ctx *ctx, const double *x, int32_t n_obs, int32_t per_member, const double *O, double *y,
                            double *X_final, double *F);
 
+/* ABI v8 (additive).  The vector-Jacobian product of the trajectory read-out: the backward of grape_eval_observables.  Any
+ * real loss l written on y[s,j,k] = tr(O_kj' X_{k,s}) and on X_final gets its gradient with respect to the controls from
+ * the cotangents the caller (or an autograd framework) computes on the host -- no new kernel, no new setting per loss.
+ *   x, n_obs, per_member, O   exactly as in grape_eval_observables (x is theta / u with a basis / bounds in force; up to
+ *              16 probes; O is (n, m, n_obs), or (n, m, E, n_obs) with per_member = 1)
+ *   ybar       host c128 (N+1, n_obs, E), the layout of y; nullable (NULL means zero)
+ *   Xbar_final host c128 (n, m, E), the layout of X_final; nullable
+ *   G          host f64 (K, N), or (K, M) in parameter mode; required
+ * Cotangent convention: ybar = dl/dRe y + i dl/dIm y, Xbar_final likewise entry by entry -- what torch hands to backward for
+ * a complex output of a real loss.
+ * With the states and propagators of the physical pulse, X_{k,s+1} = P_{k,s} X_{k,s}:
+ *   Lam_{k,N} = Xbar_k + sum_j ybar[N,j,k] O_kj
+ *   Lam_{k,s} = P_{k,s}' Lam_{k,s+1} + sum_j ybar[s,j,k] O_kj          s = N-1 .. 1
+ *   G[c,t]    = sum_k Re tr( Lam_{k,t+1}' (-i dt B_kc) X_{k,t+1} )     t = 0 .. N-1
+ * ybar[0,.,.] is read and validated but contributes nothing (X_0 = Xi).  G holds no ensemble weight, penalty, running cost
+ * or risk: it is the gradient of the caller's loss alone (the caller puts w_k into l).  The gradient is FIRST ORDER in dt,
+ * like the reference's grad_func! and like grape_set_running_cost (the derivative of exp(-i dt H) is taken as -i dt B P);
+ * against central differences of a smooth loss on a smooth pulse the deviation falls by ~4 per 4x in N.  An exact VJP is not
+ * offered.
+ * With grape_set_bounds and / or grape_set_basis in force G is returned in the coordinates of x: the summed physical row
+ * goes through bounds_slope_kernel / basis_project_kernel (the slope of this very evaluation), without the penalty and F
+ * that an evaluation's own tail carries -- so grape_eval_observables and this call agree on coordinates.
+ * The call runs ONE evaluation of x exactly as the context is configured, as grape_eval_observables does, and discards its
+ * [G, F]; behind the sweep of every member block (the running-cost kernels, if any) trajectory_vjp_kernel reads the stored
+ * propagators -- one workgroup per member, one lane per time chunk, one pair of backward walks whatever n_obs is -- and
+ * vjp_sum_kernel adds the members' rows in a tree fixed by the members' ensemble indices (groups of 32 consecutive members
+ * in member order, then the groups in order).  Blocking, ordered behind an in-flight grape_eval_device;
+ * afterwards grape_get_kernel_names includes the two kernels.  An eval -> vjp -> eval sequence returns the first
+ * evaluation's bits; results are bitwise reproducible call to call; a member-chunked context returns the unchunked
+ * context's bits; a standing running cost, penalties or risk do not change G.  The whole ybar is uploaded per call.
+ * Served: kernel family 0 (n = 2, 3, 4), GRAPE_UNITARY_GATE with any m (kets included), Hermitian and non-Hermitian
+ * generators, both variants, gradient = 0 and objective = 0, single-device contexts without communicator or mailbox --
+ * member-chunked contexts, max_batch > 1 (the call takes one array) and forced slices_per_lane / waves_per_member included.
+ * Refused before anything runs, GRAPE_ERR_UNSUPPORTED with the reason in the message: n = 1 and n >= 5 ("dimension"),
+ * StateTransfer / CoherenceTransfer ("StateTransfer": the sandwich needs a second term), gradient = exact or objective = c1
+ * ("exact"), multi-device contexts ("multi-device"), an attached communicator or mailbox ("communicator").
+ * GRAPE_ERR_INVALID_ARG: null x or G; ybar and Xbar_final both NULL; n_obs outside 0..16; n_obs = 0 with a non-NULL ybar;
+ * n_obs > 0 with a NULL O; per_member other than 0 or 1; a non-finite entry of O, ybar or Xbar_final ("not finite").  The
+ * context's refusals are checked first.  Before grape_set_operators: GRAPE_ERR_NOT_READY.  After any refusal the context
+ * evaluates exactly as before.  Non-finite x propagates NaN. */
+int grape_eval_vjp(grape_ctx *ctx, const double *x, int32_t n_obs, int32_t per_member, const double *O, const double *ybar,
+                   const double *Xbar_final, double *G);
+
 /* Device-resident L-BFGS: stands in for
  *     Optim.optimize(Optim.only_fg!(topt), x0, Optim.LBFGS(), optim_options)       src/solve.jl:138, :244
  * with x, g, the (s, y) history and the line-search trial points kept on the GPU; per evaluation the host

@@ -201,6 +201,22 @@ struct grape_ctx {
     double2 *d_obs_y = nullptr;                // (N + 1, n_obs, E)
     double2 *d_obs_xf = nullptr;               // (n, m, E)
     size_t obs_O_bytes = 0, obs_y_bytes = 0, obs_xf_bytes = 0;
+    // grape_eval_vjp (vjp.hip): behind the sweep (the running-cost kernels, the read-out) of every member block of ONE
+    // evaluation, trajectory_vjp_kernel pulls the caller's cotangents back along the stored propagators and vjp_sum_kernel
+    // adds the members' rows group by group into d_vjp_part and, behind the last block, the groups into d_vjp_g.  vjp_on is set
+    // by the entry point around that evaluation only; the buffers are
+    // allocated by the first call that needs them and only ever grow.  The members' rows and the general flow's states use
+    // the running cost's buffers (rc_ensure): its kernels of the same member block are done with them, in stream order.
+    bool vjp_on = false;
+    int vjp_n = 0, vjp_per_member = 0;
+    bool vjp_has_y = false, vjp_has_x = false;
+    double2 *d_vjp_O = nullptr;                // the probes of the call
+    double2 *d_vjp_ybar = nullptr;             // (N + 1, n_obs, E)
+    double2 *d_vjp_xbar = nullptr;             // (n, m, E)
+    double *d_vjp_part = nullptr;              // (K N, groups of 32 members): the members' rows summed group by group
+    double *d_vjp_g = nullptr;                 // [the summed physical row (K N) | 0]: what the slope / projection tail reads
+    double *d_vjp_out = nullptr;               // [G in the coordinates of x (K M) | 0] behind that tail
+    size_t vjp_O_bytes = 0, vjp_ybar_bytes = 0, vjp_xbar_bytes = 0, vjp_part_bytes = 0, vjp_g_bytes = 0, vjp_out_bytes = 0;
     // grape_set_basis ("parameter mode"): the entry points take theta (K, M) and return G_theta; basis_expand_kernel writes the
     // physical controls into d_x in front of the evaluation, basis_project_kernel folds the complete summed rows in d_fg behind
     // it (basis.hip).  Kept by the context the caller holds (a group: device buffers on its first device); shards never see it.
@@ -595,6 +611,7 @@ static void free_all(grape_ctx *c)
     (void)hipFree(c->d_pen_w);
     (void)hipFree(c->d_rc_R); (void)hipFree(c->d_rc_rho); (void)hipFree(c->d_rc_xs); (void)hipFree(c->d_rc_rows);
     (void)hipFree(c->d_obs_O); (void)hipFree(c->d_obs_y); (void)hipFree(c->d_obs_xf);
+    (void)hipFree(c->d_vjp_O); (void)hipFree(c->d_vjp_ybar); (void)hipFree(c->d_vjp_xbar); (void)hipFree(c->d_vjp_part); (void)hipFree(c->d_vjp_g); (void)hipFree(c->d_vjp_out);
     (void)hipFree(c->d_basis_phi); (void)hipFree(c->d_basis_x0);
     (void)hipFree(c->d_bounds); (void)hipFree(c->d_slope);
     (void)hipFree(c->d_fom_member); (void)hipFree(c->d_fom_rows);
@@ -2525,6 +2542,10 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
         const int rc = rc_ensure(c);
         if (rc) return rc;
     }
+    if (c->vjp_on) {                                         // (the rows, and the states of the general flow)
+        const int rc = rc_ensure(c);
+        if (rc) return rc;
+    }
     KernelLogScope log_scope(&c->kernel_log);
     c->mf_wait = 0;
     SweepParams p = sweep_params(c, d_x, n_x);
@@ -2616,6 +2637,29 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
                 o.obs_y = c->obs_want_y ? c->d_obs_y : nullptr;
                 o.obs_xf = c->obs_want_xf ? c->d_obs_xf : nullptr;
                 HIP_TRY(c, launch_small_family(c, sand, mode, o, stream));
+            }
+            if (c->vjp_on) {                                 // grape_eval_vjp: the cotangents of these members, pulled back
+                SweepParams v = q;
+                v.vjp_only = 1;
+                v.vjp_n = c->vjp_has_y ? c->vjp_n : 0;
+                v.vjp_m = c->m;
+                v.vjp_per_member = c->vjp_per_member;
+                v.vjp_unitary = c->unitary ? 1 : 0;
+                v.vjp_CH = c->CH;
+                v.vjp_Etot = c->cfg.n_ensemble;
+                v.vjp_E0 = lo;
+                v.vjp_O = c->d_vjp_O;
+                v.vjp_ybar = c->vjp_has_y ? c->d_vjp_ybar : nullptr;
+                v.vjp_xbar = c->vjp_has_x ? c->d_vjp_xbar : nullptr;
+                v.vjp_xs = c->d_rc_xs;
+                v.vjp_rows = c->d_rc_rows;
+                v.vjp_part = c->d_vjp_part;
+                v.vjp_G = c->d_vjp_g;
+                HIP_TRY(c, launch_small_family(c, 0, mode, v, stream));
+                if (lo + cnt == c->cfg.n_ensemble) {         // behind the last block: the groups' sums into the row
+                    v.vjp_only = 2;
+                    HIP_TRY(c, launch_small_family(c, 0, mode, v, stream));
+                }
             }
             if (exact) {                                     // exact gradient + objective from the stored trajectory
                 grape::ExactParams xq{};
@@ -3358,6 +3402,88 @@ extern "C" int grape_eval_observables(grape_ctx *c, const double *x, int32_t n_o
     if (rc) return rc;
     if (want_y) HIP_TRY(c, hipMemcpy(y, c->d_obs_y, sizeof(double2) * (N + 1) * (size_t)n_obs * E, hipMemcpyDeviceToHost));
     if (X_final) HIP_TRY(c, hipMemcpy(X_final, c->d_obs_xf, sizeof(double2) * n * m * E, hipMemcpyDeviceToHost));
+    return GRAPE_OK;
+}
+
+// ---- grape_eval_vjp: one evaluation + the pull-back of the caller's cotangents along its trajectory ---------------------------
+extern "C" int grape_eval_vjp(grape_ctx *c, const double *x, int32_t n_obs, int32_t per_member, const double *O,
+                              const double *ybar, const double *Xbar_final, double *G)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp: null context");
+    // what the context cannot serve first, as the header lists it; then the arguments
+    const char *who = "grape_eval_vjp", *why = why_exchange_not_served(c);
+    if (why) {}
+    else if (c->family != 0) why = "the operator dimension must be 2, 3 or 4 (the sweeps that leave every propagator in the workspace)";
+    else if (c->cfg.sys_type != GRAPE_UNITARY_GATE) why = "StateTransfer / CoherenceTransfer are not served (the sandwich needs a second term)";
+    else if (c->cfg.gradient == GRAPE_GRADIENT_EXACT) why = "gradient = exact is not served";
+    else if (c->cfg.objective != GRAPE_OBJECTIVE_FOM) why = "objective = c1 (the exact objective) is not served";
+    if (why) return fail(c, GRAPE_ERR_UNSUPPORTED, std::string("grape_eval_vjp: ") + why);
+    if (!x) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp: x is null");
+    if (!G) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp: G is null");
+    if (!ybar && !Xbar_final) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp: ybar and Xbar_final are both null");
+    if (n_obs < 0 || n_obs > 16)
+        return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp: n_obs = " + std::to_string(n_obs) + " (must be in 0..16)");
+    if (n_obs == 0 && ybar) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp: n_obs = 0 with a non-null ybar");
+    if (n_obs > 0 && !O) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp: n_obs > 0 with a null O");
+    if (per_member != 0 && per_member != 1)
+        return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp: per_member = " + std::to_string(per_member) + " (must be 0 or 1)");
+    if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, "grape_eval_vjp: operators not set");
+    const size_t n = (size_t)c->cfg.n, m = (size_t)c->m, E = (size_t)c->cfg.n_ensemble, N = (size_t)c->cfg.n_slices;
+    const size_t n_O = n * m * (per_member ? E : 1) * (size_t)n_obs, n_y = (N + 1) * (size_t)n_obs * E, n_X = n * m * E;
+    int rc = check_finite(c, O, 2 * n_O, who, "O", 2);
+    if (rc) return rc;
+    if (ybar) rc = check_finite(c, ybar, 2 * n_y, who, "ybar", 2);
+    if (rc) return rc;
+    if (Xbar_final) rc = check_finite(c, Xbar_final, 2 * n_X, who, "Xbar_final", 2);
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t kn = KN(c), kp = KP(c);
+    // (the buffers belong to this entry point alone, which is blocking: no launch in flight reads them)
+    if (ybar) {
+        rc = grow(c, &c->d_vjp_O, &c->vjp_O_bytes, sizeof(double2) * n_O, who, "the probes");
+        if (rc) return rc;
+        rc = grow(c, &c->d_vjp_ybar, &c->vjp_ybar_bytes, sizeof(double2) * n_y, who, "the cotangents of the expectation values");
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpy(c->d_vjp_O, O, sizeof(double2) * n_O, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(c->d_vjp_ybar, ybar, sizeof(double2) * n_y, hipMemcpyHostToDevice));
+    }
+    if (Xbar_final) {
+        rc = grow(c, &c->d_vjp_xbar, &c->vjp_xbar_bytes, sizeof(double2) * n_X, who, "the cotangents of the final states");
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpy(c->d_vjp_xbar, Xbar_final, sizeof(double2) * n_X, hipMemcpyHostToDevice));
+    }
+    rc = grow(c, &c->d_vjp_part, &c->vjp_part_bytes, sizeof(double) * kn * ((E + grape::kVjpGroup - 1) / grape::kVjpGroup), who, "the groups' rows");
+    if (rc) return rc;
+    rc = grow(c, &c->d_vjp_g, &c->vjp_g_bytes, sizeof(double) * (kn + 1), who, "the summed row");
+    if (rc) return rc;
+    rc = grow(c, &c->d_vjp_out, &c->vjp_out_bytes, sizeof(double) * (kp + 1), who, "the projected row");
+    if (rc) return rc;
+    const double zero = 0.0;                                 // (where the tail expects F)
+    HIP_TRY(c, hipMemcpy(c->d_vjp_g + kn, &zero, sizeof(double), hipMemcpyHostToDevice));
+    c->vjp_n = n_obs;
+    c->vjp_per_member = per_member;
+    c->vjp_has_y = ybar != nullptr;
+    c->vjp_has_x = Xbar_final != nullptr;
+    c->vjp_on = true;                                        // enqueue_eval's member blocks end in the two kernels of vjp.hip
+    rc = eval_host(c, 1, x, nullptr, nullptr, who);          // (its [G, F] are not wanted)
+    c->vjp_on = false;
+    if (rc) return rc;
+    // the summed physical row -> the coordinates of x: the slope / projection of the evaluation that has just run (its slope
+    // array is in place), without the penalty and F that the evaluation's own tail carries
+    const double *d_res = c->d_vjp_g;
+    if (pulse_map(c)) {
+        KernelLogScope log_scope(&c->kernel_log, true);
+        const grape::BasisOp op = basis_op(c, true, 1);
+        grape::DoneSignal d;
+        d.basis = &op;
+        HIP_TRY(c, grape::launch_copy(c->d_vjp_g, c->d_vjp_out, (int)(kp + 1), c->stream, d));
+        d_res = c->d_vjp_out;
+    }
+    // (the evaluation is published by its own last kernel, or by the sweep itself: the launches above may sit behind that)
+    rc = wait_stream(c, c->stream);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpy(G, d_res, sizeof(double) * kp, hipMemcpyDeviceToHost));
     return GRAPE_OK;
 }
 

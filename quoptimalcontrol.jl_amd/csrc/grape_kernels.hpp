@@ -172,9 +172,32 @@ struct SweepParams {
     const double2 *obs_O;    // the probes, column-major (from member 0 on)
     double2 *obs_y;          // (N + 1, obs_n, obs_Etot) column-major, nullable
     double2 *obs_xf;         // (n, m, obs_Etot) X_N, nullable
+    // grape_eval_vjp (vjp.hip): launch_sweep_small / launch_sweep_pair hand a launch with vjp_only set to
+    // trajectory_vjp_kernel + vjp_sum_kernel INSTEAD of the sweep: behind the sweep of the same members (one control array)
+    // they read the propagators that sweep stored (props, chunk-major with stride vjp_CH), pull the caller's cotangents back
+    // along the trajectory and add the members' gradient rows onto the sums of their groups in vjp_part; vjp_only = 2, once
+    // behind the last member block: vjp_sum_kernel alone, the groups' sums into vjp_G
+    int32_t vjp_only;
+    int32_t vjp_n;           // probes per member, 0..16 (the ybar rows; 0 with vjp_ybar null)
+    int32_t vjp_m;           // state columns m (O, Xbar, X are n x m)
+    int32_t vjp_per_member;  // 0: vjp_O is (n, m, vjp_n), shared; 1: (n, m, vjp_Etot, vjp_n)
+    int32_t vjp_unitary;     // every propagator unitary: states are walked back with P'; 0: stored in vjp_xs
+    int32_t vjp_CH;          // time chunks per member = workspace stride (LT, or LT / 2 behind the pair kernel)
+    int32_t vjp_Etot;        // members of the whole ensemble
+    int32_t vjp_E0;          // this launch's first member: offset into the probes and the cotangents
+    const double2 *vjp_O;    // the probes, column-major (from member 0 on)
+    const double2 *vjp_ybar; // (N + 1, vjp_n, vjp_Etot) column-major, nullable: dl/dRe y + i dl/dIm y
+    const double2 *vjp_xbar; // (n, m, vjp_Etot), nullable: the cotangent of X_N
+    double2 *vjp_xs;         // general flow: X_{t+1} per slice, chunk-major like props with n m elements per slice
+    double *vjp_rows;        // K N per member of this launch: the member's unweighted gradient row
+    double *vjp_part;        // (K N, ceil(vjp_Etot / kVjpGroup)): the rows summed over each group of consecutive members
+    double *vjp_G;           // K N: the groups' sums added up, in group order
 };
 // observe.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::obs_only) only
 hipError_t run_observe(int n, int sandwich, const SweepParams &p, hipStream_t stream);
+// vjp.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::vjp_only) only
+hipError_t run_trajectory_vjp(int n, const SweepParams &p, hipStream_t stream);
+constexpr int kVjpGroup = 32;                  // members per group of vjp_sum_kernel's tree: vjp_part has ceil(E / 32) rows
 // running_cost.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::rc_only) only
 hipError_t run_running_cost(int n, const SweepParams &p, hipStream_t stream);
 // fom_small.hip; reached through launch_sweep_small (pair = false) / launch_sweep_pair (pair = true) only

@@ -621,6 +621,8 @@ hipError_t launch_sweep_small(int n, int sandwich, int mode, const SweepParams &
         return run_running_cost(n, p, stream);
     if (p.obs_only)                                  // grape_eval_observables: the kernel behind the sweep (observe.hip)
         return run_observe(n, sandwich, p, stream);
+    if (p.vjp_only)                                  // grape_eval_vjp: the kernels behind the sweep (vjp.hip)
+        return run_trajectory_vjp(n, p, stream);
     switch (n * 2 + (sandwich ? 1 : 0)) {
     case 4: return launch_ns<2, 0>(mode, p, stream);
     case 5: return launch_ns<2, 1>(mode, p, stream);

@@ -40,6 +40,7 @@ EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_oper
            "grape_set_basis", "grape_get_controls", "grape_set_bounds", "grape_set_risk", "grape_get_risk_weights",
            "grape_comm_unique_id", "grape_comm_attach", "grape_ipc_export", "grape_ipc_attach",
            "grape_eval", "grape_eval_device", "grape_eval_batch", "grape_eval_batch_device", "grape_eval_fom", "grape_eval_observables",
+           "grape_eval_vjp",
            "grape_lbfgs", "grape_lbfgs_get_trace",
            "grape_get_member_results", "grape_get_trajectory",
            "grape_get_kernel_time", "grape_get_kernel_samples", "grape_get_kernel_names", "grape_get_group_timing", "grape_get_phase_stamps",
@@ -140,6 +141,7 @@ def load_library():
     L.grape_eval_batch_device.argtypes = [vp, i32, vp, vp, vp]
     L.grape_eval_fom.argtypes = [vp, i32, vp, vp, vp]
     L.grape_eval_observables.argtypes = [vp, vp, i32, i32, vp, vp, vp, dp]
+    L.grape_eval_vjp.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp]
     L.grape_lbfgs.argtypes = [vp, vp, C.POINTER(GrapeLbfgsOptions), vp, C.POINTER(GrapeLbfgsResult)]
     L.grape_get_member_results.argtypes = [vp, vp, vp]
     L.grape_get_trajectory.argtypes = [vp, i32, vp, vp, vp]
@@ -561,6 +563,51 @@ class GrapeEngine:
         if want_F:
             out.append(F.value)
         return out[0] if len(out) == 1 else tuple(out)
+
+    def observe_vjp(self, x, ops, ybar=None, xbar_final=None, per_member=False):
+        """grape_eval_vjp: the vector-Jacobian product of observe() -- the gradient with respect to x (K,N) (theta / u with a
+        basis / bounds in force) of any real loss l written on observe's returns, from its cotangents
+        ybar (E, n_obs, N+1) = dl/dRe y + i dl/dIm y and xbar_final (E, n, m) likewise (what torch hands to backward); either
+        may be None (zero), not both.  ops as in observe (None with xbar_final alone).  Returns G (K, cols), first order in
+        dt like the running cost's gradient, without ensemble weights, penalties, running cost or risk: the gradient of the
+        caller's loss alone, in the coordinates of x.  n = 2..4, UnitaryGate, single-device contexts (include/grape_hip.h)."""
+        x = np.asarray(x, dtype=np.float64)
+        if x.shape != (self.K, self._cols):
+            raise ValueError(f"x must be ({self.K},{self._cols})")
+        n, m, E, N = self.n, self.m, self.E, self.N
+        if ybar is None and xbar_final is None:
+            raise ValueError("observe_vjp: nothing to pull back (ybar and xbar_final are both None)")
+        if ops is None:
+            if ybar is not None:
+                raise ValueError("observe_vjp: ybar needs the probes it belongs to")
+            n_obs, Of = 0, None
+        else:
+            O = np.asarray(ops, dtype=np.complex128)
+            if not per_member and O.ndim == 2:
+                O = O[None]
+            want = (E, O.shape[1] if O.ndim == 4 else 0, n, m) if per_member else (O.shape[0] if O.ndim == 3 else 0, n, m)
+            if O.shape != want or not 1 <= O.shape[-3] <= 16:
+                raise ValueError(f"observe_vjp: ops must be {'(E, n_obs, n, m)' if per_member else '(n_obs, n, m)'} with "
+                                 f"E = {E}, n = {n}, m = {m} and 1 <= n_obs <= 16")
+            n_obs = O.shape[-3]
+            Of = _cm(np.swapaxes(O, 0, 1) if per_member else O)
+        yb = None
+        if ybar is not None:
+            yb = np.ascontiguousarray(ybar, dtype=np.complex128)
+            if yb.shape != (E, n_obs, N + 1):
+                raise ValueError(f"observe_vjp: ybar must be ({E},{n_obs},{N + 1})")
+        else:
+            n_obs, Of = 0, None                                   # (probes without cotangents: nothing of theirs to pull back)
+        xb = None
+        if xbar_final is not None:
+            xb = np.asarray(xbar_final, dtype=np.complex128)
+            if xb.shape != (E, n, m):
+                raise ValueError(f"observe_vjp: xbar_final must be ({E},{n},{m})")
+            xb = _cm(xb)
+        G = np.empty((self._cols, self.K))
+        xf = np.ascontiguousarray(x.T)
+        self._check(self._lib.grape_eval_vjp(self._h, _p(xf), n_obs, 1 if per_member else 0, _p(Of), _p(yb), _p(xb), _p(G)))
+        return np.ascontiguousarray(G.T)
 
     def eval_device(self, d_x_ptr, d_fg_ptr, stream=0):
         """grape_eval_device with raw device pointers (e.g. torch tensor .data_ptr())."""
