@@ -561,6 +561,43 @@ int grape_eval_observables(grape_ctx *ctx, const double *x, int32_t n_obs, int32
 int grape_eval_vjp(grape_ctx *ctx, const double *x, int32_t n_obs, int32_t per_member, const double *O, const double *ybar,
                    const double *Xbar_final, double *G);
 
+/* ABI v8 (additive).  The device forms of the pair above: every array lives in device memory of the context's GPU, nothing
+ * crosses to the host, nothing is synchronised -- the read-out and the pull-back for a loss that lives on the GPU (a torch
+ * CUDA graph of y, say).  Layouts, the cotangent convention, scope, refusals and argument checks are those of the host forms,
+ * word for word (the messages carry the device forms' names):
+ *   d_x          what grape_eval_device takes: theta / u with a basis / bounds in force
+ *   d_O          c128 (n, m, n_obs), or (n, m, E, n_obs) with per_member = 1
+ *   d_y, d_ybar  c128 (N+1, n_obs, E)            d_X_final, d_Xbar_final  c128 (n, m, E)
+ *   d_G          f64 (K, N), or (K, M) in parameter mode; required
+ *   d_fg         f64 [K cols + 1], nullable: the evaluation's own [G, F], exactly what grape_eval_device writes for d_x -- a
+ *                by-product of the read-out (cols = N, or M in parameter mode)
+ * Both calls are asynchronous on `stream`, like grape_eval_device, under the same rules: one workspace per context; later
+ * blocking calls are ordered behind the call; two device calls on different streams are ordered by the caller; the caller
+ * keeps every device array alive until the stream has passed the call.  The kernels write straight into d_y, d_X_final and
+ * d_G and read d_O, d_ybar and d_Xbar_final in place: no staging copy is made.  The context's own scratch (the members' rows,
+ * the groups' sums, the summed row under a pulse map) grows only behind a pending device call.
+ * NON-FINITE ENTRIES OF THE DEVICE ARRAYS ARE NOT CHECKED -- that would take a synchronisation.  A NaN in d_O, d_ybar or
+ * d_Xbar_final propagates into y / G, the status stays GRAPE_OK, and the context evaluates as before afterwards.  Everything
+ * else the host forms validate is validated the same way, the context's refusals first.
+ * Results are bit for bit those of the host forms on the same values.  Two instances of each kernel serve the device forms:
+ * the host forms' (observe_kernel, trajectory_vjp_kernel), and a staged one (observe_staged_kernel,
+ * trajectory_vjp_staged_kernel) that passes a member's contiguous y / ybar block through LDS so that the global accesses are
+ * lane-contiguous; same arithmetic, same order, same bits.  The library picks by the probe count where the block fits the
+ * workgroup's LDS; GRAPE_TRAJ_STAGED=0 / 1 forces the choice, grape_get_kernel_names tells which ran.
+ * Reuse: grape_eval_vjp_device with d_x = NULL pulls back along "the trajectory of the last grape_eval_observables_device or
+ * grape_eval_vjp_device call on this context": no sweep is launched, only trajectory_vjp_kernel, vjp_sum_kernel and the slope /
+ * projection tail run, on the propagators and the slope array that evaluation left in the workspace.  The result is bit for
+ * bit that of the same call with d_x given.  The context keeps a "trajectory valid" flag: set at the end of a successful call
+ * of either device form with a non-NULL d_x on a context that is not member-chunked; cleared by every other entry point that
+ * evaluates or changes a setting (grape_eval*, grape_eval_fom, grape_lbfgs, the host forms, grape_get_controls, every
+ * grape_set_*, grape_comm_attach / grape_ipc_attach) and by any failed call of the device forms.  d_x = NULL with the flag
+ * clear: GRAPE_ERR_NOT_READY, the message names the reason; a member-chunked context always answers GRAPE_ERR_NOT_READY
+ * ("member_chunk": its workspace holds one block of members only). */
+int grape_eval_observables_device(grape_ctx *ctx, const double *d_x, int32_t n_obs, int32_t per_member, const double *d_O,
+                                  double *d_y, double *d_X_final, double *d_fg, void *stream);
+int grape_eval_vjp_device(grape_ctx *ctx, const double *d_x, int32_t n_obs, int32_t per_member, const double *d_O,
+                          const double *d_ybar, const double *d_Xbar_final, double *d_G, void *stream);
+
 /* Device-resident L-BFGS: stands in for
  *     Optim.optimize(Optim.only_fg!(topt), x0, Optim.LBFGS(), optim_options)       src/solve.jl:138, :244
  * with x, g, the (s, y) history and the line-search trial points kept on the GPU; per evaluation the host

@@ -11,6 +11,10 @@ torch is imported here and nowhere else in the package: `import quoptimalcontrol
     y, X_final = autograd.trajectory(eng, x, ops)
     loss = -torch.log(1 - y[0, 0].abs() ** 2).sum()          # a log-barrier on a population
     loss.backward()                                         # x.grad: first order in dt, like the running cost's gradient
+
+trajectory_device is the same for a workflow that lives on the GPU: x, y, X_final, the loss and x.grad are CUDA tensors on the
+engine's device, the read-out and the pull-back run on torch's current stream (GrapeEngine.observe_device /
+observe_vjp_device) and nothing crosses to the host.
 """
 import numpy as np
 import torch
@@ -54,3 +58,80 @@ def trajectory(engine, x, ops, per_member=False, final=True):
         raise ValueError("trajectory: at least one probe is needed (GrapeEngine.observe(final=True) gives X_final alone)")
     ops = np.array(ops.detach().numpy() if isinstance(ops, torch.Tensor) else ops, dtype=np.complex128, copy=True)
     return _Trajectory.apply(x, engine, ops, bool(per_member), bool(final))
+
+
+def _dev_probes(ops, per_member):
+    """(n_obs, n, m) / (E, n_obs, n, m) -> the library's column-major (n, m, [E,] n_obs), on the GPU"""
+    return (ops.permute(1, 0, 3, 2) if per_member else ops.transpose(-1, -2)).contiguous()
+
+
+class _TrajectoryDevice(torch.autograd.Function):
+    """_Trajectory on device memory.  The backward pulls back along the trajectory the forward left in the engine's workspace
+    (d_x = 0, no second sweep) when reuse is set and engine.calls says that nothing has touched the engine since; otherwise,
+    and when the library finds the trajectory gone after all, it runs with the saved x."""
+
+    @staticmethod
+    def forward(ctx, x, engine, ops, per_member, final, reuse):
+        E, n, m, N = engine.E, engine.n, engine.m, engine.N
+        n_obs = ops.shape[1] if per_member else ops.shape[0]
+        xf = x.detach().t().contiguous()                     # (K, cols) column-major
+        Of = _dev_probes(ops, per_member)
+        y = torch.empty((E, n_obs, N + 1), dtype=torch.complex128, device=x.device)
+        Xf = torch.empty((E, m, n), dtype=torch.complex128, device=x.device) if final else None
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        engine.observe_device(xf.data_ptr(), n_obs, per_member, Of.data_ptr(), y.data_ptr(), Xf.data_ptr() if final else 0, 0, stream)
+        ctx.engine, ctx.per_member, ctx.n_obs, ctx.reuse = engine, per_member, n_obs, reuse
+        ctx.xf, ctx.Of, ctx.stamp = xf, Of, engine.calls
+        ctx.set_materialize_grads(False)
+        if final:
+            return y, Xf.transpose(-1, -2)
+        return y
+
+    @staticmethod
+    def backward(ctx, ybar, xbar=None):
+        if ybar is None and xbar is None:
+            return None, None, None, None, None, None
+        eng = ctx.engine
+        yb = None if ybar is None else ybar.detach().resolve_conj().contiguous()
+        xb = None if xbar is None else xbar.detach().resolve_conj().transpose(-1, -2).contiguous()
+        G = torch.empty_like(ctx.xf)
+        stream = torch.cuda.current_stream(G.device).cuda_stream
+        n_obs, Of = (ctx.n_obs, ctx.Of.data_ptr()) if yb is not None else (0, 0)
+        args = (n_obs, ctx.per_member, Of, 0 if yb is None else yb.data_ptr(), 0 if xb is None else xb.data_ptr(), G.data_ptr(), stream)
+        done = False
+        if ctx.reuse and eng.calls == ctx.stamp:
+            try:
+                eng.observe_vjp_device(0, *args)
+                done = True
+            except Exception as exc:                         # (NOT_READY: a call that bypassed the engine's counter, a member chunk)
+                if getattr(exc, "status", None) != -5:
+                    raise
+        if not done:
+            eng.observe_vjp_device(ctx.xf.data_ptr(), *args)
+        return G.t(), None, None, None, None, None
+
+
+def trajectory_device(engine, x, ops, per_member=False, final=True, reuse=True):
+    """trajectory on the GPU: x is a CUDA float64 tensor on the engine's device, of the shape engine.eval takes; returns CUDA
+    complex128 y (E, n_obs, N+1) and -- final=True -- X_final (E, n, m), differentiable with respect to x.  ops: (n_obs, n, m),
+    or (E, n_obs, n, m) with per_member=True, a tensor or anything numpy converts; not differentiated.  Forward and backward
+    run on torch's current stream; nothing crosses to the host.  reuse=True lets a backward that directly follows its forward
+    skip the second sweep (same bits)."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float64:
+        raise TypeError("trajectory_device: x must be a CUDA float64 tensor")
+    cols = getattr(engine, "n_params", 0) or engine.N
+    if tuple(x.shape) != (engine.K, cols):
+        raise ValueError(f"trajectory_device: x must be ({engine.K},{cols})")
+    if ops is None:
+        raise ValueError("trajectory_device: at least one probe is needed")
+    if not isinstance(ops, torch.Tensor):
+        ops = torch.from_numpy(np.array(ops, dtype=np.complex128, copy=True))
+    want = (engine.E, ops.shape[1] if ops.ndim == 4 else 0, engine.n, engine.m) if per_member else \
+        (ops.shape[0] if ops.ndim == 3 else 0, engine.n, engine.m)
+    if tuple(ops.shape) != want or not 1 <= ops.shape[-3] <= 16:
+        raise ValueError(f"trajectory_device: ops must be {'(E, n_obs, n, m)' if per_member else '(n_obs, n, m)'} with "
+                         f"E = {engine.E}, n = {engine.n}, m = {engine.m} and 1 <= n_obs <= 16")
+    if x.device.type != "cuda":
+        raise TypeError("trajectory_device: x must be a CUDA float64 tensor")
+    ops = ops.detach().to(device=x.device, dtype=torch.complex128)
+    return _TrajectoryDevice.apply(x, engine, ops, bool(per_member), bool(final), bool(reuse))

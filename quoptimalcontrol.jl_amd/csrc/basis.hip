@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void basis_project_kernel(const BasisOp op, co
             part += __shfl_xor(part, d, 64);
         if (lane == 0) {
             out[(size_t)b * Qm + o] = part;
-            if (o == 0)
+            if (o == 0 && !op.no_f)
                 out[(size_t)b * Qm + KM] = rows[(size_t)b * Qn + Qn - 1];
         }
     }
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void bounds_saturate_kernel(const BasisOp op, 
 __global__ __launch_bounds__(256) void bounds_slope_kernel(const BasisOp op, const double *__restrict__ rows,
                                                            double *__restrict__ out, DoneSignal done)
 {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, KN = (size_t)op.K * op.N, Q = KN + 1;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, KN = (size_t)op.K * op.N, Q = KN + (op.no_f ? 0 : 1);
     if (i < Q * op.n_x) {
         const size_t b = i / Q, j = i % Q;
         out[i] = j < KN ? rows[i] * op.slope[b * KN + j] : rows[i];
@@ -152,9 +152,11 @@ hipError_t launch_basis(const BasisOp &op, const double *src, double *dst, hipSt
         return hipErrorInvalidValue;
     if (op.bounded && (!op.lo || !op.hi || !op.slope))
         return hipErrorInvalidValue;
+    if (op.no_f && (!op.project || op.n_x != 1))
+        return hipErrorInvalidValue;
     done.basis = nullptr;                                    // (a host address: nothing for the device)
     if (op.M == 0) {
-        const size_t n = ((size_t)op.K * op.N + (op.project ? 1 : 0)) * op.n_x;
+        const size_t n = ((size_t)op.K * op.N + (op.project && !op.no_f ? 1 : 0)) * op.n_x;
         if (n > 0x7fffff00u)
             return hipErrorInvalidValue;
         if (!op.project) {

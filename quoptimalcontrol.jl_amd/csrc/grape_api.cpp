@@ -217,6 +217,19 @@ struct grape_ctx {
     double *d_vjp_g = nullptr;                 // [the summed physical row (K N) | 0]: what the slope / projection tail reads
     double *d_vjp_out = nullptr;               // [G in the coordinates of x (K M) | 0] behind that tail
     size_t vjp_O_bytes = 0, vjp_ybar_bytes = 0, vjp_xbar_bytes = 0, vjp_part_bytes = 0, vjp_g_bytes = 0, vjp_out_bytes = 0;
+    // What the read-out / pull-back kernels of the evaluation that obs_on / vjp_on announce read and write: the buffers above
+    // (the host forms) or the caller's own device arrays (grape_eval_observables_device / grape_eval_vjp_device: nothing is
+    // staged).  *_staged: bytes of the member block's LDS image, > 0 selects the staged instance (traj_staged_bytes).
+    const double2 *obs_O_call = nullptr, *vjp_O_call = nullptr, *vjp_ybar_call = nullptr, *vjp_xbar_call = nullptr;
+    double2 *obs_y_call = nullptr, *obs_xf_call = nullptr;
+    double *vjp_G_call = nullptr;              // K N: the summed physical row (d_vjp_g, or the caller's G without a pulse map)
+    int obs_staged = 0, vjp_staged = 0;
+    int lds_cap = 0;                           // LDS bytes a workgroup of this device may hold (queried by the first device form)
+    // The workspace holds the complete trajectory (every member's propagators, and the slope array of a pulse map) of the last
+    // device form: grape_eval_vjp_device may pull back along it without a sweep (d_x == NULL).  Set by a successful device form
+    // that ran an evaluation on a context that is not member-chunked; cleared by everything else that evaluates or changes a
+    // setting, and by every failed call of the device forms.
+    bool traj_valid = false;
     // grape_set_basis ("parameter mode"): the entry points take theta (K, M) and return G_theta; basis_expand_kernel writes the
     // physical controls into d_x in front of the evaluation, basis_project_kernel folds the complete summed rows in d_fg behind
     // it (basis.hip).  Kept by the context the caller holds (a group: device buffers on its first device); shards never see it.
@@ -1155,6 +1168,7 @@ extern "C" int grape_comm_attach(grape_ctx *c, const grape_comm_id *id, int32_t 
 {
     DeviceGuard guard;
     if (!c) return GRAPE_ERR_INVALID_ARG;
+    c->traj_valid = false;                                   // (grape_eval_vjp_device's reuse)
     if (!id || n_ranks < 1 || rank < 0 || rank >= n_ranks)
         return fail(c, GRAPE_ERR_INVALID_ARG, "grape_comm_attach: bad rank / n_ranks / id");
     if (c->is_group)
@@ -1226,6 +1240,7 @@ extern "C" int grape_ipc_attach(grape_ctx *c, const grape_ipc_handle *handles, i
 {
     DeviceGuard guard;
     if (!c) return GRAPE_ERR_INVALID_ARG;
+    c->traj_valid = false;                                   // (grape_eval_vjp_device's reuse)
     if (!handles || n_ranks < 1 || n_ranks > grape::kMaxShards || rank < 0 || rank >= n_ranks)
         return fail(c, GRAPE_ERR_INVALID_ARG, "grape_ipc_attach: bad rank / n_ranks / handles");
     if (!c->d_mbox || c->ipc_alloc_ranks != n_ranks)
@@ -1277,6 +1292,7 @@ extern "C" int grape_set_penalties(grape_ctx *c, const double *amp_w, const doub
 {
     DeviceGuard guard;
     if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_set_penalties: null context");
+    c->traj_valid = false;                                   // (grape_eval_vjp_device's reuse)
     const int K = c->cfg.n_controls;
     std::vector<double> w(2 * (size_t)K, 0.0);
     bool on = false;
@@ -1307,6 +1323,7 @@ extern "C" int grape_set_running_cost(grape_ctx *c, int32_t n_terms, const doubl
 {
     DeviceGuard guard;
     if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_set_running_cost: null context");
+    c->traj_valid = false;                                   // (grape_eval_vjp_device's reuse)
     const bool off = n_terms == 0 || !R;
     if (!off) {
         if (n_terms < 0 || n_terms > 4)
@@ -1365,6 +1382,7 @@ extern "C" int grape_set_risk(grape_ctx *c, double beta)
 {
     DeviceGuard guard;
     if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_set_risk: null context");
+    c->traj_valid = false;                                   // (grape_eval_vjp_device's reuse)
     if (!std::isfinite(beta))
         return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_risk: beta = " + std::to_string(beta) + " (must be finite; 0 switches the risk off)");
     if (beta != 0.0) {
@@ -1397,6 +1415,7 @@ extern "C" int grape_set_basis(grape_ctx *c, int32_t n_params, int32_t n_bases, 
 {
     DeviceGuard guard;
     if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_set_basis: null context");
+    c->traj_valid = false;                                   // (grape_eval_vjp_device's reuse)
     const int K = c->cfg.n_controls, N = c->cfg.n_slices;
     const bool off = !phi || n_params == 0;
     if (!off) {
@@ -1427,6 +1446,7 @@ extern "C" int grape_set_bounds(grape_ctx *c, const double *lo, const double *hi
 {
     DeviceGuard guard;
     if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_set_bounds: null context");
+    c->traj_valid = false;                                   // (grape_eval_vjp_device's reuse)
     const int K = c->cfg.n_controls;
     if (!lo != !hi) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_bounds: lo and hi must both be given, or both be null");
     bool on = false;
@@ -1479,6 +1499,7 @@ extern "C" int grape_get_controls(grape_ctx *c, const double *theta, double *x)
 {
     DeviceGuard guard;
     if (!c) return GRAPE_ERR_INVALID_ARG;
+    c->traj_valid = false;                                   // (grape_eval_vjp_device's reuse)
     if (!theta || !x) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_get_controls: null argument");
     if (!pulse_map(c)) {                                     // no basis, no bounds: the parameters ARE the controls
         std::memmove(x, theta, sizeof(double) * KN(c));
@@ -1518,6 +1539,7 @@ extern "C" int grape_set_operators(grape_ctx *c, const double *A, const double *
                                    const double *Xt, const double *wts)
 {
     if (!c) return GRAPE_ERR_INVALID_ARG;
+    c->traj_valid = false;                                   // (grape_eval_vjp_device's reuse)
     if (!A || !B || !Xi || !Xt || !wts)
         return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_operators: null argument");
     if (c->is_group) {                                       // hand every device its contiguous member block
@@ -2506,6 +2528,30 @@ static int fold_events(grape_ctx *c, uint64_t count)
     return GRAPE_OK;
 }
 
+// grape_eval_vjp: the launch of trajectory_vjp_kernel + vjp_sum_kernel for the members from `lo` on that `q` sweeps (or swept:
+// grape_eval_vjp_device's reuse)
+static SweepParams vjp_params(const grape_ctx *c, const SweepParams &q, int lo)
+{
+    SweepParams v = q;
+    v.vjp_only = 1;
+    v.vjp_n = c->vjp_has_y ? c->vjp_n : 0;
+    v.vjp_m = c->m;
+    v.vjp_per_member = c->vjp_per_member;
+    v.vjp_unitary = c->unitary ? 1 : 0;
+    v.vjp_CH = c->CH;
+    v.vjp_Etot = c->cfg.n_ensemble;
+    v.vjp_E0 = lo;
+    v.vjp_O = c->vjp_O_call;
+    v.vjp_ybar = c->vjp_has_y ? c->vjp_ybar_call : nullptr;
+    v.vjp_xbar = c->vjp_has_x ? c->vjp_xbar_call : nullptr;
+    v.vjp_xs = c->d_rc_xs;
+    v.vjp_rows = c->d_rc_rows;
+    v.vjp_part = c->d_vjp_part;
+    v.vjp_G = c->vjp_G_call;
+    v.vjp_staged = c->vjp_has_y ? c->vjp_staged : 0;
+    return v;
+}
+
 // one shard: sweep kernel(s) + the on-device ensemble reduction into d_fg; nothing is synchronised
 static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream_t stream, int n_x = 1,
                         grape::DoneSignal done = grape::DoneSignal())
@@ -2530,6 +2576,7 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
         }
         return GRAPE_OK;
     }
+    c->traj_valid = false;                                   // (the device forms set it behind their own evaluation)
     const bool risk = c->risk_beta != 0.0;
     if (risk) {
         const int rc = risk_ensure(c);
@@ -2633,28 +2680,14 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
                 o.obs_CH = c->CH;
                 o.obs_Etot = c->cfg.n_ensemble;
                 o.obs_E0 = lo;
-                o.obs_O = c->d_obs_O;
-                o.obs_y = c->obs_want_y ? c->d_obs_y : nullptr;
-                o.obs_xf = c->obs_want_xf ? c->d_obs_xf : nullptr;
+                o.obs_O = c->obs_O_call;
+                o.obs_y = c->obs_want_y ? c->obs_y_call : nullptr;
+                o.obs_xf = c->obs_want_xf ? c->obs_xf_call : nullptr;
+                o.obs_staged = c->obs_want_y ? c->obs_staged : 0;
                 HIP_TRY(c, launch_small_family(c, sand, mode, o, stream));
             }
             if (c->vjp_on) {                                 // grape_eval_vjp: the cotangents of these members, pulled back
-                SweepParams v = q;
-                v.vjp_only = 1;
-                v.vjp_n = c->vjp_has_y ? c->vjp_n : 0;
-                v.vjp_m = c->m;
-                v.vjp_per_member = c->vjp_per_member;
-                v.vjp_unitary = c->unitary ? 1 : 0;
-                v.vjp_CH = c->CH;
-                v.vjp_Etot = c->cfg.n_ensemble;
-                v.vjp_E0 = lo;
-                v.vjp_O = c->d_vjp_O;
-                v.vjp_ybar = c->vjp_has_y ? c->d_vjp_ybar : nullptr;
-                v.vjp_xbar = c->vjp_has_x ? c->d_vjp_xbar : nullptr;
-                v.vjp_xs = c->d_rc_xs;
-                v.vjp_rows = c->d_rc_rows;
-                v.vjp_part = c->d_vjp_part;
-                v.vjp_G = c->d_vjp_g;
+                SweepParams v = vjp_params(c, q, lo);
                 HIP_TRY(c, launch_small_family(c, 0, mode, v, stream));
                 if (lo + cnt == c->cfg.n_ensemble) {         // behind the last block: the groups' sums into the row
                     v.vjp_only = 2;
@@ -3350,27 +3383,60 @@ extern "C" int grape_eval_batch_device(grape_ctx *c, int32_t n_x, const double *
 }
 
 // ---- grape_eval_observables: one evaluation + the read-out along its trajectory --------------------------------------------
+// What the host form and the device form refuse and check alike, in the header's order: what the context cannot serve first,
+// then the arguments (x_needed: the device form of the pull-back takes a null x, its reuse).
+static int obs_check(grape_ctx *c, const std::string &who, const void *x, int32_t n_obs, int32_t per_member, const void *O,
+                     const void *y, const void *X_final)
+{
+    const char *why = why_exchange_not_served(c);
+    if (why) {}
+    else if (c->family != 0) why = "the operator dimension must be 2, 3 or 4 (the sweeps that leave every propagator in the workspace)";
+    else if (c->cfg.objective != GRAPE_OBJECTIVE_FOM) why = "objective = c1 is not served";
+    else if (c->cfg.gradient == GRAPE_GRADIENT_EXACT) why = "gradient = exact is not served";
+    if (why) return fail(c, GRAPE_ERR_UNSUPPORTED, who + ": " + why);
+    if (!x) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": x is null");
+    if (!y && !X_final) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": y and X_final are both null");
+    if (n_obs < 0 || n_obs > 16)
+        return fail(c, GRAPE_ERR_INVALID_ARG, who + ": n_obs = " + std::to_string(n_obs) + " (must be in 0..16)");
+    if (n_obs == 0 && y) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": n_obs = 0 with a non-null y");
+    if (n_obs > 0 && !O) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": n_obs > 0 with a null O");
+    if (per_member != 0 && per_member != 1)
+        return fail(c, GRAPE_ERR_INVALID_ARG, who + ": per_member = " + std::to_string(per_member) + " (must be 0 or 1)");
+    if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, who + ": operators not set");
+    return GRAPE_OK;
+}
+
+static int vjp_check(grape_ctx *c, const std::string &who, const void *x, bool x_needed, int32_t n_obs, int32_t per_member,
+                     const void *O, const void *ybar, const void *Xbar_final, const void *G)
+{
+    const char *why = why_exchange_not_served(c);
+    if (why) {}
+    else if (c->family != 0) why = "the operator dimension must be 2, 3 or 4 (the sweeps that leave every propagator in the workspace)";
+    else if (c->cfg.sys_type != GRAPE_UNITARY_GATE) why = "StateTransfer / CoherenceTransfer are not served (the sandwich needs a second term)";
+    else if (c->cfg.gradient == GRAPE_GRADIENT_EXACT) why = "gradient = exact is not served";
+    else if (c->cfg.objective != GRAPE_OBJECTIVE_FOM) why = "objective = c1 (the exact objective) is not served";
+    if (why) return fail(c, GRAPE_ERR_UNSUPPORTED, who + ": " + why);
+    if (!x && x_needed) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": x is null");
+    if (!G) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": G is null");
+    if (!ybar && !Xbar_final) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": ybar and Xbar_final are both null");
+    if (n_obs < 0 || n_obs > 16)
+        return fail(c, GRAPE_ERR_INVALID_ARG, who + ": n_obs = " + std::to_string(n_obs) + " (must be in 0..16)");
+    if (n_obs == 0 && ybar) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": n_obs = 0 with a non-null ybar");
+    if (n_obs > 0 && !O) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": n_obs > 0 with a null O");
+    if (per_member != 0 && per_member != 1)
+        return fail(c, GRAPE_ERR_INVALID_ARG, who + ": per_member = " + std::to_string(per_member) + " (must be 0 or 1)");
+    if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, who + ": operators not set");
+    return GRAPE_OK;
+}
+
 extern "C" int grape_eval_observables(grape_ctx *c, const double *x, int32_t n_obs, int32_t per_member, const double *O,
                                       double *y, double *X_final, double *F)
 {
     DeviceGuard guard;
     if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_observables: null context");
-    // what the context cannot serve first, as the header lists it; then the arguments
-    const char *who = "grape_eval_observables", *why = why_exchange_not_served(c);
-    if (why) {}
-    else if (c->family != 0) why = "the operator dimension must be 2, 3 or 4 (the sweeps that leave every propagator in the workspace)";
-    else if (c->cfg.objective != GRAPE_OBJECTIVE_FOM) why = "objective = c1 is not served";
-    else if (c->cfg.gradient == GRAPE_GRADIENT_EXACT) why = "gradient = exact is not served";
-    if (why) return fail(c, GRAPE_ERR_UNSUPPORTED, std::string("grape_eval_observables: ") + why);
-    if (!x) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_observables: x is null");
-    if (!y && !X_final) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_observables: y and X_final are both null");
-    if (n_obs < 0 || n_obs > 16)
-        return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_observables: n_obs = " + std::to_string(n_obs) + " (must be in 0..16)");
-    if (n_obs == 0 && y) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_observables: n_obs = 0 with a non-null y");
-    if (n_obs > 0 && !O) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_observables: n_obs > 0 with a null O");
-    if (per_member != 0 && per_member != 1)
-        return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_observables: per_member = " + std::to_string(per_member) + " (must be 0 or 1)");
-    if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, "grape_eval_observables: operators not set");
+    const char *who = "grape_eval_observables";
+    c->traj_valid = false;
+    if (int rc0 = obs_check(c, who, x, n_obs, per_member, O, y, X_final)) return rc0;
     const size_t n = (size_t)c->cfg.n, m = (size_t)c->m, E = (size_t)c->cfg.n_ensemble, N = (size_t)c->cfg.n_slices;
     const size_t n_O = n * m * (per_member ? E : 1) * (size_t)n_obs;
     int rc = check_finite(c, O, 2 * n_O, who, "O", 2);
@@ -3393,6 +3459,10 @@ extern "C" int grape_eval_observables(grape_ctx *c, const double *x, int32_t n_o
     c->obs_per_member = per_member;
     c->obs_want_y = want_y;
     c->obs_want_xf = X_final != nullptr;
+    c->obs_O_call = c->d_obs_O;
+    c->obs_y_call = c->d_obs_y;
+    c->obs_xf_call = c->d_obs_xf;
+    c->obs_staged = 0;
     c->obs_on = true;                                        // enqueue_eval's member blocks end in observe_kernel
     rc = eval_host(c, 1, x, F, nullptr, "grape_eval_observables");
     c->obs_on = false;
@@ -3411,24 +3481,9 @@ extern "C" int grape_eval_vjp(grape_ctx *c, const double *x, int32_t n_obs, int3
 {
     DeviceGuard guard;
     if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp: null context");
-    // what the context cannot serve first, as the header lists it; then the arguments
-    const char *who = "grape_eval_vjp", *why = why_exchange_not_served(c);
-    if (why) {}
-    else if (c->family != 0) why = "the operator dimension must be 2, 3 or 4 (the sweeps that leave every propagator in the workspace)";
-    else if (c->cfg.sys_type != GRAPE_UNITARY_GATE) why = "StateTransfer / CoherenceTransfer are not served (the sandwich needs a second term)";
-    else if (c->cfg.gradient == GRAPE_GRADIENT_EXACT) why = "gradient = exact is not served";
-    else if (c->cfg.objective != GRAPE_OBJECTIVE_FOM) why = "objective = c1 (the exact objective) is not served";
-    if (why) return fail(c, GRAPE_ERR_UNSUPPORTED, std::string("grape_eval_vjp: ") + why);
-    if (!x) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp: x is null");
-    if (!G) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp: G is null");
-    if (!ybar && !Xbar_final) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp: ybar and Xbar_final are both null");
-    if (n_obs < 0 || n_obs > 16)
-        return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp: n_obs = " + std::to_string(n_obs) + " (must be in 0..16)");
-    if (n_obs == 0 && ybar) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp: n_obs = 0 with a non-null ybar");
-    if (n_obs > 0 && !O) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp: n_obs > 0 with a null O");
-    if (per_member != 0 && per_member != 1)
-        return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp: per_member = " + std::to_string(per_member) + " (must be 0 or 1)");
-    if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, "grape_eval_vjp: operators not set");
+    const char *who = "grape_eval_vjp";
+    c->traj_valid = false;
+    if (int rc0 = vjp_check(c, who, x, true, n_obs, per_member, O, ybar, Xbar_final, G)) return rc0;
     const size_t n = (size_t)c->cfg.n, m = (size_t)c->m, E = (size_t)c->cfg.n_ensemble, N = (size_t)c->cfg.n_slices;
     const size_t n_O = n * m * (per_member ? E : 1) * (size_t)n_obs, n_y = (N + 1) * (size_t)n_obs * E, n_X = n * m * E;
     int rc = check_finite(c, O, 2 * n_O, who, "O", 2);
@@ -3465,6 +3520,11 @@ extern "C" int grape_eval_vjp(grape_ctx *c, const double *x, int32_t n_obs, int3
     c->vjp_per_member = per_member;
     c->vjp_has_y = ybar != nullptr;
     c->vjp_has_x = Xbar_final != nullptr;
+    c->vjp_O_call = c->d_vjp_O;
+    c->vjp_ybar_call = c->d_vjp_ybar;
+    c->vjp_xbar_call = c->d_vjp_xbar;
+    c->vjp_G_call = c->d_vjp_g;
+    c->vjp_staged = 0;
     c->vjp_on = true;                                        // enqueue_eval's member blocks end in the two kernels of vjp.hip
     rc = eval_host(c, 1, x, nullptr, nullptr, who);          // (its [G, F] are not wanted)
     c->vjp_on = false;
@@ -3484,6 +3544,155 @@ extern "C" int grape_eval_vjp(grape_ctx *c, const double *x, int32_t n_obs, int3
     rc = wait_stream(c, c->stream);
     if (rc) return rc;
     HIP_TRY(c, hipMemcpy(G, d_res, sizeof(double) * kp, hipMemcpyDeviceToHost));
+    return GRAPE_OK;
+}
+
+// ---- the device forms: the caller's arrays live on this device, nothing is copied, nothing is synchronised ---------------------
+// Up to how many probes the staged instances (observe_staged_kernel / trajectory_vjp_staged_kernel) are the default where the
+// member block fits the LDS budget: the counts at which they beat the direct instances by more than the block-to-block spread
+// in section (a) of tools/traj_device_time.py, profiles/r13_traj_device_time.txt (headline config, MI355X; HIP-event time per
+// call, direct minus staged, median over the blocks):
+//   read-out  n_obs 1 / 2 / 4 / 8: +12.8 / +8.2 / +15.4 / +3.8 us (spread <= 1.6 us); 12 / 16: -54.7 / -47.5 us
+//             (an image of 96 / 128 KB leaves one workgroup per CU where the direct instance runs two)
+static constexpr int kObsStagedMaxProbes = 8;
+//   pull-back n_obs 1 / 2 / 4 / 8: +9.8 / +18.7 / +49.0 / +36.6 us (spread <= 1.0 us); 12 / 16: -108.9 / -114.9 us
+static constexpr int kVjpStagedMaxProbes = 8;
+// (9 .. 11 probes were not measured: direct.  GRAPE_TRAJ_STAGED=1 reaches the staged instances at any count that fits.)
+
+// Bytes of the LDS image of one member's y / ybar block when the staged instance is to run, else 0 (the direct instance).
+// GRAPE_TRAJ_STAGED=0 / 1 forces the choice (1: where the block fits); the budget is the device's LDS per workgroup minus the
+// kernel's static LDS, or GRAPE_TRAJ_LDS_BYTES where that is smaller (tests).
+static int traj_staged_bytes(const grape_ctx *c, int n_obs, bool vjp)
+{
+    if (n_obs < 1 || env_off("GRAPE_TRAJ_STAGED")) return 0;
+    if (!env_on("GRAPE_TRAJ_STAGED") && n_obs > (vjp ? kVjpStagedMaxProbes : kObsStagedMaxProbes)) return 0;
+    const size_t fixed = grape::traj_static_lds(c->cfg.n, c->m, vjp);
+    size_t budget = (size_t)c->lds_cap > fixed ? (size_t)c->lds_cap - fixed : 0;
+    const char *v = std::getenv("GRAPE_TRAJ_LDS_BYTES");
+    if (v && v[0]) budget = std::min(budget, (size_t)std::strtoull(v, nullptr, 10));
+    const size_t want = sizeof(double2) * (size_t)n_obs * ((size_t)c->cfg.n_slices + 1);
+    return want <= budget ? (int)want : 0;
+}
+
+// what both device forms do in front of their launches: the device, the order behind a pending device call (the scratch
+// buffers may grow only behind it), the LDS a workgroup may hold
+static int traj_device_prologue(grape_ctx *c)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = order_behind_device_call(c, c)) return rc;
+    if (!c->lds_cap) HIP_TRY(c, hipDeviceGetAttribute(&c->lds_cap, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
+    return GRAPE_OK;
+}
+
+// one evaluation of d_x as grape_eval_device runs it, [G, F] into `out` (in the coordinates of x)
+static int traj_device_eval(grape_ctx *c, const double *d_x, double *out, hipStream_t st)
+{
+    return pulse_map(c) ? eval_param_device(c, d_x, out, st, 1) : eval_device_impl(c, d_x, out, (void *)st, 1);
+}
+
+extern "C" int grape_eval_observables_device(grape_ctx *c, const double *d_x, int32_t n_obs, int32_t per_member, const double *d_O,
+                                             double *d_y, double *d_X_final, double *d_fg, void *stream)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_observables_device: null context");
+    const char *who = "grape_eval_observables_device";
+    c->traj_valid = false;
+    int rc = obs_check(c, who, d_x, n_obs, per_member, d_O, d_y, d_X_final);
+    if (rc) return rc;
+    rc = traj_device_prologue(c);
+    if (rc) return rc;
+    if (!d_fg) {                                             // the evaluation's own [G, F] is not wanted: a row of the context's
+        d_fg = c->d_fg;
+        if (pulse_map(c)) {
+            rc = grow(c, &c->d_vjp_out, &c->vjp_out_bytes, sizeof(double) * (KP(c) + 1), who, "the projected row");
+            if (rc) return rc;
+            d_fg = c->d_vjp_out;
+        }
+    }
+    const bool want_y = d_y != nullptr && n_obs > 0;
+    c->obs_n = n_obs;
+    c->obs_per_member = per_member;
+    c->obs_want_y = want_y;
+    c->obs_want_xf = d_X_final != nullptr;
+    c->obs_O_call = (const double2 *)d_O;
+    c->obs_y_call = (double2 *)d_y;
+    c->obs_xf_call = (double2 *)d_X_final;
+    c->obs_staged = want_y ? traj_staged_bytes(c, n_obs, false) : 0;
+    c->obs_on = true;                                        // enqueue_eval's member blocks end in observe_kernel
+    rc = traj_device_eval(c, d_x, d_fg, (hipStream_t)stream);
+    c->obs_on = false;
+    if (rc) return rc;
+    c->traj_valid = !chunked(c);
+    return GRAPE_OK;
+}
+
+extern "C" int grape_eval_vjp_device(grape_ctx *c, const double *d_x, int32_t n_obs, int32_t per_member, const double *d_O,
+                                     const double *d_ybar, const double *d_Xbar_final, double *d_G, void *stream)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp_device: null context");
+    const char *who = "grape_eval_vjp_device";
+    const bool reuse = d_x == nullptr, was_valid = c->traj_valid;
+    c->traj_valid = false;
+    int rc = vjp_check(c, who, d_x, false, n_obs, per_member, d_O, d_ybar, d_Xbar_final, d_G);
+    if (rc) return rc;
+    if (reuse && chunked(c))
+        return fail(c, GRAPE_ERR_NOT_READY, std::string(who) + ": d_x is null (reuse), but the workspace of a context under member_chunk "
+                                            "holds one block of members only");
+    if (reuse && !was_valid)
+        return fail(c, GRAPE_ERR_NOT_READY, std::string(who) + ": d_x is null (reuse), but the workspace does not hold the trajectory of a "
+                                            "device form: another call has evaluated, changed a setting or failed since");
+    hipStream_t st = (hipStream_t)stream;
+    rc = traj_device_prologue(c);
+    if (rc) return rc;
+    const size_t E = (size_t)c->cfg.n_ensemble, kn = KN(c), kp = KP(c);
+    rc = grow(c, &c->d_vjp_part, &c->vjp_part_bytes, sizeof(double) * kn * ((E + grape::kVjpGroup - 1) / grape::kVjpGroup), who, "the groups' rows");
+    if (rc) return rc;
+    if (pulse_map(c)) {
+        rc = grow(c, &c->d_vjp_g, &c->vjp_g_bytes, sizeof(double) * (kn + 1), who, "the summed row");
+        if (rc) return rc;
+        rc = grow(c, &c->d_vjp_out, &c->vjp_out_bytes, sizeof(double) * (kp + 1), who, "the projected row");
+        if (rc) return rc;
+    }
+    c->vjp_n = n_obs;
+    c->vjp_per_member = per_member;
+    c->vjp_has_y = d_ybar != nullptr;
+    c->vjp_has_x = d_Xbar_final != nullptr;
+    c->vjp_O_call = (const double2 *)d_O;
+    c->vjp_ybar_call = (const double2 *)d_ybar;
+    c->vjp_xbar_call = (const double2 *)d_Xbar_final;
+    c->vjp_G_call = pulse_map(c) ? c->d_vjp_g : d_G;          // (no pulse map: the groups' sums ARE G)
+    c->vjp_staged = d_ybar ? traj_staged_bytes(c, n_obs, true) : 0;
+    if (!reuse) {
+        c->vjp_on = true;                                    // enqueue_eval's member blocks end in the two kernels of vjp.hip
+        rc = traj_device_eval(c, d_x, pulse_map(c) ? c->d_vjp_out : c->d_fg, st);          // (its [G, F] are not wanted)
+        c->vjp_on = false;
+        if (rc) return rc;
+    } else {
+        // the propagators (and the slope array) of the last device form are in place: the pull-back alone
+        rc = rc_ensure(c);                                   // (the rows, and the states of the general flow)
+        if (rc) return rc;
+        KernelLogScope log_scope(&c->kernel_log);
+        SweepParams q = sweep_params(c, nullptr, 1);
+        q.props = c->d_props;
+        SweepParams v = vjp_params(c, q, 0);
+        const int mode = c->unitary ? 2 : (c->d_costates ? 1 : 0);
+        HIP_TRY(c, launch_small_family(c, 0, mode, v, st));
+        v.vjp_only = 2;
+        HIP_TRY(c, launch_small_family(c, 0, mode, v, st));
+    }
+    if (pulse_map(c)) {
+        // the summed physical row -> the coordinates of x, straight into the caller's G (no F slot: BasisOp::no_f)
+        KernelLogScope log_scope(&c->kernel_log, true);
+        grape::BasisOp op = basis_op(c, true, 1);
+        op.no_f = 1;
+        grape::DoneSignal d;
+        d.basis = &op;
+        HIP_TRY(c, grape::launch_copy(c->d_vjp_g, d_G, (int)kp, st, d));
+    }
+    HIP_TRY(c, hipEventRecord(c->ev_dev, st));
+    c->dev_pending = true;
+    c->traj_valid = !chunked(c);
     return GRAPE_OK;
 }
 
@@ -3565,6 +3774,7 @@ extern "C" int grape_eval_fom(grape_ctx *c, int32_t n_x, const double *x, double
 {
     DeviceGuard guard;
     if (!c) return GRAPE_ERR_INVALID_ARG;
+    c->traj_valid = false;                                   // (grape_eval_vjp_device's reuse)
     if (!x || !F) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_fom: x or F is null");
     if (n_x < 1 || n_x > c->B)
         return fail(c, GRAPE_ERR_INVALID_ARG, "grape_eval_fom: n_x must be in 1..max(1, grape_config.max_batch)");
@@ -3897,6 +4107,7 @@ extern "C" int grape_lbfgs(grape_ctx *c, const double *x0, const grape_lbfgs_opt
 {
     DeviceGuard guard;
     if (!c) return GRAPE_ERR_INVALID_ARG;
+    c->traj_valid = false;                                   // (grape_eval_vjp_device's reuse)
     if (!x0 || !x_min || !result) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_lbfgs: null argument");
     if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, "grape_lbfgs: operators not set");
     const size_t kn = KP(c), Q = kn + 1;                     // (parameter mode: every vector is K M long)

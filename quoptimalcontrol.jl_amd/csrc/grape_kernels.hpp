@@ -51,6 +51,7 @@ struct BasisOp {
     int32_t bounded = 0;                       // 1: grape_set_bounds is in force
     const double *lo = nullptr, *hi = nullptr; // device (K) each
     double *slope = nullptr;                   // device (K, N, n_x): written by the expansion, read by the projection
+    int32_t no_f = 0;                          // project, n_x = 1: dst holds K M entries only, the F slot is neither read nor written
 };
 // optional host-visible completion signal of an evaluation's FINAL kernel (reduce.hip: signal_done);
 // flag == nullptr: none (device-pointer entry points, intermediate kernels)
@@ -192,7 +193,20 @@ struct SweepParams {
     double *vjp_rows;        // K N per member of this launch: the member's unweighted gradient row
     double *vjp_part;        // (K N, ceil(vjp_Etot / kVjpGroup)): the rows summed over each group of consecutive members
     double *vjp_G;           // K N: the groups' sums added up, in group order
+    // the device forms (grape_eval_observables_device / grape_eval_vjp_device): > 0 selects the STAGED instance of
+    // observe_kernel / trajectory_vjp_kernel, whose workgroup passes the member's contiguous y (ybar) block of
+    // obs_n (vjp_n) * (N + 1) * 16 bytes through an LDS image; the value is that size = the launch's dynamic LDS.  0: the
+    // direct instance, the kernel of the host forms.
+    int32_t obs_staged;
+    int32_t vjp_staged;
 };
+// static LDS of observe_kernel (vjp = false) / trajectory_vjp_kernel (vjp = true) at operator dimension n with m state
+// columns: the scans' wave totals.  What the host layer subtracts from the device's LDS per workgroup to get the staged
+// instances' budget (the launchers check the sum against the kernel's own attributes).
+constexpr size_t traj_static_lds(int n, int m, bool vjp)
+{
+    return (size_t)((n == 2 ? 1024 : n == 3 ? 512 : 256) / 64) * (size_t)(n * n + (vjp ? n * m : 0)) * 16;
+}
 // observe.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::obs_only) only
 hipError_t run_observe(int n, int sandwich, const SweepParams &p, hipStream_t stream);
 // vjp.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::vjp_only) only

@@ -18,6 +18,12 @@
 // Ragged decompositions: a lane whose chunk starts at or behind N, and the padding lanes behind chunk CH - 1, own no slice
 // (Q = 1, nothing stored); the last chunk may be short.  Plain vector stores, no atomics; every number has one fixed
 // evaluation order, so results are bitwise reproducible and a member-chunked launch gives the bits of an unchunked one.
+//
+// STAGED (observe_staged_kernel; the device forms, SweepParams::obs_staged): a member's y block is ONE contiguous run of
+// n_obs (N + 1) entries in the caller's layout, but lane c stores at s = c S + jj: neighbouring lanes are S 16 B apart within a
+// probe row, every wave store touches 64 sectors.  The staged instance writes the same values into an LDS image of the block
+// at [j][s] (lane 0's s = 0 entries included), and behind ONE barrier behind the walk -- reached by every lane, whatever its
+// cnt -- the workgroup streams the image out with lane-contiguous 16 B stores.  Same arithmetic, same order, same bits.
 #include "cmat.hpp"
 #include "grape_kernels.hpp"
 #include "rc_mat.hpp"
@@ -61,13 +67,14 @@ GRAPE_DEV void obs_apply(CRect<N, M> &X, const CMat<N> &U)
 
 // ops_all / o_all are separate `const __restrict__` arguments so that the wave-uniform operator and probe entries can be
 // fetched with scalar loads (as in sweep_small.hip and running_cost.hip)
-template <int N, int M, bool SAND, int MAXT>
+template <int N, int M, bool SAND, int MAXT, bool STAGED>
 __global__ __launch_bounds__(MAXT) void observe_kernel(const double2 *__restrict__ ops_all, const double2 *__restrict__ o_all,
                                                        const SweepParams p)
 {
     static_assert(!SAND || M == N, "the sandwich acts on n x n states");
     constexpr int NN = N * N, NM = N * M, MAXW = MAXT / 64;
     __shared__ double2 s_q[MAXW][NN];              // wave totals of the prefix scan
+    extern __shared__ double2 s_img[];             // STAGED: the member's y block, [j][s] as the caller lays it out
 
     const int CH = p.obs_CH, S = p.S, K = p.K, Nsl = p.N, n_obs = p.obs_n;
     const int L = threadIdx.x, lane = L & 63;
@@ -144,7 +151,10 @@ __global__ __launch_bounds__(MAXT) void observe_kernel(const double2 *__restrict
                 yi = fma(v.x, X.im[e], yi);
                 yi = fma(-v.y, X.re[e], yi);
             }
-            yk[(size_t)s + (size_t)j * ((size_t)Nsl + 1)] = make_double2(yr, yi);
+            if constexpr (STAGED)
+                s_img[s + j * (Nsl + 1)] = make_double2(yr, yi);
+            else
+                yk[(size_t)s + (size_t)j * ((size_t)Nsl + 1)] = make_double2(yr, yi);
         }
     };
     if (yk && L == 0)
@@ -155,6 +165,14 @@ __global__ __launch_bounds__(MAXT) void observe_kernel(const double2 *__restrict
         obs_apply<N, M, SAND>(X, P);
         if (yk)
             emit(lo + jj + 1);
+    }
+    if constexpr (STAGED) {                          // the image -> y, lane-contiguous (every lane reaches the barrier)
+        __syncthreads();
+        if (yk) {
+            const int tot = n_obs * (Nsl + 1);
+            for (int i = L; i < tot; i += (int)blockDim.x)
+                yk[i] = s_img[i];
+        }
     }
     // ---------------------------------------------------------------- 5: X_N
     if (p.obs_xf && cnt > 0 && hi == Nsl) {
@@ -174,7 +192,23 @@ static hipError_t obs_launch_nm(const SweepParams &p, hipStream_t stream)
         p.obs_E0 + p.E > p.obs_Etot || p.obs_n < 0 || p.obs_n > 16 || (!p.obs_y && !p.obs_xf) ||
         (p.obs_y && p.obs_n > 0 && !p.obs_O) || !p.props || !p.ops)
         return hipErrorInvalidConfiguration;
-    GRAPE_LAUNCH_AS("observe_kernel", (observe_kernel<N, M, SAND, MAXT>), dim3(p.E), dim3(threads), 0, stream, p.ops, p.obs_O, p);
+    if (p.obs_staged) {
+        // the image is exactly the member's block, and static + dynamic LDS fit a workgroup of this device
+        const auto kern = observe_kernel<N, M, SAND, MAXT, true>;
+        const size_t lds = (size_t)p.obs_staged;
+        if (!p.obs_y || p.obs_n < 1 || lds != sizeof(double2) * (size_t)p.obs_n * ((size_t)p.N + 1))
+            return hipErrorInvalidConfiguration;
+        int dev = 0, cap = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e == hipSuccess) e = hipDeviceGetAttribute(&cap, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+        if (e != hipSuccess) return e;
+        if (lds + traj_static_lds(N, M, false) > (size_t)cap) return hipErrorInvalidConfiguration;
+        e = ensure_dynamic_lds((const void *)kern, lds);
+        if (e != hipSuccess) return e;
+        GRAPE_LAUNCH_AS("observe_staged_kernel", kern, dim3(p.E), dim3(threads), lds, stream, p.ops, p.obs_O, p);
+        return hipGetLastError();
+    }
+    GRAPE_LAUNCH_AS("observe_kernel", (observe_kernel<N, M, SAND, MAXT, false>), dim3(p.E), dim3(threads), 0, stream, p.ops, p.obs_O, p);
     return hipGetLastError();
 }
 

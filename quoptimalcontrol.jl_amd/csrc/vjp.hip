@@ -24,6 +24,11 @@
 // The members' rows are unweighted, K N doubles each, written with plain vector stores; vjp_sum_kernel adds them in a tree
 // fixed by the members' ensemble indices (groups of 32 in member order, then the groups in order), so a member-chunked
 // launch sequence gives the bits of an unchunked one.
+//
+// STAGED (trajectory_vjp_staged_kernel; the device forms, SweepParams::vjp_staged): a member's ybar block is ONE contiguous run
+// of n_obs (N + 1) entries, read twice (once per walk) at a lane stride of S 16 B.  The staged instance loads the block into
+// LDS once, lane-contiguous, in front of the first walk (one barrier more, reached by every lane) and both walks read the
+// image: every ybar byte leaves HBM once.  Same arithmetic, same order, same bits.
 #include "cmat.hpp"
 #include "grape_kernels.hpp"
 #include "rc_mat.hpp"
@@ -32,7 +37,7 @@ namespace grape {
 
 // ops_all / o_all are separate `const __restrict__` arguments so that the wave-uniform operator and probe entries can be
 // fetched with scalar loads (as in running_cost.hip).  UNI: every propagator is unitary.
-template <int N, int M, bool UNI, int MAXT>
+template <int N, int M, bool UNI, int MAXT, bool STAGED>
 __global__ __launch_bounds__(MAXT) void trajectory_vjp_kernel(const double2 *__restrict__ ops_all,
                                                               const double2 *__restrict__ o_all,
                                                               const double2 *__restrict__ ybar_all,
@@ -41,6 +46,7 @@ __global__ __launch_bounds__(MAXT) void trajectory_vjp_kernel(const double2 *__r
     constexpr int NN = N * N, NM = N * M, MAXW = MAXT / 64;
     __shared__ double2 s_q[MAXW][NN];              // wave totals: prefix products, then the affine maps' matrices ...
     __shared__ double2 s_v[MAXW][NM];              // ... and their offsets
+    extern __shared__ double2 s_img[];             // STAGED: the member's ybar block, [j][s] as the caller lays it out
 
     const int CH = p.vjp_CH, S = p.S, K = p.K, Nsl = p.N, n_obs = ybar_all ? p.vjp_n : 0;
     const int L = threadIdx.x, lane = L & 63;
@@ -63,6 +69,23 @@ __global__ __launch_bounds__(MAXT) void trajectory_vjp_kernel(const double2 *__r
     const size_t y_step = (size_t)Nsl + 1;
     const double2 *__restrict__ yb = ybar_all ? ybar_all + (size_t)kg * p.vjp_n * y_step : nullptr;
     double *__restrict__ row = p.vjp_rows + (size_t)k * K * Nsl;
+    if constexpr (STAGED) {                          // (the barrier in front of the first walk publishes the image)
+        if (yb) {                                    // eight 16 B loads in flight per lane: one load per round trip left the
+            const int tot = n_obs * (Nsl + 1), bd = (int)blockDim.x;      // 16-probe block (31 trips) slower than two strided reads
+            int i = L;
+            for (; i + 7 * bd < tot; i += 8 * bd) {
+                double2 v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    v[u] = yb[i + u * bd];
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    s_img[i + u * bd] = v[u];
+            }
+            for (; i < tot; i += bd)
+                s_img[i] = yb[i];
+        }
+    }
 
     // ---------------------------------------------------------------- 1: chunk product
     CMat<N> Q, P, T;
@@ -137,7 +160,11 @@ __global__ __launch_bounds__(MAXT) void trajectory_vjp_kernel(const double2 *__r
                 }
             }
             for (int j = 0; j < n_obs; ++j) {        // Lam_{t+1} = (what came from the right) + sum_j ybar O_j
-                const double2 c = yb[(size_t)(t + 1) + (size_t)j * y_step];
+                double2 c;
+                if constexpr (STAGED)
+                    c = s_img[(t + 1) + j * (Nsl + 1)];
+                else
+                    c = yb[(size_t)(t + 1) + (size_t)j * y_step];
                 const double2 *__restrict__ o = o_mem + (size_t)j * o_step;
 #pragma unroll
                 for (int e = 0; e < NM; ++e) {
@@ -175,6 +202,8 @@ __global__ __launch_bounds__(MAXT) void trajectory_vjp_kernel(const double2 *__r
     // ---------------------------------------------------------------- 4: the chunk's affine map
     CRect<N, M> bvec;
     rzero(bvec);
+    if constexpr (STAGED)
+        __syncthreads();                             // the image is complete (every lane arrives: no path above leaves)
     walk(bvec, false);
     // ---------------------------------------------------------------- 5: suffix scan of (Q', b)
     CRect<N, M> Lin;
@@ -287,13 +316,28 @@ static hipError_t vjp_launch_nm(const SweepParams &p, hipStream_t stream)
         !p.ops || (long long)p.K * p.N > 0x7fffff00ll)
         return hipErrorInvalidConfiguration;
     const dim3 grid(p.E), block(threads);
-    if (p.vjp_unitary)
-        GRAPE_LAUNCH_AS("trajectory_vjp_kernel", (trajectory_vjp_kernel<N, M, true, MAXT>), grid, block, 0, stream, p.ops, p.vjp_O,
+    hipError_t e = hipSuccess;
+    if (p.vjp_staged) {
+        // the image is exactly the member's block, and static + dynamic LDS fit a workgroup of this device
+        const size_t lds = (size_t)p.vjp_staged;
+        if (!p.vjp_ybar || lds != sizeof(double2) * (size_t)p.vjp_n * ((size_t)p.N + 1))
+            return hipErrorInvalidConfiguration;
+        int dev = 0, cap = 0;
+        e = hipGetDevice(&dev);
+        if (e == hipSuccess) e = hipDeviceGetAttribute(&cap, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+        if (e != hipSuccess) return e;
+        if (lds + traj_static_lds(N, M, true) > (size_t)cap) return hipErrorInvalidConfiguration;
+        const auto kern = p.vjp_unitary ? trajectory_vjp_kernel<N, M, true, MAXT, true> : trajectory_vjp_kernel<N, M, false, MAXT, true>;
+        e = ensure_dynamic_lds((const void *)kern, lds);
+        if (e != hipSuccess) return e;
+        GRAPE_LAUNCH_AS("trajectory_vjp_staged_kernel", kern, grid, block, lds, stream, p.ops, p.vjp_O, p.vjp_ybar, p.vjp_xbar, p);
+    } else if (p.vjp_unitary)
+        GRAPE_LAUNCH_AS("trajectory_vjp_kernel", (trajectory_vjp_kernel<N, M, true, MAXT, false>), grid, block, 0, stream, p.ops, p.vjp_O,
                         p.vjp_ybar, p.vjp_xbar, p);
     else
-        GRAPE_LAUNCH_AS("trajectory_vjp_kernel", (trajectory_vjp_kernel<N, M, false, MAXT>), grid, block, 0, stream, p.ops, p.vjp_O,
+        GRAPE_LAUNCH_AS("trajectory_vjp_kernel", (trajectory_vjp_kernel<N, M, false, MAXT, false>), grid, block, 0, stream, p.ops, p.vjp_O,
                         p.vjp_ybar, p.vjp_xbar, p);
-    hipError_t e = hipGetLastError();
+    e = hipGetLastError();
     if (e != hipSuccess)
         return e;
     const int Q = p.K * p.N;

@@ -40,7 +40,7 @@ EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_oper
            "grape_set_basis", "grape_get_controls", "grape_set_bounds", "grape_set_risk", "grape_get_risk_weights",
            "grape_comm_unique_id", "grape_comm_attach", "grape_ipc_export", "grape_ipc_attach",
            "grape_eval", "grape_eval_device", "grape_eval_batch", "grape_eval_batch_device", "grape_eval_fom", "grape_eval_observables",
-           "grape_eval_vjp",
+           "grape_eval_vjp", "grape_eval_observables_device", "grape_eval_vjp_device",
            "grape_lbfgs", "grape_lbfgs_get_trace",
            "grape_get_member_results", "grape_get_trajectory",
            "grape_get_kernel_time", "grape_get_kernel_samples", "grape_get_kernel_names", "grape_get_group_timing", "grape_get_phase_stamps",
@@ -142,6 +142,8 @@ def load_library():
     L.grape_eval_fom.argtypes = [vp, i32, vp, vp, vp]
     L.grape_eval_observables.argtypes = [vp, vp, i32, i32, vp, vp, vp, dp]
     L.grape_eval_vjp.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp]
+    L.grape_eval_observables_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.grape_eval_vjp_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.grape_lbfgs.argtypes = [vp, vp, C.POINTER(GrapeLbfgsOptions), vp, C.POINTER(GrapeLbfgsResult)]
     L.grape_get_member_results.argtypes = [vp, vp, vp]
     L.grape_get_trajectory.argtypes = [vp, i32, vp, vp, vp]
@@ -170,6 +172,19 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+class _CountingLib:
+    """The library as an engine sees it: every function fetched through it that evaluates or changes a setting -- everything
+    but the read-only accessors -- bumps GrapeEngine.calls first."""
+
+    def __init__(self, lib, engine):
+        self.__dict__["_lib"], self.__dict__["_engine"] = lib, engine
+
+    def __getattr__(self, name):
+        if not (name.startswith("grape_get_") and name != "grape_get_controls") and name not in ("grape_last_error", "grape_lbfgs_get_trace"):
+            self._engine.calls += 1
+        return getattr(self._lib, name)
+
+
 class GrapeEngine:
     """One context = one device + one shard of the ensemble.
 
@@ -178,6 +193,8 @@ class GrapeEngine:
 
     n_params = 0                               # M of set_basis (parameter mode); 0: slice mode
     bounds = None                              # (lo, hi) of set_bounds while some control is bounded
+    calls = 0                                  # library calls that evaluate or change a setting, so far: two equal readings
+                                               # mean that nothing has touched the context in between (autograd's reuse)
 
     def __init__(self, sys_type, A, B, Xi, Xt, wts, T, n_slices, variant=0, device=-1, flags=0,
                  slices_per_lane=0, waves_per_member=0, expm_squarings=-1, member_results=False, max_batch=1,
@@ -187,7 +204,7 @@ class GrapeEngine:
         gradient: "reference" (the first-order grad_func!) or "exact" (derivative of the objective, 2 <= n <= 64);
         objective: "fom" (fom_func) or "c1" (the ADGRAPE functional C1(Xt, U Xi [U']); needs gradient="exact")."""
         self._h = None
-        self._lib = load_library()
+        self._lib = _CountingLib(load_library(), self)
         A = np.asarray(A, dtype=np.complex128)
         B = np.asarray(B, dtype=np.complex128)
         if A.ndim != 3 or B.ndim != 4 or A.shape[1] != A.shape[2]:
@@ -455,6 +472,7 @@ class GrapeEngine:
         check = self._check
 
         def call():
+            self.calls += 1
             rc = fn(h, px, pF, pg)
             if rc:
                 check(rc)
@@ -608,6 +626,40 @@ class GrapeEngine:
         xf = np.ascontiguousarray(x.T)
         self._check(self._lib.grape_eval_vjp(self._h, _p(xf), n_obs, 1 if per_member else 0, _p(Of), _p(yb), _p(xb), _p(G)))
         return np.ascontiguousarray(G.T)
+
+    def observe_device(self, d_x, n_obs, per_member, d_O, d_y, d_X_final, d_fg=0, stream=0):
+        """grape_eval_observables_device with raw device pointers (e.g. torch tensor .data_ptr()), in the library's layouts:
+        d_x f64 (K, cols) column-major, d_O c128 (n, m, [E,] n_obs), d_y c128 (N+1, n_obs, E), d_X_final c128 (n, m, E), d_fg
+        f64 [K cols + 1]; 0 for an output that is not wanted (not d_y and d_X_final both).  Asynchronous on `stream`; the
+        arrays stay alive until the stream has passed the call.  Non-finite device entries are not checked."""
+        n_obs = self._traj_device_args("observe_device", d_x, n_obs, d_O, d_y, d_X_final, "d_y and d_X_final")
+        self._check(self._lib.grape_eval_observables_device(self._h, C.c_void_p(d_x), n_obs, 1 if per_member else 0, C.c_void_p(d_O),
+                                                            C.c_void_p(d_y), C.c_void_p(d_X_final), C.c_void_p(d_fg),
+                                                            C.c_void_p(stream)))
+
+    def observe_vjp_device(self, d_x, n_obs, per_member, d_O, d_ybar, d_Xbar_final, d_G, stream=0):
+        """grape_eval_vjp_device with raw device pointers, layouts as observe_device; d_G f64 (K, cols) column-major.  d_x=0:
+        reuse -- pull back along the trajectory the last observe_device / observe_vjp_device left in the workspace, without
+        a sweep (GrapeError NOT_READY when anything else has touched the context since, or under a member chunk)."""
+        n_obs = self._traj_device_args("observe_vjp_device", 1, n_obs, d_O, d_ybar, d_Xbar_final, "d_ybar and d_Xbar_final")
+        if not d_G:
+            raise ValueError("observe_vjp_device: d_G is null")
+        self._check(self._lib.grape_eval_vjp_device(self._h, C.c_void_p(d_x), n_obs, 1 if per_member else 0, C.c_void_p(d_O),
+                                                    C.c_void_p(d_ybar), C.c_void_p(d_Xbar_final), C.c_void_p(d_G),
+                                                    C.c_void_p(stream)))
+
+    @staticmethod
+    def _traj_device_args(who, d_x, n_obs, d_O, d_a, d_b, names):
+        n_obs = int(n_obs)
+        if not 0 <= n_obs <= 16:
+            raise ValueError(f"{who}: n_obs = {n_obs} (must be in 0..16)")
+        if not d_x:
+            raise ValueError(f"{who}: d_x is null")
+        if not d_a and not d_b:
+            raise ValueError(f"{who}: {names} are both null")
+        if n_obs > 0 and not d_O:
+            raise ValueError(f"{who}: n_obs > 0 with a null d_O")
+        return n_obs
 
     def eval_device(self, d_x_ptr, d_fg_ptr, stream=0):
         """grape_eval_device with raw device pointers (e.g. torch tensor .data_ptr())."""
