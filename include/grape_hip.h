@@ -695,6 +695,8 @@ int grape_get_kernel_samples(grape_ctx *ctx, double *total_ms, double *first_ms,
  * namespace and template arguments -- e.g. "action_rows_kernel;action_parts_kernel;action_forms_sparse_kernel;reduce_stage1;
  * reduce_stage2".  Which kernels serve src/GRAPE.jl:25-96 depends on what grape_set_operators found (grape_info) and on the
  * ensemble size; benchmarks label their lines with this instead of guessing.  Multi-device contexts report the first device.
+ * After grape_lbfgs: the kernels of the run's last evaluation, then the optimiser's own kernels (lbfgs.hip), each name once
+ * in order of first launch -- which of the step kernels committed the run's accepted steps.
  * Returns the buffer size the complete list needs (> 0), or a negative status. */
 int grape_get_kernel_names(const grape_ctx *ctx, char *buf, int32_t capacity);
 

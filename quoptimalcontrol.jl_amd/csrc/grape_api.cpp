@@ -3853,6 +3853,29 @@ struct LbfgsRun {
     bool hung = false;                            // a wait timed out: the device is presumed hung, nothing is synchronised any more
     bool fused_probe = false;                     // phi / phi' of a trial step come from the evaluation's reduce kernel
     bool mb = false;                              // accepted steps run on many workgroups (lbfgs_dots_kernel + lbfgs_step_mb_kernel)
+    std::string launched, last;                   // the optimiser's own kernels, each name once, in order of first launch
+
+    // one of lbfgs.hip's launchers (one kernel each) with its kernel's name noted: grape_lbfgs appends `launched` to the log
+    // of the run's last evaluation, so that grape_get_kernel_names tells which of the step kernels a run went through
+    template <class Launch> hipError_t noted(Launch &&launch)
+    {
+        hipError_t e;
+        {
+            KernelLogScope scope(&last);
+            e = launch();
+        }
+        for (size_t at = 0; !last.empty(); at += last.size()) {
+            at = launched.find(last, at);
+            if (at == std::string::npos) {
+                if (!launched.empty()) launched.push_back(';');
+                launched += last;
+                break;
+            }
+            const size_t end = at + last.size();
+            if ((at == 0 || launched[at - 1] == ';') && (end == launched.size() || launched[end] == ';')) break;
+        }
+        return e;
+    }
 
     grape::DoneSignal signal()
     {
@@ -3893,7 +3916,7 @@ struct LbfgsRun {
         int rc = evaluate(1);
         if (rc) return rc;
         HIP_TRY(c, hipSetDevice(lead->device));
-        if (grape::launch_lbfgs_select(st, 1, lead->stream, signal(), 1) != hipSuccess)
+        if (noted([&] { return grape::launch_lbfgs_select(st, 1, lead->stream, signal(), 1); }) != hipSuccess)
             return fail(c, GRAPE_ERR_HIP, "grape_lbfgs: launch failed");
         return dots();
     }
@@ -3902,7 +3925,7 @@ struct LbfgsRun {
     {
         if (!mb) return GRAPE_OK;
         HIP_TRY(c, hipSetDevice(lead->device));
-        if (grape::launch_lbfgs_dots(st, lead->stream) != hipSuccess)
+        if (noted([&] { return grape::launch_lbfgs_dots(st, lead->stream); }) != hipSuccess)
             return fail(c, GRAPE_ERR_HIP, "grape_lbfgs: launch failed");
         return GRAPE_OK;
     }
@@ -3910,7 +3933,7 @@ struct LbfgsRun {
     int phi(double alpha, bool have_trial, double &f, double &df)
     {
         HIP_TRY(c, hipSetDevice(lead->device));
-        if (!have_trial && grape::launch_lbfgs_trial(st, alpha, lead->stream) != hipSuccess)
+        if (!have_trial && noted([&] { return grape::launch_lbfgs_trial(st, alpha, lead->stream); }) != hipSuccess)
             return fail(c, GRAPE_ERR_HIP, "grape_lbfgs: launch failed");
         int rc = probe();
         if (rc) return rc;
@@ -4206,7 +4229,7 @@ extern "C" int grape_lbfgs(grape_ctx *c, const double *x0, const grape_lbfgs_opt
     rc = run.evaluate(1);
     if (rc) return cleanup(rc);
     if (hipSetDevice(lead->device) != hipSuccess) return cleanup(fail(c, GRAPE_ERR_HIP, "grape_lbfgs: hipSetDevice failed"));
-    if (grape::launch_lbfgs_init(st, lead->stream, run.signal()) != hipSuccess)
+    if (run.noted([&] { return grape::launch_lbfgs_init(st, lead->stream, run.signal()); }) != hipSuccess)
         return cleanup(fail(c, GRAPE_ERR_HIP, "grape_lbfgs: launch failed"));
     rc = run.wait();
     if (rc) return cleanup(rc);
@@ -4232,12 +4255,12 @@ extern "C" int grape_lbfgs(grape_ctx *c, const double *x0, const grape_lbfgs_opt
             if (top > 40 || top < -60) { tried += B; continue; }
             const double alpha0 = std::ldexp(1.0, top);
             HIP_TRY(c, hipSetDevice(lead->device));
-            if (grape::launch_lbfgs_direction(st, B, alpha0, lead->stream) != hipSuccess)
+            if (run.noted([&] { return grape::launch_lbfgs_direction(st, B, alpha0, lead->stream); }) != hipSuccess)
                 return fail(c, GRAPE_ERR_HIP, "grape_lbfgs: launch failed");
             int r = run.evaluate(B);
             if (r) return r;
             HIP_TRY(c, hipSetDevice(lead->device));
-            if (grape::launch_lbfgs_select(st, B, lead->stream, run.signal(), 0) != hipSuccess)
+            if (run.noted([&] { return grape::launch_lbfgs_select(st, B, lead->stream, run.signal(), 0); }) != hipSuccess)
                 return fail(c, GRAPE_ERR_HIP, "grape_lbfgs: launch failed");
             r = run.wait();
             if (r) return r;
@@ -4251,12 +4274,12 @@ extern "C" int grape_lbfgs(grape_ctx *c, const double *x0, const grape_lbfgs_opt
         const grape::DoneSignal ds = with_signal ? run.signal() : grape::DoneSignal();
         if (commit && run.mb) {
             // (the dot products of the accepted trial point are in st.dots: lbfgs_dots_kernel ran behind its evaluation)
-            if (grape::launch_lbfgs_step_mb(st, alpha_acc, lead->stream, ds) != hipSuccess)
+            if (run.noted([&] { return grape::launch_lbfgs_step_mb(st, alpha_acc, lead->stream, ds); }) != hipSuccess)
                 return fail(c, GRAPE_ERR_HIP, "grape_lbfgs: launch failed");
             std::swap(st.sc, st.sc_out);                      // the new iterate's scalars: what every later launch reads
             return GRAPE_OK;
         }
-        if (grape::launch_lbfgs_step(st, commit, lead->stream, ds) != hipSuccess)
+        if (run.noted([&] { return grape::launch_lbfgs_step(st, commit, lead->stream, ds); }) != hipSuccess)
             return fail(c, GRAPE_ERR_HIP, "grape_lbfgs: launch failed");
         return GRAPE_OK;
     };
@@ -4377,6 +4400,11 @@ extern "C" int grape_lbfgs(grape_ctx *c, const double *x0, const grape_lbfgs_opt
     result->probes = B;
     result->line_search = o.line_search;
     result->ladder_fallbacks = hz_fallbacks;
+    if (!run.launched.empty()) {                             // behind the kernels of the run's last evaluation
+        std::string &log = lead->kernel_log;
+        if (!log.empty()) log.push_back(';');
+        log += run.launched;
+    }
     c->evaluated = true;
     return cleanup(GRAPE_OK);
 }

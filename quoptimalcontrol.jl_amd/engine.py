@@ -713,7 +713,8 @@ class GrapeEngine:
 
     def kernel_names(self):
         """The kernels the last evaluation launched, in launch order (grape_get_kernel_names): the names a rocprofv3
-        kernel trace shows, without namespace and template arguments."""
+        kernel trace shows, without namespace and template arguments.  After lbfgs(): the run's last evaluation, then the
+        optimiser's own kernels, each name once in order of first launch."""
         need = self._lib.grape_get_kernel_names(self._h, None, 0)
         if need < 0:
             self._check(need)
