@@ -598,6 +598,63 @@ int grape_eval_observables_device(grape_ctx *ctx, const double *d_x, int32_t n_o
 int grape_eval_vjp_device(grape_ctx *ctx, const double *d_x, int32_t n_obs, int32_t per_member, const double *d_O,
                           const double *d_ybar, const double *d_Xbar_final, double *d_G, void *stream);
 
+/* ABI v8 (additive).  The Jacobian-vector product of the trajectory read-out: the forward-mode twin of grape_eval_vjp.  Given
+ * a direction xdot in control space it returns how every expectation value along the trajectory, and the final state of every
+ * member, move to first order -- what a Gauss-Newton / Levenberg-Marquardt step on a loss on y needs next to the pull-back,
+ * a linear-response read-out, and the jvp of a forward-mode autograd framework.
+ *   x, n_obs, per_member, O   exactly as in grape_eval_observables / grape_eval_vjp
+ *   xdot       host f64, the shape and coordinates of x: (K, N), or (K, M) in parameter mode; the raw u-direction under bounds
+ *   ydot       host c128 (N+1, n_obs, E), the layout of y; nullable
+ *   Xdot_final host c128 (n, m, E), the layout of X_final; nullable (but not both)
+ * With the states and propagators of the physical pulse and the physical direction xdot_phys:
+ *   Xdot_{k,0}   = 0
+ *   Xdot_{k,s+1} = P_{k,s} Xdot_{k,s} + ( sum_c xdot_phys[c,s] (-i dt B_kc) ) X_{k,s+1}        s = 0 .. N-1
+ *   ydot[s,j,k]  = tr(O_kj' Xdot_{k,s})         (ydot[0,.,.] = 0, written)
+ *   Xdot_final_k = Xdot_{k,N}
+ * FIRST ORDER in dt: the linearisation of grape_eval_vjp, whose exact transpose this is -- for any cotangents, with
+ * G = grape_eval_vjp(ybar, Xbar_final) on the same context,
+ *   sum Re(conj(ybar) ydot) + sum_k Re tr(Xbar_k' Xdot_final_k) = sum_{c,t} G[c,t] xdot[c,t]
+ * holds to rounding, in the coordinates of x.  Against central differences of grape_eval_observables on a smooth pulse the
+ * deviation falls by ~4 per 4x in N.  An exact tangent is not offered.
+ * With grape_set_bounds and / or grape_set_basis in force xdot_phys = s * (xdot phi^T): the expansion without x0 (phi is the
+ * identity without a basis) times the slope array s of this very evaluation (1 without bounds) -- the transpose of what the
+ * pull-back's tail does (basis_expand_kernel / bounds_tangent_kernel in tangent mode).  No ensemble weight, penalty, running
+ * cost or risk enters.
+ * The call runs ONE evaluation of x exactly as the context is configured and discards its [G, F]; behind the sweep of every
+ * member block (the running-cost kernels, if any) trajectory_jvp_kernel reads the stored propagators -- one workgroup per
+ * member, one lane per time chunk, two forward walks whatever n_obs is.  Members are independent: there is no sum over
+ * members.  Blocking, ordered behind an in-flight grape_eval_device; afterwards grape_get_kernel_names includes the kernel.
+ * An eval -> jvp -> eval sequence returns the first evaluation's bits; results are bitwise reproducible call to call; a
+ * member-chunked context returns the unchunked context's bits; a standing running cost, penalties or risk do not change a bit.
+ * Every operation is linear in xdot: 2 xdot returns twice the bits, -xdot the negated bits, 0 returns 0.
+ * Served: the contexts grape_eval_vjp serves -- kernel family 0 (n = 2, 3, 4), GRAPE_UNITARY_GATE with any m, Hermitian and
+ * non-Hermitian generators, both variants, gradient = 0 and objective = 0, single-device contexts without communicator or
+ * mailbox, member-chunked contexts, max_batch > 1 (the call takes one array) and forced slices_per_lane / waves_per_member
+ * included.  Refused before anything runs, GRAPE_ERR_UNSUPPORTED with grape_eval_vjp's reasons ("dimension", "StateTransfer",
+ * "exact", "multi-device", "communicator").
+ * GRAPE_ERR_INVALID_ARG: null x or xdot; ydot and Xdot_final both NULL; n_obs outside 0..16; n_obs = 0 with a non-NULL ydot;
+ * n_obs > 0 with a NULL O; per_member other than 0 or 1; a non-finite entry of O or xdot ("not finite").  The context's
+ * refusals are checked first.  Before grape_set_operators: GRAPE_ERR_NOT_READY.  After any refusal the context evaluates
+ * exactly as before.  Non-finite x propagates NaN. */
+int grape_eval_jvp(grape_ctx *ctx, const double *x, const double *xdot, int32_t n_obs, int32_t per_member, const double *O,
+                   double *ydot, double *Xdot_final);
+
+/* ABI v8 (additive).  The device form of grape_eval_jvp, under the rules of grape_eval_observables_device /
+ * grape_eval_vjp_device: every array lives in device memory of the context's GPU (d_xdot f64 in the layout of d_x, d_ydot c128
+ * (N+1, n_obs, E), d_Xdot_final c128 (n, m, E)), the call is asynchronous on `stream`, nothing is synchronised, nothing is
+ * staged (without a pulse map the kernel reads d_xdot in place; with one, the tangent map writes the physical direction into
+ * scratch of the context, which grows only behind a pending device call).  Device arrays are NOT checked for non-finite
+ * entries; everything else is validated as in the host form, the context's refusals first.  Results are bit for bit the host
+ * form's.  There is one instance of the kernel (no staged one).
+ * With a non-NULL d_x on a context that is not member-chunked the call sets the "trajectory valid" flag, exactly as the other
+ * two device forms do.  d_x = NULL pushes xdot forward along the stored trajectory of the last device form: only the tangent
+ * map and trajectory_jvp_kernel run, no sweep, and the bits are those of the call with d_x given; with the flag clear, or on a
+ * member-chunked context, GRAPE_ERR_NOT_READY with grape_eval_vjp_device's messages.  A reuse call keeps the flag set, so
+ * grape_eval_vjp_device(d_x = NULL) may follow it: the Gauss-Newton inner loop (one J v, one J' w per CG iteration at one
+ * linearisation point). */
+int grape_eval_jvp_device(grape_ctx *ctx, const double *d_x, const double *d_xdot, int32_t n_obs, int32_t per_member,
+                          const double *d_O, double *d_ydot, double *d_Xdot_final, void *stream);
+
 /* Device-resident L-BFGS: stands in for
  *     Optim.optimize(Optim.only_fg!(topt), x0, Optim.LBFGS(), optim_options)       src/solve.jl:138, :244
  * with x, g, the (s, y) history and the line-search trial points kept on the GPU; per evaluation the host

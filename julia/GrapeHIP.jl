@@ -260,6 +260,37 @@ function observables(ctx::GrapeContext, x::Matrix{Float64}, O::Array{ComplexF64}
     y, Xf, F[]
 end
 
+# grape_eval_jvp: the Jacobian-vector product of `observables` -- how y and X_final move to first order (in dt too) when x
+# moves along xdot, an array of x's shape:  ydot[s+1, j, k] = tr(O_kj' Xdot_{k,s}),  Xdot_final = Xdot_{k,N}.  The exact transpose
+# of grape_eval_vjp; what a Gauss-Newton step on a loss on y, or a linear-response read-out, needs.  O as in `observables`.
+# Returns (ydot (N+1, n_obs, E), Xdot_final (n, m, E)).  n = 2..4, UnitaryGate, single-device contexts.  (Written, NOT executed,
+# like `observables`; the Python binding makes the same call and is tested on the GPU.)
+function observables_jvp(ctx::GrapeContext, x::Matrix{Float64}, xdot::Matrix{Float64}, O::Array{ComplexF64})
+    size(x) == (ctx.K, ctx.N) || throw(DimensionMismatch("x must be (n_controls, n_slices)"))
+    size(xdot) == size(x) || throw(DimensionMismatch("xdot must have the shape of x"))
+    n_obs = size(O, ndims(O))
+    (ndims(O) == 3 && size(O) == (ctx.n, ctx.m, n_obs)) || (ndims(O) == 4 && size(O) == (ctx.n, ctx.m, ctx.E, n_obs)) ||
+        throw(DimensionMismatch("O must be (n, m, n_obs) or (n, m, E, n_obs) with the context's n, m and E"))
+    1 <= n_obs <= 16 || throw(ArgumentError("observables_jvp: 1 to 16 probes"))
+    ydot = Array{ComplexF64}(undef, ctx.N + 1, n_obs, ctx.E)
+    Xdf = Array{ComplexF64}(undef, ctx.n, ctx.m, ctx.E)
+    GC.@preserve x xdot O ydot Xdf check(ctx, ccall((:grape_eval_jvp, libgrape), Cint,
+                                                    (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{ComplexF64}),
+                                                    ctx.handle, x, xdot, Int32(n_obs), Int32(ndims(O) == 4 ? 1 : 0), O, ydot, Xdf))
+    ydot, Xdf
+end
+
+# grape_eval_jvp_device: the same on device memory of the context's GPU (raw device pointers, e.g. of AMDGPU.jl arrays in the
+# layouts above; C_NULL for an output that is not wanted, not both), asynchronous on `stream`.  d_x = C_NULL pushes d_xdot forward
+# along the trajectory the last device form left in the workspace, without a sweep.
+function observables_jvp_device(ctx::GrapeContext, d_x::Ptr{Cvoid}, d_xdot::Ptr{Cvoid}, n_obs::Integer, per_member::Bool,
+                                d_O::Ptr{Cvoid}, d_ydot::Ptr{Cvoid}, d_Xdot_final::Ptr{Cvoid}; stream::Ptr{Cvoid} = C_NULL)
+    check(ctx, ccall((:grape_eval_jvp_device, libgrape), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                     ctx.handle, d_x, d_xdot, Int32(n_obs), Int32(per_member ? 1 : 0), d_O, d_ydot, d_Xdot_final, stream))
+    ctx
+end
+
 "The kernels the last evaluation launched, in launch order (grape_get_kernel_names, ABI v4)."
 function kernel_names(ctx::GrapeContext)
     need = ccall((:grape_get_kernel_names, libgrape), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Cint), ctx.handle, C_NULL, 0)

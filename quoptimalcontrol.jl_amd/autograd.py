@@ -12,6 +12,10 @@ torch is imported here and nowhere else in the package: `import quoptimalcontrol
     loss = -torch.log(1 - y[0, 0].abs() ** 2).sum()          # a log-barrier on a population
     loss.backward()                                         # x.grad: first order in dt, like the running cost's gradient
 
+Forward mode: both functions carry a jvp, so torch.autograd.forward_ad dual numbers pass through them -- the tangent of
+(y, X_final) along the tangent of x is GrapeEngine.observe_jvp's (grape_eval_jvp), the exact transpose of the backward.
+(torch.func.jvp needs the setup_context form of a Function and is not served.)
+
 trajectory_device is the same for a workflow that lives on the GPU: x, y, X_final, the loss and x.grad are CUDA tensors on the
 engine's device, the read-out and the pull-back run on torch's current stream (GrapeEngine.observe_device /
 observe_vjp_device) and nothing crosses to the host.
@@ -30,7 +34,7 @@ class _Trajectory(torch.autograd.Function):
         xn = x.detach().numpy()
         out = engine.observe(xn, ops, per_member=per_member, final=final)
         y, Xf = out if final else (out, None)
-        ctx.engine, ctx.ops, ctx.per_member = engine, ops, per_member
+        ctx.engine, ctx.ops, ctx.per_member, ctx.final = engine, ops, per_member, final
         ctx.xn = np.array(xn, copy=True)
         ctx.set_materialize_grads(False)
         y_t = torch.from_numpy(y)
@@ -46,6 +50,15 @@ class _Trajectory(torch.autograd.Function):
         xb = None if xbar is None else xbar.detach().resolve_conj().numpy()
         G = ctx.engine.observe_vjp(ctx.xn, ctx.ops, ybar=yb, xbar_final=xb, per_member=ctx.per_member)
         return torch.from_numpy(G), None, None, None, None
+
+    @staticmethod
+    def jvp(ctx, xdot, *_):
+        """forward mode: the tangents of (y, X_final) -- of y alone with final=False -- along the tangent of x"""
+        xd = xdot.detach().numpy()
+        out = ctx.engine.observe_jvp(ctx.xn, xd, ctx.ops, per_member=ctx.per_member, final=ctx.final)
+        if ctx.final:
+            return torch.from_numpy(out[0]), torch.from_numpy(out[1])
+        return torch.from_numpy(out)
 
 
 def trajectory(engine, x, ops, per_member=False, final=True):
@@ -80,7 +93,7 @@ class _TrajectoryDevice(torch.autograd.Function):
         Xf = torch.empty((E, m, n), dtype=torch.complex128, device=x.device) if final else None
         stream = torch.cuda.current_stream(x.device).cuda_stream
         engine.observe_device(xf.data_ptr(), n_obs, per_member, Of.data_ptr(), y.data_ptr(), Xf.data_ptr() if final else 0, 0, stream)
-        ctx.engine, ctx.per_member, ctx.n_obs, ctx.reuse = engine, per_member, n_obs, reuse
+        ctx.engine, ctx.per_member, ctx.n_obs, ctx.reuse, ctx.final = engine, per_member, n_obs, reuse, final
         ctx.xf, ctx.Of, ctx.stamp = xf, Of, engine.calls
         ctx.set_materialize_grads(False)
         if final:
@@ -109,6 +122,33 @@ class _TrajectoryDevice(torch.autograd.Function):
         if not done:
             eng.observe_vjp_device(ctx.xf.data_ptr(), *args)
         return G.t(), None, None, None, None, None
+
+    @staticmethod
+    def jvp(ctx, xdot, *_):
+        """forward mode, under the backward's rule: along the stored trajectory (d_x = 0) when reuse is set and nothing has
+        touched the engine since, else with the saved x.  Either way the workspace then holds the trajectory of the saved x,
+        so the stamp moves on and a backward (or another jvp) that follows directly may reuse it."""
+        eng = ctx.engine
+        E, n, m, N = eng.E, eng.n, eng.m, eng.N
+        xdf = xdot.detach().t().contiguous()                 # (K, cols) column-major
+        yd = torch.empty((E, ctx.n_obs, N + 1), dtype=torch.complex128, device=xdf.device)
+        Xd = torch.empty((E, m, n), dtype=torch.complex128, device=xdf.device) if ctx.final else None
+        stream = torch.cuda.current_stream(xdf.device).cuda_stream
+        args = (xdf.data_ptr(), ctx.n_obs, ctx.per_member, ctx.Of.data_ptr(), yd.data_ptr(), Xd.data_ptr() if ctx.final else 0, stream)
+        done = False
+        if ctx.reuse and eng.calls == ctx.stamp:
+            try:
+                eng.observe_jvp_device(0, *args)
+                done = True
+            except Exception as exc:                         # (NOT_READY: a call that bypassed the engine's counter, a member chunk)
+                if getattr(exc, "status", None) != -5:
+                    raise
+        if not done:
+            eng.observe_jvp_device(ctx.xf.data_ptr(), *args)
+        ctx.stamp = eng.calls
+        if ctx.final:
+            return yd, Xd.transpose(-1, -2)
+        return yd
 
 
 def trajectory_device(engine, x, ops, per_member=False, final=True, reuse=True):

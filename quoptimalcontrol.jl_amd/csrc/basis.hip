@@ -16,6 +16,10 @@
 // with a = x0 + theta phi^T (fused into the two kernels above: no second pass over x, the projection keeps its order), or
 // a = the entry point's argument when no basis is in force (M = 0: bounds_saturate_kernel / bounds_slope_kernel).  With
 // bounded == 0 the two basis kernels do exactly the arithmetic they always did.
+//
+// grape_eval_jvp (BasisOp::tangent) pushes a DIRECTION through the same seam: xdot[c,t] = s[c,t] sum_m thetadot[c,m] phi_b[t,m],
+// the expansion without x0 and without the saturation, times the slope array the evaluation's own expansion has just written
+// (read here, not written; 1 without bounds; M = 0: bounds_tangent_kernel) -- the transpose of the projection.
 #include "done_signal.hpp"
 
 namespace grape {
@@ -51,7 +55,7 @@ __global__ __launch_bounds__(256) void basis_expand_kernel(const BasisOp op, con
     const bool live = t < op.N;
     const double *ph = op.phi + (size_t)(op.n_bases == 1 ? 0 : c) * op.N * op.M + (live ? t : 0);
     const double *th = theta + (size_t)b * op.K * op.M + c;
-    double acc = live && op.x0 ? op.x0[c + (size_t)op.K * t] : 0.0;
+    double acc = live && op.x0 && !op.tangent ? op.x0[c + (size_t)op.K * t] : 0.0;
     for (int m0 = 0; m0 < op.M; m0 += kBasisTile) {
         const int cnt = op.M - m0 < kBasisTile ? op.M - m0 : kBasisTile;
         __syncthreads();
@@ -64,7 +68,10 @@ __global__ __launch_bounds__(256) void basis_expand_kernel(const BasisOp op, con
     }
     if (live) {
         const size_t i = (size_t)b * op.K * op.N + c + (size_t)op.K * t;
-        if (op.bounded) {
+        if (op.tangent) {                                    // grape_eval_jvp: the direction, times the slope in place
+            if (op.bounded)
+                acc *= op.slope[i];
+        } else if (op.bounded) {
             double s;
             acc = saturate(acc, op.lo[c], op.hi[c], s);
             op.slope[i] = s;
@@ -126,6 +133,15 @@ __global__ __launch_bounds__(256) void bounds_saturate_kernel(const BasisOp op, 
     op.slope[i] = s;
 }
 
+// grape_eval_jvp under bounds without a basis: the direction times the slope array of the evaluation (BasisOp::tangent)
+__global__ __launch_bounds__(256) void bounds_tangent_kernel(const BasisOp op, const double *__restrict__ udot,
+                                                             double *__restrict__ xdot)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < (size_t)op.K * op.N)
+        xdot[i] = udot[i] * op.slope[i];
+}
+
 // ... and behind it, the evaluation's LAST kernel in this mode: out = n_x blocks of { G_tot s, F } from the complete summed
 // rows, published as basis_project_kernel publishes.
 __global__ __launch_bounds__(256) void bounds_slope_kernel(const BasisOp op, const double *__restrict__ rows,
@@ -154,11 +170,17 @@ hipError_t launch_basis(const BasisOp &op, const double *src, double *dst, hipSt
         return hipErrorInvalidValue;
     if (op.no_f && (!op.project || op.n_x != 1))
         return hipErrorInvalidValue;
+    if (op.tangent && (op.project || op.n_x != 1))
+        return hipErrorInvalidValue;
     done.basis = nullptr;                                    // (a host address: nothing for the device)
     if (op.M == 0) {
         const size_t n = ((size_t)op.K * op.N + (op.project && !op.no_f ? 1 : 0)) * op.n_x;
         if (n > 0x7fffff00u)
             return hipErrorInvalidValue;
+        if (op.tangent) {
+            GRAPE_LAUNCH(bounds_tangent_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, op, src, dst);
+            return hipGetLastError();
+        }
         if (!op.project) {
             GRAPE_LAUNCH(bounds_saturate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, op, src, dst);
             return hipGetLastError();

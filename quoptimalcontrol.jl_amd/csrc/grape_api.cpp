@@ -224,7 +224,25 @@ struct grape_ctx {
     double2 *obs_y_call = nullptr, *obs_xf_call = nullptr;
     double *vjp_G_call = nullptr;              // K N: the summed physical row (d_vjp_g, or the caller's G without a pulse map)
     int obs_staged = 0, vjp_staged = 0;
-    int lds_cap = 0;                           // LDS bytes a workgroup of this device may hold (queried by the first device form)
+    // grape_eval_jvp (jvp.hip): behind the sweep (the running-cost kernels) of every member block of ONE evaluation,
+    // trajectory_jvp_kernel pushes the caller's direction forward along the stored propagators.  jvp_on is set by the entry
+    // point around that evaluation only.  Under a pulse map the direction goes through the map's tangent first (BasisOp::tangent,
+    // into d_jvp_xphys) behind the expansion of the same evaluation, whose slope array it reads.  The buffers are allocated by
+    // the first call that needs them and only ever grow; d_jvp_xphys is shared by both forms, so it grows only behind a pending
+    // device call.  *_call: the buffers of the host form or the caller's own device arrays (the device form).
+    bool jvp_on = false;
+    int jvp_n = 0, jvp_per_member = 0;
+    bool jvp_has_y = false, jvp_has_x = false;
+    double2 *d_jvp_O = nullptr;                // the probes of the call
+    double *d_jvp_xdot = nullptr;              // the direction in the coordinates of x (K M)
+    double *d_jvp_xphys = nullptr;             // the direction in the coordinates of the physical pulse (K N): pulse maps only
+    double2 *d_jvp_ydot = nullptr;             // (N + 1, n_obs, E)
+    double2 *d_jvp_xf = nullptr;               // (n, m, E)
+    size_t jvp_O_bytes = 0, jvp_xdot_bytes = 0, jvp_xphys_bytes = 0, jvp_ydot_bytes = 0, jvp_xf_bytes = 0;
+    const double2 *jvp_O_call = nullptr;
+    const double *jvp_xdot_call = nullptr;
+    double2 *jvp_ydot_call = nullptr, *jvp_xf_call = nullptr;
+    int lds_cap = 0;                          // LDS bytes a workgroup of this device may hold (queried by the first device form)
     // The workspace holds the complete trajectory (every member's propagators, and the slope array of a pulse map) of the last
     // device form: grape_eval_vjp_device may pull back along it without a sweep (d_x == NULL).  Set by a successful device form
     // that ran an evaluation on a context that is not member-chunked; cleared by everything else that evaluates or changes a
@@ -625,6 +643,7 @@ static void free_all(grape_ctx *c)
     (void)hipFree(c->d_rc_R); (void)hipFree(c->d_rc_rho); (void)hipFree(c->d_rc_xs); (void)hipFree(c->d_rc_rows);
     (void)hipFree(c->d_obs_O); (void)hipFree(c->d_obs_y); (void)hipFree(c->d_obs_xf);
     (void)hipFree(c->d_vjp_O); (void)hipFree(c->d_vjp_ybar); (void)hipFree(c->d_vjp_xbar); (void)hipFree(c->d_vjp_part); (void)hipFree(c->d_vjp_g); (void)hipFree(c->d_vjp_out);
+    (void)hipFree(c->d_jvp_O); (void)hipFree(c->d_jvp_xdot); (void)hipFree(c->d_jvp_xphys); (void)hipFree(c->d_jvp_ydot); (void)hipFree(c->d_jvp_xf);
     (void)hipFree(c->d_basis_phi); (void)hipFree(c->d_basis_x0);
     (void)hipFree(c->d_bounds); (void)hipFree(c->d_slope);
     (void)hipFree(c->d_fom_member); (void)hipFree(c->d_fom_rows);
@@ -2552,6 +2571,38 @@ static SweepParams vjp_params(const grape_ctx *c, const SweepParams &q, int lo)
     return v;
 }
 
+// grape_eval_jvp: the launch of trajectory_jvp_kernel for the members from `lo` on that `q` sweeps (or swept:
+// grape_eval_jvp_device's reuse)
+static SweepParams jvp_params(const grape_ctx *c, const SweepParams &q, int lo)
+{
+    SweepParams v = q;
+    v.jvp_only = 1;
+    v.jvp_n = c->jvp_has_y ? c->jvp_n : 0;
+    v.jvp_m = c->m;
+    v.jvp_per_member = c->jvp_per_member;
+    v.jvp_CH = c->CH;
+    v.jvp_Etot = c->cfg.n_ensemble;
+    v.jvp_E0 = lo;
+    v.jvp_O = c->jvp_O_call;
+    v.jvp_xdot = pulse_map(c) ? c->d_jvp_xphys : c->jvp_xdot_call;
+    v.jvp_ydot = c->jvp_has_y ? c->jvp_ydot_call : nullptr;
+    v.jvp_xf = c->jvp_has_x ? c->jvp_xf_call : nullptr;
+    return v;
+}
+
+// grape_eval_jvp under a pulse map: the caller's direction -> the coordinates of the physical pulse, slope * (xdot phi')
+// into d_jvp_xphys (basis.hip, BasisOp::tangent).  The slope array it reads is the one the expansion of the same evaluation
+// has written in front of it on `stream` (or the stored trajectory's: the reuse).  Logged into the open kernel log.
+static int jvp_tangent_map(grape_ctx *c, hipStream_t stream)
+{
+    grape::BasisOp op = basis_op(c, false, 1);
+    op.tangent = 1;
+    grape::DoneSignal d;
+    d.basis = &op;
+    HIP_TRY(c, grape::launch_copy(c->jvp_xdot_call, c->d_jvp_xphys, (int)KN(c), stream, d));
+    return GRAPE_OK;
+}
+
 // one shard: sweep kernel(s) + the on-device ensemble reduction into d_fg; nothing is synchronised
 static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream_t stream, int n_x = 1,
                         grape::DoneSignal done = grape::DoneSignal())
@@ -2594,6 +2645,10 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
         if (rc) return rc;
     }
     KernelLogScope log_scope(&c->kernel_log);
+    if (c->jvp_on && pulse_map(c)) {                         // (the expansion in front has written this evaluation's slope array)
+        const int rc = jvp_tangent_map(c, stream);
+        if (rc) return rc;
+    }
     c->mf_wait = 0;
     SweepParams p = sweep_params(c, d_x, n_x);
     p.props = c->d_props;
@@ -2693,6 +2748,10 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
                     v.vjp_only = 2;
                     HIP_TRY(c, launch_small_family(c, 0, mode, v, stream));
                 }
+            }
+            if (c->jvp_on) {                                 // grape_eval_jvp: the direction of these members, pushed forward
+                SweepParams v = jvp_params(c, q, lo);
+                HIP_TRY(c, launch_small_family(c, 0, mode, v, stream));
             }
             if (exact) {                                     // exact gradient + objective from the stored trajectory
                 grape::ExactParams xq{};
@@ -3406,15 +3465,41 @@ static int obs_check(grape_ctx *c, const std::string &who, const void *x, int32_
     return GRAPE_OK;
 }
 
+// why the pull-back and the push-forward along the trajectory (grape_eval_vjp, grape_eval_jvp and their device forms) do
+// not serve this context; null: they do
+static const char *why_linearisation_not_served(const grape_ctx *c)
+{
+    if (const char *why = why_exchange_not_served(c)) return why;
+    if (c->family != 0) return "the operator dimension must be 2, 3 or 4 (the sweeps that leave every propagator in the workspace)";
+    if (c->cfg.sys_type != GRAPE_UNITARY_GATE) return "StateTransfer / CoherenceTransfer are not served (the sandwich needs a second term)";
+    if (c->cfg.gradient == GRAPE_GRADIENT_EXACT) return "gradient = exact is not served";
+    if (c->cfg.objective != GRAPE_OBJECTIVE_FOM) return "objective = c1 (the exact objective) is not served";
+    return nullptr;
+}
+
+// grape_eval_jvp / grape_eval_jvp_device: vjp_check's order with the direction in place of G and the tangents in place of
+// the cotangents
+static int jvp_check(grape_ctx *c, const std::string &who, const void *x, bool x_needed, const void *xdot, int32_t n_obs,
+                     int32_t per_member, const void *O, const void *ydot, const void *Xdot_final)
+{
+    if (const char *why = why_linearisation_not_served(c)) return fail(c, GRAPE_ERR_UNSUPPORTED, who + ": " + why);
+    if (!x && x_needed) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": x is null");
+    if (!xdot) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": xdot is null");
+    if (!ydot && !Xdot_final) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": ydot and Xdot_final are both null");
+    if (n_obs < 0 || n_obs > 16)
+        return fail(c, GRAPE_ERR_INVALID_ARG, who + ": n_obs = " + std::to_string(n_obs) + " (must be in 0..16)");
+    if (n_obs == 0 && ydot) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": n_obs = 0 with a non-null ydot");
+    if (n_obs > 0 && !O) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": n_obs > 0 with a null O");
+    if (per_member != 0 && per_member != 1)
+        return fail(c, GRAPE_ERR_INVALID_ARG, who + ": per_member = " + std::to_string(per_member) + " (must be 0 or 1)");
+    if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, who + ": operators not set");
+    return GRAPE_OK;
+}
+
 static int vjp_check(grape_ctx *c, const std::string &who, const void *x, bool x_needed, int32_t n_obs, int32_t per_member,
                      const void *O, const void *ybar, const void *Xbar_final, const void *G)
 {
-    const char *why = why_exchange_not_served(c);
-    if (why) {}
-    else if (c->family != 0) why = "the operator dimension must be 2, 3 or 4 (the sweeps that leave every propagator in the workspace)";
-    else if (c->cfg.sys_type != GRAPE_UNITARY_GATE) why = "StateTransfer / CoherenceTransfer are not served (the sandwich needs a second term)";
-    else if (c->cfg.gradient == GRAPE_GRADIENT_EXACT) why = "gradient = exact is not served";
-    else if (c->cfg.objective != GRAPE_OBJECTIVE_FOM) why = "objective = c1 (the exact objective) is not served";
+    const char *why = why_linearisation_not_served(c);
     if (why) return fail(c, GRAPE_ERR_UNSUPPORTED, who + ": " + why);
     if (!x && x_needed) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": x is null");
     if (!G) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": G is null");
@@ -3689,6 +3774,122 @@ extern "C" int grape_eval_vjp_device(grape_ctx *c, const double *d_x, int32_t n_
         grape::DoneSignal d;
         d.basis = &op;
         HIP_TRY(c, grape::launch_copy(c->d_vjp_g, d_G, (int)kp, st, d));
+    }
+    HIP_TRY(c, hipEventRecord(c->ev_dev, st));
+    c->dev_pending = true;
+    c->traj_valid = !chunked(c);
+    return GRAPE_OK;
+}
+
+// ---- grape_eval_jvp: one evaluation + the push-forward of the caller's direction along its trajectory ------------------------
+extern "C" int grape_eval_jvp(grape_ctx *c, const double *x, const double *xdot, int32_t n_obs, int32_t per_member,
+                              const double *O, double *ydot, double *Xdot_final)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_jvp: null context");
+    const char *who = "grape_eval_jvp";
+    c->traj_valid = false;
+    if (int rc0 = jvp_check(c, who, x, true, xdot, n_obs, per_member, O, ydot, Xdot_final)) return rc0;
+    const size_t n = (size_t)c->cfg.n, m = (size_t)c->m, E = (size_t)c->cfg.n_ensemble, N = (size_t)c->cfg.n_slices;
+    const size_t n_O = n * m * (per_member ? E : 1) * (size_t)n_obs, n_y = (N + 1) * (size_t)n_obs * E, n_X = n * m * E;
+    const size_t kn = KN(c), kp = KP(c);
+    int rc = check_finite(c, O, 2 * n_O, who, "O", 2);
+    if (rc) return rc;
+    rc = check_finite(c, xdot, kp, who, "xdot");
+    if (rc) return rc;
+    // the direction's buffers are the device form's too, and that one does not block: nothing of it is in flight from here on
+    rc = drain(c, c);
+    if (rc) return rc;
+    const bool want_y = ydot != nullptr && n_obs > 0;
+    if (want_y) {
+        rc = grow(c, &c->d_jvp_O, &c->jvp_O_bytes, sizeof(double2) * n_O, who, "the probes");
+        if (rc) return rc;
+        rc = grow(c, &c->d_jvp_ydot, &c->jvp_ydot_bytes, sizeof(double2) * n_y, who, "the tangents of the expectation values");
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpy(c->d_jvp_O, O, sizeof(double2) * n_O, hipMemcpyHostToDevice));
+    }
+    if (Xdot_final) {
+        rc = grow(c, &c->d_jvp_xf, &c->jvp_xf_bytes, sizeof(double2) * n_X, who, "the tangents of the final states");
+        if (rc) return rc;
+    }
+    rc = grow(c, &c->d_jvp_xdot, &c->jvp_xdot_bytes, sizeof(double) * kp, who, "the direction");
+    if (rc) return rc;
+    if (pulse_map(c)) {
+        rc = grow(c, &c->d_jvp_xphys, &c->jvp_xphys_bytes, sizeof(double) * kn, who, "the direction of the physical pulse");
+        if (rc) return rc;
+    }
+    HIP_TRY(c, hipMemcpy(c->d_jvp_xdot, xdot, sizeof(double) * kp, hipMemcpyHostToDevice));
+    c->jvp_n = n_obs;
+    c->jvp_per_member = per_member;
+    c->jvp_has_y = want_y;
+    c->jvp_has_x = Xdot_final != nullptr;
+    c->jvp_O_call = c->d_jvp_O;
+    c->jvp_xdot_call = c->d_jvp_xdot;
+    c->jvp_ydot_call = c->d_jvp_ydot;
+    c->jvp_xf_call = c->d_jvp_xf;
+    c->jvp_on = true;                                        // enqueue_eval's member blocks end in trajectory_jvp_kernel
+    rc = eval_host(c, 1, x, nullptr, nullptr, who);          // (its [G, F] are not wanted)
+    c->jvp_on = false;
+    if (rc) return rc;
+    // (the evaluation is published by its own last kernel, or by the sweep itself: the push-forward may sit behind that)
+    rc = wait_stream(c, c->stream);
+    if (rc) return rc;
+    if (want_y) HIP_TRY(c, hipMemcpy(ydot, c->d_jvp_ydot, sizeof(double2) * n_y, hipMemcpyDeviceToHost));
+    if (Xdot_final) HIP_TRY(c, hipMemcpy(Xdot_final, c->d_jvp_xf, sizeof(double2) * n_X, hipMemcpyDeviceToHost));
+    return GRAPE_OK;
+}
+
+extern "C" int grape_eval_jvp_device(grape_ctx *c, const double *d_x, const double *d_xdot, int32_t n_obs, int32_t per_member,
+                                     const double *d_O, double *d_ydot, double *d_Xdot_final, void *stream)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_jvp_device: null context");
+    const char *who = "grape_eval_jvp_device";
+    const bool reuse = d_x == nullptr, was_valid = c->traj_valid;
+    c->traj_valid = false;
+    int rc = jvp_check(c, who, d_x, false, d_xdot, n_obs, per_member, d_O, d_ydot, d_Xdot_final);
+    if (rc) return rc;
+    if (reuse && chunked(c))
+        return fail(c, GRAPE_ERR_NOT_READY, std::string(who) + ": d_x is null (reuse), but the workspace of a context under member_chunk "
+                                            "holds one block of members only");
+    if (reuse && !was_valid)
+        return fail(c, GRAPE_ERR_NOT_READY, std::string(who) + ": d_x is null (reuse), but the workspace does not hold the trajectory of a "
+                                            "device form: another call has evaluated, changed a setting or failed since");
+    hipStream_t st = (hipStream_t)stream;
+    rc = traj_device_prologue(c);
+    if (rc) return rc;
+    if (pulse_map(c)) {
+        rc = grow(c, &c->d_jvp_xphys, &c->jvp_xphys_bytes, sizeof(double) * KN(c), who, "the direction of the physical pulse");
+        if (rc) return rc;
+        rc = grow(c, &c->d_vjp_out, &c->vjp_out_bytes, sizeof(double) * (KP(c) + 1), who, "the projected row");
+        if (rc) return rc;
+    }
+    const bool want_y = d_ydot != nullptr && n_obs > 0;
+    c->jvp_n = n_obs;
+    c->jvp_per_member = per_member;
+    c->jvp_has_y = want_y;
+    c->jvp_has_x = d_Xdot_final != nullptr;
+    c->jvp_O_call = (const double2 *)d_O;
+    c->jvp_xdot_call = d_xdot;
+    c->jvp_ydot_call = (double2 *)d_ydot;
+    c->jvp_xf_call = (double2 *)d_Xdot_final;
+    if (!reuse) {
+        c->jvp_on = true;                                    // enqueue_eval's member blocks end in trajectory_jvp_kernel
+        rc = traj_device_eval(c, d_x, pulse_map(c) ? c->d_vjp_out : c->d_fg, st);          // (its [G, F] are not wanted)
+        c->jvp_on = false;
+        if (rc) return rc;
+    } else {
+        // the propagators (and the slope array) of the last device form are in place: the tangent map and the push-forward alone
+        KernelLogScope log_scope(&c->kernel_log);
+        if (pulse_map(c)) {
+            rc = jvp_tangent_map(c, st);
+            if (rc) return rc;
+        }
+        SweepParams q = sweep_params(c, nullptr, 1);
+        q.props = c->d_props;
+        const SweepParams v = jvp_params(c, q, 0);
+        const int mode = c->unitary ? 2 : (c->d_costates ? 1 : 0);
+        HIP_TRY(c, launch_small_family(c, 0, mode, v, st));
     }
     HIP_TRY(c, hipEventRecord(c->ev_dev, st));
     c->dev_pending = true;

@@ -52,6 +52,10 @@ struct BasisOp {
     const double *lo = nullptr, *hi = nullptr; // device (K) each
     double *slope = nullptr;                   // device (K, N, n_x): written by the expansion, read by the projection
     int32_t no_f = 0;                          // project, n_x = 1: dst holds K M entries only, the F slot is neither read nor written
+    // grape_eval_jvp, expand with n_x = 1 only: the TANGENT of the expansion at the point whose slope array is in place,
+    //   dst (K, N) = slope * sum_m src[c, m] phi_b[t, m]   (no x0, no saturation; the slope is READ, 1 without bounds;
+    //   M = 0: dst = src * slope, bounds_tangent_kernel) -- the transpose of what the projection does to a gradient
+    int32_t tangent = 0;
 };
 // optional host-visible completion signal of an evaluation's FINAL kernel (reduce.hip: signal_done);
 // flag == nullptr: none (device-pointer entry points, intermediate kernels)
@@ -199,6 +203,21 @@ struct SweepParams {
     // direct instance, the kernel of the host forms.
     int32_t obs_staged;
     int32_t vjp_staged;
+    // grape_eval_jvp (jvp.hip): launch_sweep_small / launch_sweep_pair hand a launch with jvp_only set to
+    // trajectory_jvp_kernel INSTEAD of the sweep: behind the sweep of the same members (one control array) it reads the
+    // propagators that sweep stored (props, chunk-major with stride jvp_CH), pushes the caller's direction forward along the
+    // trajectory and stores tr(O_kj' Xdot_ks) and Xdot_N.  Members are independent: no sum, no second launch
+    int32_t jvp_only;
+    int32_t jvp_n;           // probes per member, 0..16 (the ydot rows; 0 with jvp_ydot null)
+    int32_t jvp_m;           // state columns m (O, X, Xdot are n x m)
+    int32_t jvp_per_member;  // 0: jvp_O is (n, m, jvp_n), shared; 1: (n, m, jvp_Etot, jvp_n)
+    int32_t jvp_CH;          // time chunks per member = workspace stride (LT, or LT / 2 behind the pair kernel)
+    int32_t jvp_Etot;        // members of the whole ensemble
+    int32_t jvp_E0;          // this launch's first member: offset into the probes and the outputs
+    const double2 *jvp_O;    // the probes, column-major (from member 0 on)
+    const double *jvp_xdot;  // (K, N) column-major: the direction in the coordinates of the PHYSICAL pulse
+    double2 *jvp_ydot;       // (N + 1, jvp_n, jvp_Etot) column-major, nullable
+    double2 *jvp_xf;         // (n, m, jvp_Etot) Xdot_N, nullable
 };
 // static LDS of observe_kernel (vjp = false) / trajectory_vjp_kernel (vjp = true) at operator dimension n with m state
 // columns: the scans' wave totals.  What the host layer subtracts from the device's LDS per workgroup to get the staged
@@ -211,7 +230,9 @@ constexpr size_t traj_static_lds(int n, int m, bool vjp)
 hipError_t run_observe(int n, int sandwich, const SweepParams &p, hipStream_t stream);
 // vjp.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::vjp_only) only
 hipError_t run_trajectory_vjp(int n, const SweepParams &p, hipStream_t stream);
-constexpr int kVjpGroup = 32;                  // members per group of vjp_sum_kernel's tree: vjp_part has ceil(E / 32) rows
+// jvp.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::jvp_only) only
+hipError_t run_trajectory_jvp(int n, const SweepParams &p, hipStream_t stream);
+constexpr int kVjpGroup = 32;                 // members per group of vjp_sum_kernel's tree: vjp_part has ceil(E / 32) rows
 // running_cost.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::rc_only) only
 hipError_t run_running_cost(int n, const SweepParams &p, hipStream_t stream);
 // fom_small.hip; reached through launch_sweep_small (pair = false) / launch_sweep_pair (pair = true) only

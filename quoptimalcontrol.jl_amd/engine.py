@@ -40,7 +40,7 @@ EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_oper
            "grape_set_basis", "grape_get_controls", "grape_set_bounds", "grape_set_risk", "grape_get_risk_weights",
            "grape_comm_unique_id", "grape_comm_attach", "grape_ipc_export", "grape_ipc_attach",
            "grape_eval", "grape_eval_device", "grape_eval_batch", "grape_eval_batch_device", "grape_eval_fom", "grape_eval_observables",
-           "grape_eval_vjp", "grape_eval_observables_device", "grape_eval_vjp_device",
+           "grape_eval_vjp", "grape_eval_observables_device", "grape_eval_vjp_device", "grape_eval_jvp", "grape_eval_jvp_device",
            "grape_lbfgs", "grape_lbfgs_get_trace",
            "grape_get_member_results", "grape_get_trajectory",
            "grape_get_kernel_time", "grape_get_kernel_samples", "grape_get_kernel_names", "grape_get_group_timing", "grape_get_phase_stamps",
@@ -144,6 +144,8 @@ def load_library():
     L.grape_eval_vjp.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp]
     L.grape_eval_observables_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.grape_eval_vjp_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.grape_eval_jvp.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
+    L.grape_eval_jvp_device.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
     L.grape_lbfgs.argtypes = [vp, vp, C.POINTER(GrapeLbfgsOptions), vp, C.POINTER(GrapeLbfgsResult)]
     L.grape_get_member_results.argtypes = [vp, vp, vp]
     L.grape_get_trajectory.argtypes = [vp, i32, vp, vp, vp]
@@ -627,6 +629,42 @@ class GrapeEngine:
         self._check(self._lib.grape_eval_vjp(self._h, _p(xf), n_obs, 1 if per_member else 0, _p(Of), _p(yb), _p(xb), _p(G)))
         return np.ascontiguousarray(G.T)
 
+    def observe_jvp(self, x, xdot, ops, per_member=False, final=False):
+        """grape_eval_jvp: the Jacobian-vector product of observe() -- how its returns move to first order when x (K,N)
+        (theta / u with a basis / bounds in force) moves along xdot, an array of x's shape and coordinates.  ops as in observe
+        (None with final=True for the final states alone).  Returns ydot (E, n_obs, N+1) complex128 -- then Xdot_final
+        (E, n, m) with final=True.  First order in dt, the exact transpose of observe_vjp: sum Re(conj(ybar) ydot) +
+        sum Re(conj(xbar_final) Xdot_final) = sum(observe_vjp(x, ops, ybar, xbar_final) * xdot) to rounding.  n = 2..4,
+        UnitaryGate, single-device contexts (include/grape_hip.h)."""
+        x = np.asarray(x, dtype=np.float64)
+        xd = np.asarray(xdot, dtype=np.float64)
+        if x.shape != (self.K, self._cols):
+            raise ValueError(f"x must be ({self.K},{self._cols})")
+        if xd.shape != x.shape:
+            raise ValueError(f"observe_jvp: xdot must be ({self.K},{self._cols}), the shape of x")
+        n, m, E, N = self.n, self.m, self.E, self.N
+        if ops is None:
+            if not final:
+                raise ValueError("observe_jvp: nothing asked for (ops=None needs final=True)")
+            n_obs, Of, yd = 0, None, None
+        else:
+            O = np.asarray(ops, dtype=np.complex128)
+            if not per_member and O.ndim == 2:
+                O = O[None]
+            want = (E, O.shape[1] if O.ndim == 4 else 0, n, m) if per_member else (O.shape[0] if O.ndim == 3 else 0, n, m)
+            if O.shape != want or not 1 <= O.shape[-3] <= 16:
+                raise ValueError(f"observe_jvp: ops must be {'(E, n_obs, n, m)' if per_member else '(n_obs, n, m)'} with "
+                                 f"E = {E}, n = {n}, m = {m} and 1 <= n_obs <= 16")
+            n_obs = O.shape[-3]
+            Of = _cm(np.swapaxes(O, 0, 1) if per_member else O)
+            yd = np.empty((E, n_obs, N + 1), np.complex128)
+        Xf = np.empty((E, m, n), np.complex128) if final else None
+        xf, xdf = np.ascontiguousarray(x.T), np.ascontiguousarray(xd.T)
+        self._check(self._lib.grape_eval_jvp(self._h, _p(xf), _p(xdf), n_obs, 1 if per_member else 0, _p(Of), _p(yd), _p(Xf)))
+        if final:
+            return yd, np.ascontiguousarray(np.swapaxes(Xf, -1, -2))
+        return yd
+
     def observe_device(self, d_x, n_obs, per_member, d_O, d_y, d_X_final, d_fg=0, stream=0):
         """grape_eval_observables_device with raw device pointers (e.g. torch tensor .data_ptr()), in the library's layouts:
         d_x f64 (K, cols) column-major, d_O c128 (n, m, [E,] n_obs), d_y c128 (N+1, n_obs, E), d_X_final c128 (n, m, E), d_fg
@@ -646,6 +684,18 @@ class GrapeEngine:
             raise ValueError("observe_vjp_device: d_G is null")
         self._check(self._lib.grape_eval_vjp_device(self._h, C.c_void_p(d_x), n_obs, 1 if per_member else 0, C.c_void_p(d_O),
                                                     C.c_void_p(d_ybar), C.c_void_p(d_Xbar_final), C.c_void_p(d_G),
+                                                    C.c_void_p(stream)))
+
+    def observe_jvp_device(self, d_x, d_xdot, n_obs, per_member, d_O, d_ydot, d_Xdot_final, stream=0):
+        """grape_eval_jvp_device with raw device pointers, layouts as observe_device; d_xdot f64 (K, cols) column-major like
+        d_x.  d_x=0: reuse -- push d_xdot forward along the trajectory the last device form left in the workspace, without a
+        sweep (GrapeError NOT_READY when anything else has touched the context since, or under a member chunk); an
+        observe_vjp_device(0, ...) may follow at the same point."""
+        n_obs = self._traj_device_args("observe_jvp_device", 1, n_obs, d_O, d_ydot, d_Xdot_final, "d_ydot and d_Xdot_final")
+        if not d_xdot:
+            raise ValueError("observe_jvp_device: d_xdot is null")
+        self._check(self._lib.grape_eval_jvp_device(self._h, C.c_void_p(d_x), C.c_void_p(d_xdot), n_obs, 1 if per_member else 0,
+                                                    C.c_void_p(d_O), C.c_void_p(d_ydot), C.c_void_p(d_Xdot_final),
                                                     C.c_void_p(stream)))
 
     @staticmethod
