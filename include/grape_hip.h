@@ -535,8 +535,8 @@ int grape_eval_observables(grape_ctx *ctx, const double *x, int32_t n_obs, int32
  * ybar[0,.,.] is read and validated but contributes nothing (X_0 = Xi).  G holds no ensemble weight, penalty, running cost
  * or risk: it is the gradient of the caller's loss alone (the caller puts w_k into l).  The gradient is FIRST ORDER in dt,
  * like the reference's grad_func! and like grape_set_running_cost (the derivative of exp(-i dt H) is taken as -i dt B P);
- * against central differences of a smooth loss on a smooth pulse the deviation falls by ~4 per 4x in N.  An exact VJP is not
- * offered.
+ * against central differences of a smooth loss on a smooth pulse the deviation falls by ~4 per 4x in N.  The exact
+ * derivative is a setting of the context: grape_set_trajectory_derivative(ctx, GRAPE_TRAJ_EXACT), below.
  * With grape_set_bounds and / or grape_set_basis in force G is returned in the coordinates of x: the summed physical row
  * goes through bounds_slope_kernel / basis_project_kernel (the slope of this very evaluation), without the penalty and F
  * that an evaluation's own tail carries -- so grape_eval_observables and this call agree on coordinates.
@@ -615,7 +615,7 @@ int grape_eval_vjp_device(grape_ctx *ctx, const double *d_x, int32_t n_obs, int3
  * G = grape_eval_vjp(ybar, Xbar_final) on the same context,
  *   sum Re(conj(ybar) ydot) + sum_k Re tr(Xbar_k' Xdot_final_k) = sum_{c,t} G[c,t] xdot[c,t]
  * holds to rounding, in the coordinates of x.  Against central differences of grape_eval_observables on a smooth pulse the
- * deviation falls by ~4 per 4x in N.  An exact tangent is not offered.
+ * deviation falls by ~4 per 4x in N.  The exact tangent: grape_set_trajectory_derivative(ctx, GRAPE_TRAJ_EXACT), below.
  * With grape_set_bounds and / or grape_set_basis in force xdot_phys = s * (xdot phi^T): the expansion without x0 (phi is the
  * identity without a basis) times the slope array s of this very evaluation (1 without bounds) -- the transpose of what the
  * pull-back's tail does (basis_expand_kernel / bounds_tangent_kernel in tangent mode).  No ensemble weight, penalty, running
@@ -654,6 +654,42 @@ int grape_eval_jvp(grape_ctx *ctx, const double *x, const double *xdot, int32_t 
  * linearisation point). */
 int grape_eval_jvp_device(grape_ctx *ctx, const double *d_x, const double *d_xdot, int32_t n_obs, int32_t per_member,
                           const double *d_O, double *d_ydot, double *d_Xdot_final, void *stream);
+
+/* ABI v8 (additive).  The derivative rule of the pull-back and the push-forward along the trajectory: all six entry points --
+ * grape_eval_vjp, grape_eval_vjp_device, grape_eval_jvp, grape_eval_jvp_device and the d_x = NULL reuse forms of both device
+ * calls.  GRAPE_TRAJ_FIRST_ORDER (the default) takes dP_t/dx[c,t] as (-i dt B_c) P_t, as documented above.  GRAPE_TRAJ_EXACT
+ * takes the Frechet derivative DF_t[E] at G_t = -i dt H_t of the map the sweep itself evaluated (the degree-8 Taylor
+ * polynomial at G_t / 2^s squared s times, with the sweep's own s per slice, a forced expm_squarings included), operation by
+ * operation -- exact to the rounding of P_t, the code path of gradient = exact (exact_grad.hip):
+ *   VJP:  G[c,t]       = sum_k Re tr( Lam_{k,t+1}' DF_t[B'_kc] X_{k,t} ) = sum_k Re tr( DF_t[W_{k,t}] B'_kc ),
+ *                        W_{k,t} = X_{k,t} Lam_{k,t+1}' ,  B' = -i dt B     (ONE derivative per slice serves all K controls)
+ *   JVP:  Xdot_{k,t+1} = P_{k,t} Xdot_{k,t} + DF_t[V_t] X_{k,t} ,   V_t = sum_c xdot_phys[c,t] B'_kc
+ * X_{k,t} is the state BEFORE slice t (the first-order rule uses X_{k,t+1}).  Everything else is unchanged: the layouts and
+ * the cotangent convention, the Lam recurrence and ybar[0] contributing nothing, no weight / penalty / running cost / risk in
+ * the result, the slope / projection tail and the tangent map under bounds / basis, member-chunked contexts, max_batch > 1,
+ * the argument checks and the refusals.  The pair stays an exact transpose pair, now of the true derivative:
+ * torch.autograd.gradcheck on the read-out passes, and against central differences the deviation is that of the differences.
+ * The running cost's own gradient (grape_set_running_cost) STAYS first order, and so does the main objective's unless the
+ * context was created with gradient = exact.
+ * Kernels (grape_get_kernel_names tells which ran): the exact instance of trajectory_vjp_kernel
+ * (trajectory_vjp_exact_kernel) stores W_t per slice, traj_frechet_rows_kernel -- one lane (n = 3) or lane pair (n = 2, 4)
+ * per (member, slice) -- rebuilds G_t from the physical pulse the evaluation left on the device and writes the row entries
+ * that vjp_sum_kernel sums as ever; traj_frechet_dir_kernel stores E_t = DF_t[V_t] per slice and the exact instance of
+ * trajectory_jvp_kernel (trajectory_jvp_exact_kernel) consumes it.  In front of them copy_kernel keeps the physical pulse
+ * for the reuse forms, which stay bit for bit equal to the calls with d_x given.  The staged VJP instance is not used in
+ * this mode (GRAPE_TRAJ_STAGED is ignored for the pull-back).  Scratch: one n x n c128 block per slice and member of a
+ * workspace block -- the size of one control array's propagators -- shared by W_t and E_t, allocated by the first exact
+ * call, counted in grape_info.workspace_bytes, growing only behind a pending device call.  No atomics: results are
+ * bitwise reproducible call to call, member-chunked = unchunked, host form = device form, and the JVP is exactly linear in
+ * xdot.
+ * A setting like the other grape_set_*: valid any time after grape_create, persists across grape_set_operators, ordered
+ * behind an in-flight grape_eval_device, clears the "trajectory valid" flag.  GRAPE_ERR_INVALID_ARG: mode outside {0, 1}.
+ * mode = GRAPE_TRAJ_EXACT on a context that grape_eval_vjp refuses is refused with GRAPE_ERR_UNSUPPORTED and that call's
+ * reason ("dimension", "StateTransfer", "exact", "multi-device", "communicator"); while the mode is exact,
+ * grape_comm_attach / grape_ipc_attach are refused.  After a failure the previous setting stays in force.  With mode = 0,
+ * and on a context that never calls this, every entry point launches the kernels it always did and returns the same bits. */
+typedef enum grape_traj_derivative { GRAPE_TRAJ_FIRST_ORDER = 0, GRAPE_TRAJ_EXACT = 1 } grape_traj_derivative;
+int grape_set_trajectory_derivative(grape_ctx *ctx, int32_t mode);
 
 /* Device-resident L-BFGS: stands in for
  *     Optim.optimize(Optim.only_fg!(topt), x0, Optim.LBFGS(), optim_options)       src/solve.jl:138, :244

@@ -291,6 +291,14 @@ function observables_jvp_device(ctx::GrapeContext, d_x::Ptr{Cvoid}, d_xdot::Ptr{
     ctx
 end
 
+# grape_set_trajectory_derivative: :first_order (default) or :exact -- observables_vjp / observables_jvp, their device forms and
+# the reuse forms then use the Frechet derivative of the sweep's own expm evaluation per slice instead of (-i dt B) P
+function set_trajectory_derivative!(ctx::GrapeContext, mode::Symbol)
+    mode in (:first_order, :exact) || throw(ArgumentError("mode must be :first_order or :exact"))
+    check(ctx, ccall((:grape_set_trajectory_derivative, libgrape), Cint, (Ptr{Cvoid}, Int32), ctx.handle, Int32(mode == :exact ? 1 : 0)))
+    ctx
+end
+
 "The kernels the last evaluation launched, in launch order (grape_get_kernel_names, ABI v4)."
 function kernel_names(ctx::GrapeContext)
     need = ccall((:grape_get_kernel_names, libgrape), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Cint), ctx.handle, C_NULL, 0)

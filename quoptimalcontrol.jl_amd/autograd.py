@@ -16,6 +16,12 @@ Forward mode: both functions carry a jvp, so torch.autograd.forward_ad dual numb
 (y, X_final) along the tangent of x is GrapeEngine.observe_jvp's (grape_eval_jvp), the exact transpose of the backward.
 (torch.func.jvp needs the setup_context form of a Function and is not served.)
 
+Which derivative: the engine's setting carries through.  By default both directions are first order in dt
+(GrapeEngine.trajectory_derivative == "first_order"), so torch.autograd.gradcheck on these functions FAILS -- the backward is
+the transpose of a first-order linearisation, not of the forward's true derivative.  After
+eng.set_trajectory_derivative("exact") the backward and the jvp differentiate the propagators the forward used, exactly:
+gradcheck passes and a quasi-Newton solve on a custom loss converges to its own gradient tolerance.
+
 trajectory_device is the same for a workflow that lives on the GPU: x, y, X_final, the loss and x.grad are CUDA tensors on the
 engine's device, the read-out and the pull-back run on torch's current stream (GrapeEngine.observe_device /
 observe_vjp_device) and nothing crosses to the host.

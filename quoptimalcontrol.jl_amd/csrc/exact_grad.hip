@@ -20,56 +20,10 @@
 
 #include "cmat.hpp"
 #include "cmatp.hpp"
+#include "frechet.hpp"
 #include "grape_kernels.hpp"
 
 namespace grape {
-
-template <int N>
-GRAPE_DEV void lin2(CMat<N> &o, double a, const CMat<N> &x, double b, const CMat<N> &y)
-{
-#pragma unroll
-    for (int e = 0; e < N * N; ++e) {
-        o.re[e] = fma(a, x.re[e], b * y.re[e]);
-        o.im[e] = fma(a, x.im[e], b * y.im[e]);
-    }
-}
-
-template <int N>
-GRAPE_DEV void acc(CMat<N> &o, double a, const CMat<N> &x)
-{
-#pragma unroll
-    for (int e = 0; e < N * N; ++e) {
-        o.re[e] = fma(a, x.re[e], o.re[e]);
-        o.im[e] = fma(a, x.im[e], o.im[e]);
-    }
-}
-
-// o += a * b
-template <int N>
-GRAPE_DEV void mul_acc(CMat<N> &o, const CMat<N> &a, const CMat<N> &b)
-{
-    CMat<N> t;
-    mul(t, a, b);
-    acc(o, 1.0, t);
-}
-
-// tr(A * B) = sum_ij A[i,j] B[j,i]
-template <int N>
-GRAPE_DEV void trace_ab(double &zr, double &zi, const CMat<N> &a, const CMat<N> &b)
-{
-    double sr = 0.0, si = 0.0;
-#pragma unroll
-    for (int j = 0; j < N; ++j)
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            const double ar = a.re[i + j * N], ai = a.im[i + j * N];
-            const double br = b.re[j + i * N], bi = b.im[j + i * N];
-            sr = fma(ar, br, sr); sr = fma(-ai, bi, sr);
-            si = fma(ar, bi, si); si = fma(ai, br, si);
-        }
-    zr = sr;
-    zi = si;
-}
 
 template <int N, int SAND>
 __global__ __launch_bounds__(64) void exact_grad_kernel(const double2 *__restrict__ ops_all, const double *__restrict__ x_all,
@@ -123,86 +77,19 @@ __global__ __launch_bounds__(64) void exact_grad_kernel(const double2 *__restric
         mul(tmp, P, X);                                  // X_{t+1} = P X
         trace_ah_b(phr, phi, Ln, tmp);
     }
-    // generator of this slice and the shared part of the Taylor-8 evaluation
-    CMat<N> G;
-    if (p.variant == 0) {
-#pragma unroll
-        for (int e = 0; e < NN; ++e) { G.re[e] = 0.0; G.im[e] = 0.0; }
-    } else {
-#pragma unroll
-        for (int e = 0; e < NN; ++e) { const double2 a = ops[e]; G.re[e] = a.x; G.im[e] = a.y; }
-    }
-    for (int c = 0; c < K; ++c) {
-        const double xv = x_all[c + (size_t)tt * K];
-#pragma unroll
-        for (int e = 0; e < NN; ++e) {
-            const double2 b = opB[c * NN + e];
-            G.re[e] = fma(b.x, xv, G.re[e]);
-            G.im[e] = fma(b.y, xv, G.im[e]);
-        }
-    }
-    if (p.variant == 0) {
-#pragma unroll
-        for (int e = 0; e < NN; ++e) { const double2 a = ops[e]; G.re[e] += a.x; G.im[e] += a.y; }
-    }
-    const int s = p.s_forced >= 0 ? p.s_forced : squarings_for(norm1_bound(G));
-    const double sc = s > 0 ? ldexp(1.0, -s) : 1.0;
-#pragma unroll
-    for (int e = 0; e < NN; ++e) { G.re[e] *= sc; G.im[e] *= sc; }
-    CMat<N> A2, T1, A4, U, T2;
-    mul(A2, G, G);
-    lin2(T1, kX1, G, kX2, A2);
-    mul(A4, A2, T1);
-    lin2(U, kX3, A2, 1.0, A4);
-    lin2(T2, kX5, G, kX6, A2);
-    acc(T2, kX7, A4);
-#pragma unroll
-    for (int i = 0; i < N; ++i) T2.re[i + i * N] += kX4;
-    // value at the scaled point (needed by the squaring chain rule): Ps = U T2 + G + y2 A2 + I
-    CMat<N> Ps;
-    mul(Ps, U, T2);
-    acc(Ps, 1.0, G);
-    acc(Ps, kY2, A2);
-#pragma unroll
-    for (int i = 0; i < N; ++i) Ps.re[i + i * N] += 1.0;
+    // generator of this slice and the shared part of the Taylor-8 evaluation (frechet.hpp)
+    FrechetLane<N> fr;
+    build_generator(fr.G, ops, opB, x_all + (size_t)tt * K, K, p.variant);
+    fr.prepare(p.s_forced);
 
     double *__restrict__ out = p.member_out + (size_t)k * ((size_t)K * Nsl + 1);
     const double D2 = 1.0 / ((double)N * (double)N);
-    // The map G -> P evaluated above is a POLYNOMIAL F in G (Taylor-8 at G / 2^s, squared s times), and for a polynomial
-    //     tr( DF_G[B] W ) = tr( DF_G[W] B )        (every term  tr(G^j B G^(k-1-j) W) = tr(G^(k-1-j) W G^j B), summed over j)
-    // -- so ONE derivative in the direction W1 (and one in W2 where the sandwich needs it) serves all K controls, each of
-    // which is left with a trace.  (Round 2 differentiated in the K directions B'_c: 6 + 2 s products per control.)
-    auto frechet = [&](CMat<N> &dP, const CMat<N> &W) {
-        CMat<N> E;                                       // direction, scaled like G
-#pragma unroll
-        for (int e = 0; e < NN; ++e) { E.re[e] = sc * W.re[e]; E.im[e] = sc * W.im[e]; }
-        CMat<N> dA2, dT1, dA4, dU, dT2;
-        mul(dA2, E, G);
-        mul_acc(dA2, G, E);
-        lin2(dT1, kX1, E, kX2, dA2);
-        mul(dA4, dA2, T1);
-        mul_acc(dA4, A2, dT1);
-        lin2(dU, kX3, dA2, 1.0, dA4);
-        lin2(dT2, kX5, E, kX6, dA2);
-        acc(dT2, kX7, dA4);
-        mul(dP, dU, T2);
-        mul_acc(dP, U, dT2);
-        acc(dP, 1.0, E);
-        acc(dP, kY2, dA2);
-        CMat<N> Pq = Ps;                                 // undo the scaling: P <- P^2, dP <- dP P + P dP
-        for (int i = 0; i < s; ++i) {
-            mul(tmp, dP, Pq);
-            mul_acc(tmp, Pq, dP);
-            dP = tmp;
-            mul(tmp, Pq, Pq);
-            Pq = tmp;
-        }
-    };
+    // ONE derivative in the direction W1 (and one in W2 where the sandwich needs it) serves all K controls (frechet.hpp)
     CMat<N> D1, D2m;
-    frechet(D1, W1);
+    fr.apply(D1, W1);
     const bool second = SAND && !p.herm_states;          // Hermitian X, L: W2 == W1
     if (second)
-        frechet(D2m, W2);
+        fr.apply(D2m, W2);
     for (int c = 0; c < K; ++c) {
         CMat<N> Bc;
 #pragma unroll
@@ -235,65 +122,7 @@ __global__ __launch_bounds__(64) void exact_grad_kernel(const double2 *__restric
     }
 }
 
-// ---- n = 2, 4: the same evaluation on LANE PAIRS (cmatp.hpp: lane parity p owns n/2 columns of every matrix, the partner's
-// half comes through DPP).  With whole 4 x 4 matrices per lane the kernel above holds a dozen 64-register matrices: 512
-// registers and 1.1 - 2.3 KB of scratch per lane (420 us at C3).  A pair-split matrix is 32 registers; the intermediates are
-// sequenced so that at most eleven are alive.
-template <int N>
-GRAPE_DEV void plin2(PMat<N> &o, double a, const PMat<N> &x, double b, const PMat<N> &y)
-{
-#pragma unroll
-    for (int e = 0; e < N * PMat<N>::NC; ++e) {
-        o.re[e] = fma(a, x.re[e], b * y.re[e]);
-        o.im[e] = fma(a, x.im[e], b * y.im[e]);
-    }
-}
-
-template <int N>
-GRAPE_DEV void pacc(PMat<N> &o, double a, const PMat<N> &x)
-{
-#pragma unroll
-    for (int e = 0; e < N * PMat<N>::NC; ++e) {
-        o.re[e] = fma(a, x.re[e], o.re[e]);
-        o.im[e] = fma(a, x.im[e], o.im[e]);
-    }
-}
-
-// o += a * b   (a's partner half fetched here)
-template <int N>
-GRAPE_DEV void pmul_acc(PMat<N> &o, const PMat<N> &a, const PMat<N> &b)
-{
-    PMat<N> par, t;
-    fetch_partner(par, a);
-    pmul(t, a, par, b);
-    pacc(o, 1.0, t);
-}
-
-template <int N>
-GRAPE_DEV void pmul_f(PMat<N> &o, const PMat<N> &a, const PMat<N> &b)
-{
-    PMat<N> par;
-    fetch_partner(par, a);
-    pmul(o, a, par, b);
-}
-
-// tr(A B) = sum_ij A[i,j] B[j,i]: the pair layout of B^T is not at hand, so through  tr(A B) = tr((A')' B): conj-transpose
-// products are what cmatp.hpp has -- here B comes from memory, loaded directly TRANSPOSED (see pload_t below)
-template <int N>
-GRAPE_DEV void ptrace_elem(double &zr, double &zi, const PMat<N> &a, const PMat<N> &bt)
-{
-    double sr = 0.0, si = 0.0;
-#pragma unroll
-    for (int e = 0; e < N * PMat<N>::NC; ++e) {
-        sr = fma(a.re[e], bt.re[e], sr);
-        sr = fma(-a.im[e], bt.im[e], sr);
-        si = fma(a.re[e], bt.im[e], si);
-        si = fma(a.im[e], bt.re[e], si);
-    }
-    zr = sr + pair_swap(sr);
-    zi = si + pair_swap(si);
-}
-
+// ---- n = 2, 4: the same evaluation on LANE PAIRS (frechet.hpp: FrechetPair)
 // W1IN (UnitaryGate, Hermitian generators -- round 4): the backward sweep of the unitary flow has left W_t = X_t L_{t+1}' in
 // `states` and Phi = tr(L' X) per member in `zphi` (SweepParams::dump_w1): no P_t / X_t / L_{t+1} loads, two products less,
 // and a sweep of 0.09 instead of 0.16 ms in front of this kernel.
@@ -310,30 +139,14 @@ __global__ __launch_bounds__(64) void exact_pair_kernel(const double2 *__restric
     const double2 *__restrict__ ops = ops_all + (size_t)k * (K + 3) * NN;
     const double2 *__restrict__ opB = ops + NN;
     const double2 *__restrict__ opXt = ops + (size_t)(2 + K) * NN;
-    // local element (r, jl) of the pair layout <-> global (i, j), column-major i + j n
     int gidx[NE], gidx_t[NE];
-#pragma unroll
-    for (int jl = 0; jl < NC; ++jl)
-#pragma unroll
-        for (int r = 0; r < N; ++r) {
-            const int i = (((r / NC) ^ par) * NC) + (r % NC), j = par * NC + jl;
-            gidx[r + jl * N] = i + j * N;
-            gidx_t[r + jl * N] = j + i * N;              // the transposed matrix' element
-        }
+    pair_indices<N>(par, gidx, gidx_t);
     auto ws_load = [&](PMat<N> &m, const double2 *__restrict__ ws, int slice) {
         const int L = slice / p.S, j = slice - L * p.S;
         const double2 *__restrict__ base = ws + ((size_t)k * p.S + j) * NN * p.CH + L;
 #pragma unroll
         for (int e = 0; e < NE; ++e) {
             const double2 v = base[(size_t)gidx[e] * p.CH];
-            m.re[e] = v.x;
-            m.im[e] = v.y;
-        }
-    };
-    auto op_load = [&](PMat<N> &m, const double2 *__restrict__ src, const int (&idx)[NE]) {
-#pragma unroll
-        for (int e = 0; e < NE; ++e) {
-            const double2 v = src[idx[e]];
             m.re[e] = v.x;
             m.im[e] = v.y;
         }
@@ -351,7 +164,7 @@ __global__ __launch_bounds__(64) void exact_pair_kernel(const double2 *__restric
         if (tt + 1 < Nsl)
             ws_load(Ln, p.costates, tt + 1);             // costate after slice t
         else
-            op_load(Ln, opXt, gidx);
+            pair_op_load(Ln, opXt, gidx);
         fetch_partner(Lp, Ln);
         if (SAND) {
             PMat<N> Y, Pp, Xp;
@@ -374,88 +187,20 @@ __global__ __launch_bounds__(64) void exact_pair_kernel(const double2 *__restric
             ptrace_ah_b(phr, phi, Ln, tmp);
         }
     }
-    // generator of this slice (the sweep's order of the sum) and the shared part of the Taylor-8 evaluation
-    PMat<N> G;
-    if (p.variant == 0) {
-#pragma unroll
-        for (int e = 0; e < NE; ++e) { G.re[e] = 0.0; G.im[e] = 0.0; }
-    } else {
-        op_load(G, ops, gidx);
-    }
-    for (int c = 0; c < K; ++c) {
-        const double xv = x_all[c + (size_t)tt * K];
-#pragma unroll
-        for (int e = 0; e < NE; ++e) {
-            const double2 b = opB[c * NN + gidx[e]];
-            G.re[e] = fma(b.x, xv, G.re[e]);
-            G.im[e] = fma(b.y, xv, G.im[e]);
-        }
-    }
-    if (p.variant == 0) {
-#pragma unroll
-        for (int e = 0; e < NE; ++e) { const double2 a = ops[gidx[e]]; G.re[e] += a.x; G.im[e] += a.y; }
-    }
-    const int s = p.s_forced >= 0 ? p.s_forced : squarings_for(pnorm1_bound(G));
-    const double sc = s > 0 ? ldexp(1.0, -s) : 1.0;
-#pragma unroll
-    for (int e = 0; e < NE; ++e) { G.re[e] *= sc; G.im[e] *= sc; }
-    PMat<N> A2, A4, T1;
-    pmul_f(A2, G, G);
-    plin2(T1, kX1, G, kX2, A2);
-    pmul_f(A4, A2, T1);
-    // U = x3 A2 + A4 and T2 = x5 G + x6 A2 + x7 A4 + x4 I are rebuilt where they are used (two registers sets less alive)
-    auto make_U = [&](PMat<N> &U) { plin2(U, kX3, A2, 1.0, A4); };
-    auto make_T2 = [&](PMat<N> &T2) {
-        plin2(T2, kX5, G, kX6, A2);
-        pacc(T2, kX7, A4);
-#pragma unroll
-        for (int jl = 0; jl < NC; ++jl) T2.re[jl + jl * N] += kX4;      // own diagonal: local row (0, jl) of column jl
-    };
-    auto frechet = [&](PMat<N> &dP, const PMat<N> &W) {
-        PMat<N> E, dA2, dT, dA4, Tm;
-#pragma unroll
-        for (int e = 0; e < NE; ++e) { E.re[e] = sc * W.re[e]; E.im[e] = sc * W.im[e]; }
-        pmul_f(dA2, E, G);
-        pmul_acc(dA2, G, E);
-        plin2(dT, kX1, E, kX2, dA2);                     // dT1
-        pmul_f(dA4, dA2, T1);
-        pmul_acc(dA4, A2, dT);
-        plin2(dT, kX3, dA2, 1.0, dA4);                   // dU
-        make_T2(Tm);
-        pmul_f(dP, dT, Tm);                              // dU T2
-        plin2(dT, kX5, E, kX6, dA2);                     // dT2
-        pacc(dT, kX7, dA4);
-        make_U(Tm);
-        pmul_acc(dP, Tm, dT);                            // + U dT2
-        pacc(dP, 1.0, E);
-        pacc(dP, kY2, dA2);
-        if (s > 0) {                                     // undo the scaling: P <- P^2, dP <- dP P + P dP
-            PMat<N> Pq, T2;
-            make_T2(T2);
-            pmul_f(Pq, Tm, T2);                          // value at the scaled point: U T2 + G + y2 A2 + I
-            pacc(Pq, 1.0, G);
-            pacc(Pq, kY2, A2);
-#pragma unroll
-            for (int jl = 0; jl < NC; ++jl) Pq.re[jl + jl * N] += 1.0;
-            for (int i = 0; i < s; ++i) {
-                pmul_f(dT, dP, Pq);
-                pmul_acc(dT, Pq, dP);
-                dP = dT;
-                pmul_f(dT, Pq, Pq);
-                Pq = dT;
-            }
-        }
-    };
+    // generator of this slice (the sweep's order of the sum) and the shared part of the Taylor-8 evaluation (frechet.hpp)
+    FrechetPair<N> fr;
+    build_generator_pair(fr.G, ops, opB, x_all + (size_t)tt * K, K, p.variant, gidx);
+    fr.prepare(p.s_forced);
     double *__restrict__ out = p.member_out + (size_t)k * ((size_t)K * Nsl + 1);
     const double D2 = 1.0 / ((double)N * (double)N);
     PMat<N> D1, D2m;
-    frechet(D1, W1);
+    fr.apply(D1, W1);
     const bool second = SAND && !p.herm_states;          // Hermitian X, L: W2 == W1
     if (second)
-        frechet(D2m, W2);
+        fr.apply(D2m, W2);
     for (int c = 0; c < K; ++c) {
         PMat<N> BT;                                      // B'_c transposed, in the pair layout: tr(D B) = sum D .* B^T
-        op_load(BT, opB + c * NN, gidx_t);
+        pair_op_load(BT, opB + c * NN, gidx_t);
         double ar, ai, dr, di;
         ptrace_elem(ar, ai, D1, BT);
         dr = ar;

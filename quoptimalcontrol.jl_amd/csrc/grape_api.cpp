@@ -248,6 +248,16 @@ struct grape_ctx {
     // that ran an evaluation on a context that is not member-chunked; cleared by everything else that evaluates or changes a
     // setting, and by every failed call of the device forms.
     bool traj_valid = false;
+    // grape_set_trajectory_derivative: GRAPE_TRAJ_EXACT makes the pull-back and the push-forward (all six entry points) use
+    // the Frechet derivative of the sweep's own expm evaluation per slice (traj_frechet.hip) instead of the first-order rule.
+    // d_traj_w: W_t = X_t Lam_{t+1}' (pull-back) / E_t = DF_t[V_t] (push-forward), one n x n block per slice and member of a
+    // workspace block; d_traj_x: the PHYSICAL pulse of the evaluation whose propagators the workspace holds -- what the
+    // Frechet kernels rebuild G_t from, kept for the reuse forms (d_x = NULL) as long as traj_valid is set.  Both are
+    // allocated by the first exact call and only ever grow.
+    int traj_mode = 0;                         // grape_traj_derivative
+    double2 *d_traj_w = nullptr;
+    double *d_traj_x = nullptr;
+    size_t traj_w_bytes = 0, traj_x_bytes = 0;
     // grape_set_basis ("parameter mode"): the entry points take theta (K, M) and return G_theta; basis_expand_kernel writes the
     // physical controls into d_x in front of the evaluation, basis_project_kernel folds the complete summed rows in d_fg behind
     // it (basis.hip).  Kept by the context the caller holds (a group: device buffers on its first device); shards never see it.
@@ -643,6 +653,7 @@ static void free_all(grape_ctx *c)
     (void)hipFree(c->d_rc_R); (void)hipFree(c->d_rc_rho); (void)hipFree(c->d_rc_xs); (void)hipFree(c->d_rc_rows);
     (void)hipFree(c->d_obs_O); (void)hipFree(c->d_obs_y); (void)hipFree(c->d_obs_xf);
     (void)hipFree(c->d_vjp_O); (void)hipFree(c->d_vjp_ybar); (void)hipFree(c->d_vjp_xbar); (void)hipFree(c->d_vjp_part); (void)hipFree(c->d_vjp_g); (void)hipFree(c->d_vjp_out);
+    (void)hipFree(c->d_traj_w); (void)hipFree(c->d_traj_x);
     (void)hipFree(c->d_jvp_O); (void)hipFree(c->d_jvp_xdot); (void)hipFree(c->d_jvp_xphys); (void)hipFree(c->d_jvp_ydot); (void)hipFree(c->d_jvp_xf);
     (void)hipFree(c->d_basis_phi); (void)hipFree(c->d_basis_x0);
     (void)hipFree(c->d_bounds); (void)hipFree(c->d_slope);
@@ -1196,6 +1207,8 @@ extern "C" int grape_comm_attach(grape_ctx *c, const grape_comm_id *id, int32_t 
         return fail(c, GRAPE_ERR_INVALID_ARG, "grape_comm_attach: a communicator is already attached");
     if (c->rc_terms > 0)
         return fail(c, GRAPE_ERR_UNSUPPORTED, "grape_comm_attach: a running cost is set (grape_set_running_cost serves contexts without an exchange only)");
+    if (c->traj_mode != GRAPE_TRAJ_FIRST_ORDER)
+        return fail(c, GRAPE_ERR_UNSUPPORTED, "grape_comm_attach: the trajectory derivative is exact (grape_set_trajectory_derivative serves contexts without an exchange only)");
     if (c->risk_beta != 0.0)
         return fail(c, GRAPE_ERR_UNSUPPORTED, "grape_comm_attach: a risk is set (grape_set_risk serves contexts without a communicator or mailbox exchange only)");
     RcclApi *api = rccl();
@@ -1268,6 +1281,8 @@ extern "C" int grape_ipc_attach(grape_ctx *c, const grape_ipc_handle *handles, i
         return fail(c, GRAPE_ERR_INVALID_ARG, "grape_ipc_attach: a communicator is already attached");
     if (c->rc_terms > 0)
         return fail(c, GRAPE_ERR_UNSUPPORTED, "grape_ipc_attach: a running cost is set (grape_set_running_cost serves contexts without an exchange only)");
+    if (c->traj_mode != GRAPE_TRAJ_FIRST_ORDER)
+        return fail(c, GRAPE_ERR_UNSUPPORTED, "grape_ipc_attach: the trajectory derivative is exact (grape_set_trajectory_derivative serves contexts without an exchange only)");
     if (c->risk_beta != 0.0)
         return fail(c, GRAPE_ERR_UNSUPPORTED, "grape_ipc_attach: a risk is set (grape_set_risk serves contexts without a communicator or mailbox exchange only)");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -2547,6 +2562,26 @@ static int fold_events(grape_ctx *c, uint64_t count)
     return GRAPE_OK;
 }
 
+static bool traj_exact(const grape_ctx *c) { return c->traj_mode == GRAPE_TRAJ_EXACT; }
+
+// GRAPE_TRAJ_EXACT: the scratch of the exact instances behind the CURRENT workspace plan -- one n x n block per slice and
+// member of a workspace block (the size of one control array's propagators), shared by W_t and E_t, and the physical pulse
+static int traj_exact_ensure(grape_ctx *c, const char *who)
+{
+    const size_t w = sizeof(double2) * (size_t)c->Ec * c->S * c->CH * c->cfg.n * c->cfg.n;
+    if (int rc = grow(c, &c->d_traj_w, &c->traj_w_bytes, w, who, "the exact trajectory derivative's per-slice blocks")) return rc;
+    return grow(c, &c->d_traj_x, &c->traj_x_bytes, sizeof(double) * KN(c), who, "the physical pulse of the stored trajectory");
+}
+
+// what the exact instances of a vjp_only / jvp_only launch read next to the first-order fields
+static void traj_exact_params(const grape_ctx *c, SweepParams &v)
+{
+    if (!traj_exact(c)) return;
+    v.traj_exact = 1;
+    v.traj_w = c->d_traj_w;
+    v.traj_x = c->d_traj_x;
+}
+
 // grape_eval_vjp: the launch of trajectory_vjp_kernel + vjp_sum_kernel for the members from `lo` on that `q` sweeps (or swept:
 // grape_eval_vjp_device's reuse)
 static SweepParams vjp_params(const grape_ctx *c, const SweepParams &q, int lo)
@@ -2567,7 +2602,8 @@ static SweepParams vjp_params(const grape_ctx *c, const SweepParams &q, int lo)
     v.vjp_rows = c->d_rc_rows;
     v.vjp_part = c->d_vjp_part;
     v.vjp_G = c->vjp_G_call;
-    v.vjp_staged = c->vjp_has_y ? c->vjp_staged : 0;
+    v.vjp_staged = c->vjp_has_y && !traj_exact(c) ? c->vjp_staged : 0;      // (exact mode: the direct instance only)
+    traj_exact_params(c, v);
     return v;
 }
 
@@ -2587,6 +2623,7 @@ static SweepParams jvp_params(const grape_ctx *c, const SweepParams &q, int lo)
     v.jvp_xdot = pulse_map(c) ? c->d_jvp_xphys : c->jvp_xdot_call;
     v.jvp_ydot = c->jvp_has_y ? c->jvp_ydot_call : nullptr;
     v.jvp_xf = c->jvp_has_x ? c->jvp_xf_call : nullptr;
+    traj_exact_params(c, v);
     return v;
 }
 
@@ -2644,7 +2681,15 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
         const int rc = rc_ensure(c);
         if (rc) return rc;
     }
+    // GRAPE_TRAJ_EXACT: every evaluation that may leave a trajectory for the pull-back / push-forward (the read-out's device
+    // form too: a reuse call may follow it) keeps the physical pulse its propagators were formed from
+    const bool keep_x = traj_exact(c) && c->family == 0 && (c->obs_on || c->vjp_on || c->jvp_on);
+    if (keep_x) {
+        const int rc = traj_exact_ensure(c, "grape_set_trajectory_derivative");
+        if (rc) return rc;
+    }
     KernelLogScope log_scope(&c->kernel_log);
+    if (keep_x) HIP_TRY(c, grape::launch_copy(d_x, c->d_traj_x, (int)KN(c), stream));
     if (c->jvp_on && pulse_map(c)) {                         // (the expansion in front has written this evaluation's slope array)
         const int rc = jvp_tangent_map(c, stream);
         if (rc) return rc;
@@ -3477,6 +3522,24 @@ static const char *why_linearisation_not_served(const grape_ctx *c)
     return nullptr;
 }
 
+// ---- grape_set_trajectory_derivative: first-order or exact derivative of the pull-back / push-forward -------------------------
+extern "C" int grape_set_trajectory_derivative(grape_ctx *c, int32_t mode)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_set_trajectory_derivative: null context");
+    c->traj_valid = false;                                   // (grape_eval_vjp_device's reuse)
+    if (mode != GRAPE_TRAJ_FIRST_ORDER && mode != GRAPE_TRAJ_EXACT)
+        return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_trajectory_derivative: mode = " + std::to_string(mode) +
+                                              " (must be GRAPE_TRAJ_FIRST_ORDER = 0 or GRAPE_TRAJ_EXACT = 1)");
+    if (mode == GRAPE_TRAJ_EXACT)
+        if (const char *why = why_linearisation_not_served(c))
+            return fail(c, GRAPE_ERR_UNSUPPORTED, std::string("grape_set_trajectory_derivative: ") + why);
+    if (c->is_group) return GRAPE_OK;                        // (switching off what can never be on)
+    if (int rc = drain(c, c)) return rc;                     // (behind an in-flight grape_eval_device)
+    c->traj_mode = mode;
+    return GRAPE_OK;
+}
+
 // grape_eval_jvp / grape_eval_jvp_device: vjp_check's order with the direction in place of G and the tangents in place of
 // the cotangents
 static int jvp_check(grape_ctx *c, const std::string &who, const void *x, bool x_needed, const void *xdot, int32_t n_obs,
@@ -3757,6 +3820,10 @@ extern "C" int grape_eval_vjp_device(grape_ctx *c, const double *d_x, int32_t n_
         // the propagators (and the slope array) of the last device form are in place: the pull-back alone
         rc = rc_ensure(c);                                   // (the rows, and the states of the general flow)
         if (rc) return rc;
+        if (traj_exact(c)) {                                 // (the pulse is in place; the blocks, after a read-out alone)
+            rc = traj_exact_ensure(c, who);
+            if (rc) return rc;
+        }
         KernelLogScope log_scope(&c->kernel_log);
         SweepParams q = sweep_params(c, nullptr, 1);
         q.props = c->d_props;
@@ -3880,6 +3947,10 @@ extern "C" int grape_eval_jvp_device(grape_ctx *c, const double *d_x, const doub
         if (rc) return rc;
     } else {
         // the propagators (and the slope array) of the last device form are in place: the tangent map and the push-forward alone
+        if (traj_exact(c)) {                                 // (the pulse is in place; the blocks, after a read-out alone)
+            rc = traj_exact_ensure(c, who);
+            if (rc) return rc;
+        }
         KernelLogScope log_scope(&c->kernel_log);
         if (pulse_map(c)) {
             rc = jvp_tangent_map(c, st);

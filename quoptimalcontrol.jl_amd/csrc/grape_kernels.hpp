@@ -218,6 +218,14 @@ struct SweepParams {
     const double *jvp_xdot;  // (K, N) column-major: the direction in the coordinates of the PHYSICAL pulse
     double2 *jvp_ydot;       // (N + 1, jvp_n, jvp_Etot) column-major, nullable
     double2 *jvp_xf;         // (n, m, jvp_Etot) Xdot_N, nullable
+    // grape_set_trajectory_derivative, GRAPE_TRAJ_EXACT (traj_frechet.hip): a vjp_only / jvp_only launch with traj_exact set
+    // runs the exact instances -- trajectory_vjp_exact_kernel (W_t = X_t Lam_{t+1}' into traj_w) + traj_frechet_rows_kernel
+    // (the rows) + vjp_sum_kernel;  traj_frechet_dir_kernel (E_t = DF_t[V_t] into traj_w) + trajectory_jvp_exact_kernel.
+    // 0: the first-order kernels, which read neither field.  (The sweep kernels read none of the three: only their kernarg
+    // size moved.)
+    int32_t traj_exact;
+    double2 *traj_w;         // one n x n block per (member of the launch, slice), chunk-major like props
+    const double *traj_x;    // (K, N) the PHYSICAL pulse the stored propagators were formed from
 };
 // static LDS of observe_kernel (vjp = false) / trajectory_vjp_kernel (vjp = true) at operator dimension n with m state
 // columns: the scans' wave totals.  What the host layer subtracts from the device's LDS per workgroup to get the staged
@@ -232,6 +240,8 @@ hipError_t run_observe(int n, int sandwich, const SweepParams &p, hipStream_t st
 hipError_t run_trajectory_vjp(int n, const SweepParams &p, hipStream_t stream);
 // jvp.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::jvp_only) only
 hipError_t run_trajectory_jvp(int n, const SweepParams &p, hipStream_t stream);
+// traj_frechet.hip; reached through run_trajectory_vjp (dir = false) / run_trajectory_jvp (dir = true) only
+hipError_t run_traj_frechet(int n, bool dir, const SweepParams &p, hipStream_t stream);
 constexpr int kVjpGroup = 32;                 // members per group of vjp_sum_kernel's tree: vjp_part has ceil(E / 32) rows
 // running_cost.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::rc_only) only
 hipError_t run_running_cost(int n, const SweepParams &p, hipStream_t stream);

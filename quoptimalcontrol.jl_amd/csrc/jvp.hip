@@ -126,9 +126,26 @@ GRAPE_DEV void jvp_step(CRect<N, C> &X, CRect<N, C> &D, const double2 *__restric
     rmul_acc(D, P, X);
 }
 
+// The same slice in the exact derivative mode (GRAPE_TRAJ_EXACT):  D <- P D + E_t X,  X <- P X  with E_t = DF_t[V_t] from
+// traj_frechet_dir_kernel and X the state BEFORE the slice.  P is loaded a second time behind E_t (from L2) instead of
+// kept: one n x n block live next to X and D, as in the first-order step.
+template <int N, int C>
+GRAPE_DEV void jvp_step_exact(CRect<N, C> &X, CRect<N, C> &D, const double2 *__restrict__ Pt, const double2 *__restrict__ Et,
+                              size_t stride)
+{
+    CMat<N> P;
+    rc_load_mat(P, Pt, stride);
+    rmul_inplace(D, P);
+    rc_load_mat(P, Et, stride);
+    rmul_acc(D, P, X);
+    rc_load_mat(P, Pt, stride);
+    rmul_inplace(X, P);
+}
+
 // ops_all / o_all are separate `const __restrict__` arguments so that the wave-uniform operator and probe entries can be
-// fetched with scalar loads (as in vjp.hip)
-template <int N, int M, int MAXT>
+// fetched with scalar loads (as in vjp.hip).  EXACT: the instance of the exact derivative mode, which consumes the E_t that
+// traj_frechet_dir_kernel left chunk-major in SweepParams::traj_w (xdot is not read here).
+template <int N, int M, int MAXT, bool EXACT = false>
 __global__ __launch_bounds__(MAXT) void trajectory_jvp_kernel(const double2 *__restrict__ ops_all,
                                                               const double2 *__restrict__ o_all,
                                                               const double *__restrict__ xdot, const SweepParams p)
@@ -157,6 +174,7 @@ __global__ __launch_bounds__(MAXT) void trajectory_jvp_kernel(const double2 *__r
     const size_t y_step = (size_t)Nsl + 1;
     double2 *__restrict__ yk = p.jvp_ydot ? p.jvp_ydot + (size_t)kg * p.jvp_n * y_step : nullptr;
     const double *__restrict__ xd = xdot + (size_t)lo * K;        // (never read by a lane without a slice)
+    const double2 *__restrict__ Ew = EXACT ? p.traj_w + (size_t)k * S * NN * stride + L : nullptr;
 
     // ---------------------------------------------------------------- 1: chunk product and its tangent, relative to the chunk start
     CMat<N> Q, T;
@@ -170,8 +188,12 @@ __global__ __launch_bounds__(MAXT) void trajectory_jvp_kernel(const double2 *__r
         }
         rzero(Rdot);
 #pragma unroll 1
-        for (int jj = 0; jj < cnt; ++jj)
-            jvp_step(R, Rdot, Pw + (size_t)jj * NN * stride, stride, xd + (size_t)jj * K, opB, K);
+        for (int jj = 0; jj < cnt; ++jj) {
+            if constexpr (EXACT)
+                jvp_step_exact(R, Rdot, Pw + (size_t)jj * NN * stride, Ew + (size_t)jj * NN * stride, stride);
+            else
+                jvp_step(R, Rdot, Pw + (size_t)jj * NN * stride, stride, xd + (size_t)jj * K, opB, K);
+        }
 #pragma unroll
         for (int e = 0; e < NN; ++e) {
             Q.re[e] = R.re[e];
@@ -300,7 +322,10 @@ __global__ __launch_bounds__(MAXT) void trajectory_jvp_kernel(const double2 *__r
 #pragma unroll 1
     for (int jj = 0; jj < cnt; ++jj) {
         const int t = lo + jj;                       // slice index; the state and the tangent behind it are X_{t+1}, D_{t+1}
-        jvp_step(Xlo, Din, Pw + (size_t)jj * NN * stride, stride, xd + (size_t)jj * K, opB, K);
+        if constexpr (EXACT)
+            jvp_step_exact(Xlo, Din, Pw + (size_t)jj * NN * stride, Ew + (size_t)jj * NN * stride, stride);
+        else
+            jvp_step(Xlo, Din, Pw + (size_t)jj * NN * stride, stride, xd + (size_t)jj * K, opB, K);
         emit_y(Din, t + 1);
         if (p.jvp_xf && t + 1 == Nsl) {
             double2 *__restrict__ xf = p.jvp_xf + (size_t)kg * NM;
@@ -320,6 +345,17 @@ static hipError_t jvp_launch_nm(const SweepParams &p, hipStream_t stream)
         p.jvp_E0 + p.E > p.jvp_Etot || p.jvp_n < 0 || p.jvp_n > 16 || (!p.jvp_ydot && !p.jvp_xf) ||
         (p.jvp_ydot && (p.jvp_n < 1 || !p.jvp_O)) || !p.jvp_xdot || !p.props || !p.ops || (long long)p.K * p.N > 0x7fffff00ll)
         return hipErrorInvalidConfiguration;
+    if (p.traj_exact) {
+        // the exact derivative mode: E_t = DF_t[V_t] per (member, slice) into traj_w, then the instance that consumes it
+        if (!p.traj_w || !p.traj_x)
+            return hipErrorInvalidConfiguration;
+        const hipError_t e = run_traj_frechet(N, true, p, stream);
+        if (e != hipSuccess)
+            return e;
+        GRAPE_LAUNCH_AS("trajectory_jvp_exact_kernel", (trajectory_jvp_kernel<N, M, MAXT, true>), dim3(p.E), dim3(threads), 0, stream,
+                        p.ops, p.jvp_O, p.jvp_xdot, p);
+        return hipGetLastError();
+    }
     GRAPE_LAUNCH_AS("trajectory_jvp_kernel", (trajectory_jvp_kernel<N, M, MAXT>), dim3(p.E), dim3(threads), 0, stream, p.ops, p.jvp_O,
                     p.jvp_xdot, p);
     return hipGetLastError();

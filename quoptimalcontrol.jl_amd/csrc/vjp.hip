@@ -37,7 +37,11 @@ namespace grape {
 
 // ops_all / o_all are separate `const __restrict__` arguments so that the wave-uniform operator and probe entries can be
 // fetched with scalar loads (as in running_cost.hip).  UNI: every propagator is unitary.
-template <int N, int M, bool UNI, int MAXT, bool STAGED>
+// EXACT (grape_set_trajectory_derivative, GRAPE_TRAJ_EXACT): walk 6 stores W_t = X_t Lam_{t+1}' (n x n whatever m is; X_t the
+// state BEFORE slice t) chunk-major into SweepParams::traj_w instead of the K traces; traj_frechet_rows_kernel
+// (traj_frechet.hip) turns every W_t into the row entries behind this kernel.  Unitary flow: X_t is at hand after the step
+// back X_t = P_t' X_{t+1}; general flow: the forward walk stores the state BEFORE every slice (slot jj: X_{lo+jj}).
+template <int N, int M, bool UNI, int MAXT, bool STAGED, bool EXACT = false>
 __global__ __launch_bounds__(MAXT) void trajectory_vjp_kernel(const double2 *__restrict__ ops_all,
                                                               const double2 *__restrict__ o_all,
                                                               const double2 *__restrict__ ybar_all,
@@ -136,9 +140,12 @@ __global__ __launch_bounds__(MAXT) void trajectory_vjp_kernel(const double2 *__r
             Xhi = Xs;
             for (int jj = 0; jj < cnt; ++jj) {
                 rc_load_mat(P, Pw + (size_t)jj * NN * stride, stride);
+                if constexpr (EXACT)
+                    rstore_ws(Xw + (size_t)jj * NM * stride, stride, Xhi);  // the state BEFORE slice lo + jj
                 rmul(Xs, P, Xhi);
                 Xhi = Xs;
-                rstore_ws(Xw + (size_t)jj * NM * stride, stride, Xhi);      // the state AFTER slice lo + jj
+                if constexpr (!EXACT)
+                    rstore_ws(Xw + (size_t)jj * NM * stride, stride, Xhi);  // the state AFTER slice lo + jj
             }
         }
     }
@@ -174,25 +181,40 @@ __global__ __launch_bounds__(MAXT) void trajectory_vjp_kernel(const double2 *__r
                 }
             }
             if (emit) {
-                if (!UNI)
-                    rload_ws(X, Xw + (size_t)jj * NM * stride, stride);
-                CMat<N> Mx;
-                rmul_a_bh(Mx, X, Lam);               // X Lam'
-                for (int c = 0; c < K; ++c) {
-                    double re = 0.0;
+                if constexpr (EXACT) {
+                    if (UNI) {
+                        rmul_ah(Tm, P, X);           // X_t = P_t' X_{t+1}
+                        X = Tm;
+                    } else {
+                        rload_ws(X, Xw + (size_t)jj * NM * stride, stride);
+                    }
+                    CMat<N> Mx;
+                    rmul_a_bh(Mx, X, Lam);           // W_t = X_t Lam_{t+1}'
+                    double2 *__restrict__ wp = p.traj_w + ((size_t)k * S + jj) * NN * stride + L;
 #pragma unroll
-                    for (int b2 = 0; b2 < N; ++b2)
+                    for (int e = 0; e < NN; ++e)
+                        wp[e * stride] = make_double2(Mx.re[e], Mx.im[e]);
+                } else {
+                    if (!UNI)
+                        rload_ws(X, Xw + (size_t)jj * NM * stride, stride);
+                    CMat<N> Mx;
+                    rmul_a_bh(Mx, X, Lam);               // X Lam'
+                    for (int c = 0; c < K; ++c) {
+                        double re = 0.0;
 #pragma unroll
-                        for (int a2 = 0; a2 < N; ++a2) {
-                            const double2 b = opB[c * NN + a2 + b2 * N];
-                            re = fma(b.x, Mx.re[b2 + a2 * N], re);
-                            re = fma(-b.y, Mx.im[b2 + a2 * N], re);
-                        }
-                    row[(size_t)t * K + c] = re;
-                }
-                if (UNI) {
-                    rmul_ah(Tm, P, X);
-                    X = Tm;
+                        for (int b2 = 0; b2 < N; ++b2)
+#pragma unroll
+                            for (int a2 = 0; a2 < N; ++a2) {
+                                const double2 b = opB[c * NN + a2 + b2 * N];
+                                re = fma(b.x, Mx.re[b2 + a2 * N], re);
+                                re = fma(-b.y, Mx.im[b2 + a2 * N], re);
+                            }
+                        row[(size_t)t * K + c] = re;
+                    }
+                    if (UNI) {
+                        rmul_ah(Tm, P, X);
+                        X = Tm;
+                    }
                 }
             }
             rmul_ah(Tm, P, Lam);                     // pull the costate back over slice t
@@ -317,7 +339,24 @@ static hipError_t vjp_launch_nm(const SweepParams &p, hipStream_t stream)
         return hipErrorInvalidConfiguration;
     const dim3 grid(p.E), block(threads);
     hipError_t e = hipSuccess;
-    if (p.vjp_staged) {
+    if (p.traj_exact) {
+        // the exact derivative mode: the direct instance alone (vjp_staged is ignored), W_t into traj_w, then one Frechet
+        // derivative per (member, slice) into the rows
+        if (!p.traj_w || !p.traj_x)
+            return hipErrorInvalidConfiguration;
+        if (p.vjp_unitary)
+            GRAPE_LAUNCH_AS("trajectory_vjp_exact_kernel", (trajectory_vjp_kernel<N, M, true, MAXT, false, true>), grid, block, 0, stream,
+                            p.ops, p.vjp_O, p.vjp_ybar, p.vjp_xbar, p);
+        else
+            GRAPE_LAUNCH_AS("trajectory_vjp_exact_kernel", (trajectory_vjp_kernel<N, M, false, MAXT, false, true>), grid, block, 0, stream,
+                            p.ops, p.vjp_O, p.vjp_ybar, p.vjp_xbar, p);
+        e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+        e = run_traj_frechet(N, false, p, stream);
+        if (e != hipSuccess)
+            return e;
+    } else if (p.vjp_staged) {
         // the image is exactly the member's block, and static + dynamic LDS fit a workgroup of this device
         const size_t lds = (size_t)p.vjp_staged;
         if (!p.vjp_ybar || lds != sizeof(double2) * (size_t)p.vjp_n * ((size_t)p.N + 1))

@@ -34,6 +34,8 @@ STATUS = {0: "GRAPE_OK", -1: "GRAPE_ERR_INVALID_ARG", -2: "GRAPE_ERR_UNSUPPORTED
           -3: "GRAPE_ERR_NO_DEVICE", -4: "GRAPE_ERR_HIP", -5: "GRAPE_ERR_NOT_READY",
           -6: "GRAPE_ERR_ALLOC", -7: "GRAPE_ERR_TIMEOUT", -8: "GRAPE_ERR_COMM"}
 
+TRAJ_DERIVATIVE_CODES = {"first_order": 0, "exact": 1}    # grape_traj_derivative
+
 # every symbol include/grape_hip.h declares
 EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_operators", "grape_set_penalties",
            "grape_set_running_cost",
@@ -41,6 +43,7 @@ EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_oper
            "grape_comm_unique_id", "grape_comm_attach", "grape_ipc_export", "grape_ipc_attach",
            "grape_eval", "grape_eval_device", "grape_eval_batch", "grape_eval_batch_device", "grape_eval_fom", "grape_eval_observables",
            "grape_eval_vjp", "grape_eval_observables_device", "grape_eval_vjp_device", "grape_eval_jvp", "grape_eval_jvp_device",
+           "grape_set_trajectory_derivative",
            "grape_lbfgs", "grape_lbfgs_get_trace",
            "grape_get_member_results", "grape_get_trajectory",
            "grape_get_kernel_time", "grape_get_kernel_samples", "grape_get_kernel_names", "grape_get_group_timing", "grape_get_phase_stamps",
@@ -146,6 +149,7 @@ def load_library():
     L.grape_eval_vjp_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.grape_eval_jvp.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
     L.grape_eval_jvp_device.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    L.grape_set_trajectory_derivative.argtypes = [vp, i32]
     L.grape_lbfgs.argtypes = [vp, vp, C.POINTER(GrapeLbfgsOptions), vp, C.POINTER(GrapeLbfgsResult)]
     L.grape_get_member_results.argtypes = [vp, vp, vp]
     L.grape_get_trajectory.argtypes = [vp, i32, vp, vp, vp]
@@ -239,6 +243,7 @@ class GrapeEngine:
                           0 if m == n else m, len(devices) if len(devices) > 1 else 0, ids,
                           {"reference": 0, "exact": 1}[gradient], {"fom": 0, "c1": 1}[objective])
         self.max_batch = max(1, int(max_batch))
+        self._traj_derivative = "first_order"
         h = C.c_void_p()
         rc = self._lib.grape_create(C.byref(cfg), C.byref(h))
         if rc:
@@ -352,6 +357,23 @@ class GrapeEngine:
         member_F of fom() stay the unweighted F_k.  beta = 0 (or None) switches it off.  Single-device contexts without
         a running cost (include/grape_hip.h)."""
         self._check(self._lib.grape_set_risk(self._h, 0.0 if beta is None else float(beta)))
+
+    def set_trajectory_derivative(self, mode):
+        """grape_set_trajectory_derivative: "first_order" (the default: dP_t/dx[c,t] taken as (-i dt B_c) P_t) or "exact" --
+        observe_vjp, observe_jvp, their device forms and the reuse forms then differentiate the sweep's own expm evaluation
+        per slice (the Frechet derivative, exact to the rounding of the propagators): what torch.autograd.gradcheck on
+        autograd.trajectory and a quasi-Newton solve on a custom loss need.  The contexts observe_vjp serves; a refused call
+        (ValueError here, GrapeError from the library) leaves the previous mode in force.  The running cost's own
+        gradient stays first order."""
+        if mode not in TRAJ_DERIVATIVE_CODES:
+            raise ValueError(f"mode must be one of {sorted(TRAJ_DERIVATIVE_CODES)}")
+        self._check(self._lib.grape_set_trajectory_derivative(self._h, TRAJ_DERIVATIVE_CODES[mode]))
+        self._traj_derivative = mode
+
+    @property
+    def trajectory_derivative(self):
+        """the mode set_trajectory_derivative left in force: "first_order" or "exact" """
+        return self._traj_derivative
 
     def risk_weights(self):
         """grape_get_risk_weights: p (E,) of the last evaluation under set_risk (array 0 of a batch); sum p = sum w."""
