@@ -297,7 +297,9 @@ int grape_set_penalties(grape_ctx *ctx, const double *amp_w, const double *var_w
  *   Lam_{k,j,N} = rho[N-1,j] y_{k,j,N} R_{k,j}
  *   Lam_{k,j,s} = P_{k,s}' Lam_{k,j,s+1} + rho[s-1,j] y_{k,j,s} R_{k,j}      (P_{k,s}: the propagator taking X_s to X_{s+1})
  * This is the derivative of J with dP_t/dx[c,t] replaced by (-i dt) B_c P_t: FIRST ORDER in dt, the same order as the
- * reference's grad_func! (src/GRAPE.jl:261-303) that G itself follows; the exact gradient of J is out of scope.
+ * reference's grad_func! (src/GRAPE.jl:261-303) that G itself follows.  The EXACT gradient of J is a setting of the context:
+ * grape_set_running_cost_derivative(ctx, GRAPE_TRAJ_EXACT), below -- with it a running cost is also served on contexts
+ * created with gradient = exact (either objective), which refuse it otherwise.
  * Instances (lambda: the caller's weight):  C5 with forbidden kets psiF_j: R_j = psiF_j (n x 1 states), rho = +lambda;
  * C6: R = Xt, rho = -lambda / (N D^2), the constant +lambda added by the caller;  C7 for pure states held as n x 1 kets
  * under UnitaryGate: R = psiT (|psiT' psi|^2 = tr(rhoT rho)), rho = -lambda / N, plus the constant.
@@ -669,8 +671,9 @@ int grape_eval_jvp_device(grape_ctx *ctx, const double *d_x, const double *d_xdo
  * the result, the slope / projection tail and the tangent map under bounds / basis, member-chunked contexts, max_batch > 1,
  * the argument checks and the refusals.  The pair stays an exact transpose pair, now of the true derivative:
  * torch.autograd.gradcheck on the read-out passes, and against central differences the deviation is that of the differences.
- * The running cost's own gradient (grape_set_running_cost) STAYS first order, and so does the main objective's unless the
- * context was created with gradient = exact.
+ * The running cost's own gradient (grape_set_running_cost) follows its own setting, grape_set_running_cost_derivative
+ * below (first order by default), and the main objective's stays first order unless the context was created with
+ * gradient = exact.
  * Kernels (grape_get_kernel_names tells which ran): the exact instance of trajectory_vjp_kernel
  * (trajectory_vjp_exact_kernel) stores W_t per slice, traj_frechet_rows_kernel -- one lane (n = 3) or lane pair (n = 2, 4)
  * per (member, slice) -- rebuilds G_t from the physical pulse the evaluation left on the device and writes the row entries
@@ -690,6 +693,42 @@ int grape_eval_jvp_device(grape_ctx *ctx, const double *d_x, const double *d_xdo
  * and on a context that never calls this, every entry point launches the kernels it always did and returns the same bits. */
 typedef enum grape_traj_derivative { GRAPE_TRAJ_FIRST_ORDER = 0, GRAPE_TRAJ_EXACT = 1 } grape_traj_derivative;
 int grape_set_trajectory_derivative(grape_ctx *ctx, int32_t mode);
+
+/* ABI v8 (additive).  The derivative rule of the running cost's gradient (grape_set_running_cost), in every evaluation:
+ * grape_eval, grape_eval_device, the batched forms and grape_lbfgs.  GRAPE_TRAJ_FIRST_ORDER (the default) is the rule
+ * documented at grape_set_running_cost.  GRAPE_TRAJ_EXACT takes the Frechet derivative DF_t of the map the sweep itself
+ * evaluated, as defined above; with X_{k,t} the state BEFORE slice t:
+ *   dJ/dx[c,t] = sum_k w_k Re tr( DF_t[W_{k,t}] B'_kc ) ,   W_{k,t} = X_{k,t} Lam_{k,t+1}' ,   B' = -i dt B
+ *   Lam_{k,N}  = 2 sum_j rho[N-1,j] y_{k,j,N} R_kj
+ *   Lam_{k,s}  = P_{k,s}' Lam_{k,s+1} + 2 sum_j rho[s-1,j] y_{k,j,s} R_kj
+ * -- the w-weighted sum over the members of grape_eval_vjp's exact pull-back with the probes R and the cotangents
+ * ybar_{k,j,s} = 2 rho[s-1,j] y_{k,j,s}, ybar_{k,j,0} = 0.  One derivative per (member, slice) serves all K controls and all
+ * terms.  J itself is unchanged, bit for bit; the penalties, the basis / bounds tails and the ensemble sum work on the
+ * result as ever.
+ * Served where grape_set_running_cost is served -- family 0 (n = 2, 3, 4), GRAPE_UNITARY_GATE with any m, single-device
+ * contexts, member-chunked ones and max_batch > 1 included -- and ALSO on contexts created with gradient = exact, with
+ * objective fom or c1 (J never looks at the objective): there grape_set_running_cost is accepted only while this mode is
+ * exact (with the default mode it is refused as before, the message names "exact"), and switching back to
+ * GRAPE_TRAJ_FIRST_ORDER while a running cost stands on such a context is refused with GRAPE_ERR_UNSUPPORTED.  On a first-order
+ * context the exact mode gives F first order and J exact.  Elsewhere mode = GRAPE_TRAJ_EXACT is refused with
+ * GRAPE_ERR_UNSUPPORTED and grape_set_running_cost's reason ("dimension", "StateTransfer", "c1", "multi-device",
+ * "communicator").  Unchanged: the refusal of a running cost under a risk and of grape_comm_attach / grape_ipc_attach under
+ * a running cost, grape_eval_fom's fallback, grape_get_member_results and member_F WITHOUT J (on gradient = exact contexts
+ * too: J's rows join a private copy of the members' rows), grape_set_trajectory_derivative and everything grape_eval_vjp /
+ * grape_eval_jvp return.
+ * Kernels (grape_get_kernel_names tells which ran): the exact instance of running_cost_kernel (running_cost_exact_kernel)
+ * stores W_t, summed over the terms, per slice; the running-cost instance of traj_frechet_rows_kernel rebuilds G_t from the
+ * physical pulse of the evaluation and writes the K N gradient entries of the member's row; running_cost_fold_kernel
+ * (first-order contexts) or running_cost_join_kernel (gradient = exact contexts) joins the rows to the ensemble sum in member
+ * order.  Scratch: one n x n c128 block per slice and (control array, member) of a workspace block, shared with the exact
+ * trajectory pair (stream order separates the users), grown where the running cost's rows are and counted in
+ * grape_info.workspace_bytes.  No atomics: bitwise reproducible call to call, member-chunked = unchunked, host form = device
+ * form = one-array batch.
+ * A setting like the other grape_set_*: valid any time after grape_create, persists across grape_set_operators, ordered
+ * behind an in-flight grape_eval_device, clears the "trajectory valid" flag.  GRAPE_ERR_INVALID_ARG: mode outside {0, 1}.
+ * After a failure the previous setting stays in force.  With mode = 0, and on a context that never calls this, every
+ * evaluation launches the kernels it always did and returns the same bits. */
+int grape_set_running_cost_derivative(grape_ctx *ctx, int32_t mode);
 
 /* Device-resident L-BFGS: stands in for
  *     Optim.optimize(Optim.only_fg!(topt), x0, Optim.LBFGS(), optim_options)       src/solve.jl:138, :244

@@ -299,6 +299,15 @@ function set_trajectory_derivative!(ctx::GrapeContext, mode::Symbol)
     ctx
 end
 
+# grape_set_running_cost_derivative: :first_order (default) or :exact -- the J part of every gradient then uses the Frechet
+# derivative of the sweep's own expm evaluation per slice; contexts created with gradient = exact take a running cost in the
+# exact mode only (set it before set_running_cost!)
+function set_running_cost_derivative!(ctx::GrapeContext, mode::Symbol)
+    mode in (:first_order, :exact) || throw(ArgumentError("mode must be :first_order or :exact"))
+    check(ctx, ccall((:grape_set_running_cost_derivative, libgrape), Cint, (Ptr{Cvoid}, Int32), ctx.handle, Int32(mode == :exact ? 1 : 0)))
+    ctx
+end
+
 "The kernels the last evaluation launched, in launch order (grape_get_kernel_names, ABI v4)."
 function kernel_names(ctx::GrapeContext)
     need = ccall((:grape_get_kernel_names, libgrape), Cint, (Ptr{Cvoid}, Ptr{UInt8}, Cint), ctx.handle, C_NULL, 0)

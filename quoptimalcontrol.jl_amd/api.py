@@ -112,6 +112,10 @@ class GRAPE:
     running_costs: Any = None      # list of ForbiddenStates / EvolutionTime (new: the reference's C5 / C6 / C7 are called by none
                                    # of its solvers): costs on the intermediate states, added to the objective on the device
                                    # (grape_set_running_cost; n = 2..4, UnitaryGate-type problems, one device)
+    running_cost_derivative: str = "first_order"   # "exact": the gradient of the running costs differentiates the sweep's own
+                                   # expm evaluation per slice (grape_set_running_cost_derivative) instead of taking
+                                   # dP_t/dx as (-i dt B) P_t -- what few, coarse slices need; the figure of merit's own
+                                   # gradient stays the reference's first-order one (ADGRAPE: both exact)
     risk: float = 0.0              # beta of grape_set_risk (new): the optimiser -- host or device -- minimises the soft worst case
                                    # F_beta = (W / beta) log((1 / W) sum_k w_k exp(beta F_k)) over the ensemble instead of its
                                    # weighted mean; res.minimum is F_beta.  0: the mean.  One device, no running costs
@@ -130,6 +134,9 @@ class ADGRAPE:
     devices: Optional[list] = None
     peer_sum: bool = False
     penalties: Any = None
+    running_costs: Any = None      # list of ForbiddenStates / EvolutionTime, as GRAPE's: added to the functional on the device
+                                   # with their EXACT gradient (grape_set_running_cost_derivative, which make_engine sets
+                                   # before the costs: an exact-gradient context takes them in that mode only)
 
 
 @dataclass
@@ -408,6 +415,9 @@ def make_engine(prob, alg, **engine_kw):
     if costs:
         try:
             R, rho, const = running_cost_terms(members, costs, alg.n_slices, wts)
+            mode = "exact" if isinstance(alg, ADGRAPE) else getattr(alg, "running_cost_derivative", "first_order")
+            if mode != "first_order":       # the mode BEFORE the costs: an exact-gradient context refuses them otherwise
+                eng.set_running_cost_derivative(mode)
             eng.set_running_cost(R, rho)
             eng.running_cost_constant = const
         except Exception:
@@ -525,6 +535,8 @@ def save(solres, file_path):
                                                if getattr(alg, "bounds", None) is not None else {}),
                                             **({"running_costs": [c.to_json() for c in alg.running_costs]}
                                                if getattr(alg, "running_costs", None) else {}),
+                                            **({"running_cost_derivative": str(alg.running_cost_derivative)}
+                                               if getattr(alg, "running_cost_derivative", "first_order") != "first_order" else {}),
                                             **({"risk": float(alg.risk)} if getattr(alg, "risk", 0.0) else {})},
                                            default=_json_default)),
     }

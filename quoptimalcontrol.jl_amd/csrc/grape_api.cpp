@@ -191,6 +191,12 @@ struct grape_ctx {
     double2 *d_rc_xs = nullptr;                // general flow: the states behind every slice (allocated by the first evaluation that needs it)
     double *d_rc_rows = nullptr;               // one row of K N + 1 per (control array, member) of a workspace block
     size_t rc_xs_bytes = 0, rc_rows_bytes = 0;
+    // grape_set_running_cost_derivative: GRAPE_TRAJ_EXACT makes the J part of every gradient the exact one --
+    // running_cost_exact_kernel leaves W_t in d_traj_w (shared with the trajectory pair: stream order separates the users)
+    // and the running-cost instance of traj_frechet_rows_kernel writes the rows' gradient entries.  On gradient = exact
+    // contexts d_rc_rows holds one UNWEIGHTED row per member of the whole ensemble: [dJ_k/dx, J_k] plus a copy of the
+    // exact gradient's member row (running_cost_join_kernel), and the ensemble reduction sums it in place of d_member_out.
+    int rc_mode = 0;                           // grape_traj_derivative
     // grape_eval_observables (observe.hip): behind the sweep (and the running-cost kernels) of every member block of ONE
     // evaluation, observe_kernel reads the stored propagators and writes tr(O_kj' X_ks) and X_N.  obs_on is set by the entry
     // point around that evaluation only; the buffers are allocated by the first call that needs them and only ever grow.
@@ -1353,6 +1359,24 @@ extern "C" int grape_set_penalties(grape_ctx *c, const double *amp_w, const doub
     return shard_set_penalties(c, w, on);
 }
 
+// why a running cost whose gradient follows `mode` (grape_traj_derivative) is not served on this context; null: it is.  A
+// gradient = exact context takes the exact mode only, with either objective (J never looks at the objective).
+static const char *why_running_cost_not_served(const grape_ctx *c, int mode)
+{
+    if (const char *why = why_exchange_not_served(c)) return why;
+    if (c->family != 0) return "the operator dimension must be 2, 3 or 4 (the register-resident kernel family)";
+    if (c->cfg.sys_type != GRAPE_UNITARY_GATE)
+        return "StateTransfer / CoherenceTransfer (the sandwich needs a second term) are not served; hold the states as n x m columns under UnitaryGate";
+    if (c->cfg.gradient == GRAPE_GRADIENT_EXACT) {
+        if (mode != GRAPE_TRAJ_EXACT)
+            return "gradient = exact is not served (the running cost's gradient is first order in dt; "
+                   "grape_set_running_cost_derivative(GRAPE_TRAJ_EXACT) makes it exact)";
+        return nullptr;
+    }
+    if (c->cfg.objective != GRAPE_OBJECTIVE_FOM) return "objective = c1 is not served";
+    return nullptr;
+}
+
 extern "C" int grape_set_running_cost(grape_ctx *c, int32_t n_terms, const double *R, const double *rho)
 {
     DeviceGuard guard;
@@ -1363,14 +1387,9 @@ extern "C" int grape_set_running_cost(grape_ctx *c, int32_t n_terms, const doubl
         if (n_terms < 0 || n_terms > 4)
             return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_running_cost: n_terms = " + std::to_string(n_terms) + " (must be in 0..4)");
         if (!rho) return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_running_cost: null rho");
-        const char *why = why_exchange_not_served(c);
-        if (why) {}
-        else if (c->family != 0) why = "the operator dimension must be 2, 3 or 4 (the register-resident kernel family)";
-        else if (c->cfg.sys_type != GRAPE_UNITARY_GATE)
-            why = "StateTransfer / CoherenceTransfer (the sandwich needs a second term) are not served; hold the states as n x m columns under UnitaryGate";
-        else if (c->cfg.gradient == GRAPE_GRADIENT_EXACT) why = "gradient = exact is not served (the running cost's gradient is first order in dt)";
-        else if (c->cfg.objective != GRAPE_OBJECTIVE_FOM) why = "objective = c1 is not served";
-        else if (c->risk_beta != 0.0) why = "a risk is set: grape_set_risk does not serve a running cost (the members' J_k are not in the member rows)";
+        const char *why = why_running_cost_not_served(c, c->rc_mode);
+        if (!why && c->risk_beta != 0.0)
+            why = "a risk is set: grape_set_risk does not serve a running cost (the members' J_k are not in the member rows)";
         if (why) return fail(c, GRAPE_ERR_UNSUPPORTED, std::string("grape_set_running_cost: ") + why);
         const size_t nr = 2 * (size_t)c->cfg.n * c->m * c->cfg.n_ensemble * n_terms, nw = (size_t)c->cfg.n_slices * n_terms;
         if (int rc = check_finite(c, R, nr, "grape_set_running_cost", "R", 2)) return rc;
@@ -1392,6 +1411,28 @@ extern "C" int grape_set_running_cost(grape_ctx *c, int32_t n_terms, const doubl
     c->d_rc_R = (double2 *)d_R;
     c->d_rc_rho = (double *)d_rho;
     c->rc_terms = off ? 0 : n_terms;
+    return GRAPE_OK;
+}
+
+// ---- grape_set_running_cost_derivative: first-order or exact gradient of the running cost -----------------------------------
+extern "C" int grape_set_running_cost_derivative(grape_ctx *c, int32_t mode)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_set_running_cost_derivative: null context");
+    c->traj_valid = false;                                   // (grape_eval_vjp_device's reuse)
+    if (mode != GRAPE_TRAJ_FIRST_ORDER && mode != GRAPE_TRAJ_EXACT)
+        return fail(c, GRAPE_ERR_INVALID_ARG, "grape_set_running_cost_derivative: mode = " + std::to_string(mode) +
+                                              " (must be GRAPE_TRAJ_FIRST_ORDER = 0 or GRAPE_TRAJ_EXACT = 1)");
+    if (mode == GRAPE_TRAJ_EXACT) {
+        if (const char *why = why_running_cost_not_served(c, mode))
+            return fail(c, GRAPE_ERR_UNSUPPORTED, std::string("grape_set_running_cost_derivative: ") + why);
+    } else if (c->rc_terms > 0 && c->cfg.gradient == GRAPE_GRADIENT_EXACT) {
+        return fail(c, GRAPE_ERR_UNSUPPORTED, "grape_set_running_cost_derivative: a running cost is set on a gradient = exact context "
+                                              "(it takes the exact mode only; switch the running cost off first)");
+    }
+    if (c->is_group) return GRAPE_OK;                        // (switching off what can never be on)
+    if (int rc = drain(c, c)) return rc;                     // (behind an in-flight grape_eval_device)
+    c->rc_mode = mode;
     return GRAPE_OK;
 }
 
@@ -2496,10 +2537,18 @@ static void copy_out_rows(const double *h_fg, int n_x, size_t len, double *F, do
 // capacity, flow) -- sized here because grape_set_operators may re-plan the workspace and decides the flow
 static int rc_ensure(grape_ctx *c)
 {
-    const size_t rows = sizeof(double) * (size_t)c->Ec * ws_batch(c) * (KN(c) + 1);
+    // (gradient = exact contexts: one row per member of the WHOLE ensemble -- the reduction reads them in one piece; their
+    // batches run array by array)
+    const size_t nrows = c->cfg.gradient == GRAPE_GRADIENT_EXACT ? (size_t)c->cfg.n_ensemble : (size_t)c->Ec * ws_batch(c);
+    const size_t rows = sizeof(double) * nrows * (KN(c) + 1);
     const size_t xs = c->unitary ? 0 : sizeof(double2) * (size_t)c->Ec * ws_batch(c) * c->S * c->CH * c->cfg.n * c->m;
     if (int rc = grow(c, &c->d_rc_rows, &c->rc_rows_bytes, rows, "grape_set_running_cost", "the members' running-cost rows")) return rc;
-    return grow(c, &c->d_rc_xs, &c->rc_xs_bytes, xs, "grape_set_running_cost", "the stored states of the general flow");
+    if (int rc = grow(c, &c->d_rc_xs, &c->rc_xs_bytes, xs, "grape_set_running_cost", "the stored states of the general flow")) return rc;
+    if (c->rc_terms > 0 && c->rc_mode == GRAPE_TRAJ_EXACT) { // W_t: one n x n block per slice and (control array, member)
+        const size_t w = sizeof(double2) * (size_t)c->Ec * ws_batch(c) * c->S * c->CH * c->cfg.n * c->cfg.n;
+        return grow(c, &c->d_traj_w, &c->traj_w_bytes, w, "grape_set_running_cost_derivative", "the exact derivative's per-slice blocks");
+    }
+    return GRAPE_OK;
 }
 
 // grape_set_risk: the buffers an evaluation needs -- the weights and F_beta of max_batch arrays, and the members' rows where the
@@ -2769,6 +2818,14 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
                 r.rc_rho = c->d_rc_rho;
                 r.rc_xs = c->d_rc_xs;
                 r.rc_rows = c->d_rc_rows;
+                if (c->rc_mode == GRAPE_TRAJ_EXACT) {        // grape_set_running_cost_derivative: W_t, then the Frechet rows
+                    r.rc_exact = 1;
+                    r.traj_w = c->d_traj_w;
+                    if (exact) {                             // unweighted, at the members' places in the whole ensemble's rows
+                        r.rc_unweighted = 1;
+                        r.rc_rows = c->d_rc_rows + (size_t)lo * Qrow;
+                    }
+                }
                 HIP_TRY(c, launch_small_family(c, 0, mode, r, stream));
             }
             if (c->obs_on) {                                 // grape_eval_observables: the read-out of these members
@@ -2818,6 +2875,13 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
                 xq.w1_in = c->exact_w1 ? 1 : 0;
                 xq.zphi = q.zphi;
                 HIP_TRY(c, grape::launch_exact_grad(c->cfg.n, c->cfg.sys_type != GRAPE_UNITARY_GATE, xq, stream));
+                if (rc_on) {                                 // the members' exact rows join their [dJ_k/dx, J_k], in a private copy
+                    SweepParams r = q;
+                    r.rc_only = 2;
+                    r.member_out = xq.member_out;
+                    r.rc_rows = c->d_rc_rows + (size_t)lo * Qrow;
+                    HIP_TRY(c, launch_small_family(c, 0, mode, r, stream));
+                }
             }
             return GRAPE_OK;
         }
@@ -2902,7 +2966,7 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
     }
     if (timed) HIP_TRY(c, hipEventRecord(e1, stream));
     if (exact)
-        HIP_TRY(c, grape::launch_reduce(c->d_member_out, c->d_wts, c->d_partial, d_fg, p.E, (int)(KN(c) + 1), c->ksplit,
+        HIP_TRY(c, grape::launch_reduce(rc_on ? c->d_rc_rows : c->d_member_out, c->d_wts, c->d_partial, d_fg, p.E, (int)(KN(c) + 1), c->ksplit,
                                         stream, with_risk(c, with_pen(c, done, d_x), c->risk_slot)));
     else if (direct || fold)
         ;                                                    // the sweep / forms kernel has written [G, F] (and the flag)

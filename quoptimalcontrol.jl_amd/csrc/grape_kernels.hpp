@@ -162,7 +162,7 @@ struct SweepParams {
     int32_t rc_Etot;         // members of the whole ensemble: term stride of rc_R
     const double2 *rc_R;     // (n, m, rc_Etot, rc_terms) column-major, advanced to this launch's first member
     const double *rc_rho;    // (N, rc_terms): entry [s - 1, j] weights the state after s slices
-    double2 *rc_xs;          // general flow: X_{t+1} per slice, chunk-major like props with n m elements per slice
+    double2 *rc_xs;          // general flow: X_{t+1} per slice (rc_exact: X_t), chunk-major like props with n m elements per slice
     double *rc_rows;         // (K N + 1) per (control array, member) of this launch: w_k [dJ_k/dx, J_k]
     // grape_eval_observables (observe.hip): launch_sweep_small / launch_sweep_pair hand a launch with obs_only set to
     // observe_kernel INSTEAD of the sweep: behind the sweep of the same members (one control array) it reads the propagators
@@ -226,6 +226,14 @@ struct SweepParams {
     int32_t traj_exact;
     double2 *traj_w;         // one n x n block per (member of the launch, slice), chunk-major like props
     const double *traj_x;    // (K, N) the PHYSICAL pulse the stored propagators were formed from
+    // grape_set_running_cost_derivative, GRAPE_TRAJ_EXACT: an rc_only launch with rc_exact set runs running_cost_exact_kernel
+    // (W_t = X_t Lam_{t+1}' summed over the terms into traj_w, the J entry into rc_rows) + the running-cost instance of
+    // traj_frechet_rows_kernel (the K N gradient entries of rc_rows, from the pulse x of the launch itself) in front of the
+    // fold.  rc_unweighted (gradient = exact contexts): the rows carry no w_k and nothing is folded; rc_only = 2, behind the
+    // exact gradient of the same members: running_cost_join_kernel alone, rc_rows += the members' rows in member_out.
+    // (Appended: the offsets of every field above stay what they were.)
+    int32_t rc_exact;
+    int32_t rc_unweighted;
 };
 // static LDS of observe_kernel (vjp = false) / trajectory_vjp_kernel (vjp = true) at operator dimension n with m state
 // columns: the scans' wave totals.  What the host layer subtracts from the device's LDS per workgroup to get the staged

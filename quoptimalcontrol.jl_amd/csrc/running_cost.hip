@@ -21,6 +21,9 @@
 //   6  the same backward walk from the true incoming costate: Lam_t+1 at every slice, M = X_t+1 Lam_t+1', and the K traces
 //      2 Re tr(B'_c M) weighted by w_k -- stored to (term 0) or added to (later terms; same lane, program order) the
 //      member's row
+// The traces above are the FIRST-ORDER rule.  grape_set_running_cost_derivative(GRAPE_TRAJ_EXACT) replaces them with
+//   dJ/dx[c,t] = sum_k w_k 2 Re tr( DF_t[W_{k,t}] B'_kc ) ,   W_{k,t} = X_{k,t} sum_j Lam_{k,j,t+1}'
+// DF_t the Frechet derivative of the map the sweep evaluated (frechet.hpp): the EXACT instance below + traj_frechet.hip.
 // Ragged decompositions: a lane whose chunk starts at or behind N owns no slice (Q = 1, b = 0), the last chunk may be short.
 // No atomics, plain vector stores; the fold kernel below adds the members' rows to the sweep's per-workgroup rows in member
 // order, so the ensemble sum that follows is the one it always was and results are bitwise reproducible.
@@ -32,7 +35,15 @@ namespace grape {
 
 // ops_all / r_all / rho / wts_all are separate `const __restrict__` arguments so that the wave-uniform operator, probe and
 // weight entries can be fetched with scalar loads (as in sweep_small.hip).  UNI: every propagator is unitary.
-template <int N, int M, bool UNI, int MAXT>
+// EXACT (grape_set_running_cost_derivative, GRAPE_TRAJ_EXACT; reported as running_cost_exact_kernel): walk 6 stores
+// W_t = X_t Lam_{t+1}' (n x n whatever m is; X_t the state BEFORE slice t) chunk-major into SweepParams::traj_w instead of
+// forming the K traces -- term 0 stores, later terms add (same lane, program order), so one block per slice carries the sum
+// over the terms and ONE Frechet derivative per (member, slice) serves all controls and all terms (the running-cost instance
+// of traj_frechet_rows_kernel, behind this kernel, writes the K N gradient entries of the row).  The per-term walks stay:
+// J's chain of FMAs is the first-order instance's, bit for bit.  Unitary flow: X_t is at hand after the step back
+// X_t = P_t' X_{t+1}; general flow: the forward walk stores the state BEFORE every slice (slot jj: X_{lo+jj}, slot 0 the
+// chunk's start state) and the walks carry X_{t+1} = slot jj + 1 (the chunk's end state for the last slice) in registers.
+template <int N, int M, bool UNI, int MAXT, bool EXACT = false>
 __global__ __launch_bounds__(MAXT) void running_cost_kernel(const double2 *__restrict__ ops_all,
                                                             const double2 *__restrict__ r_all,
                                                             const double *__restrict__ rho,
@@ -59,7 +70,7 @@ __global__ __launch_bounds__(MAXT) void running_cost_kernel(const double2 *__res
     const double2 *__restrict__ opB = ops + NN;
     const double2 *__restrict__ opXi = ops + (size_t)(1 + K) * NN;
     double *__restrict__ row = p.rc_rows + (size_t)k * ((size_t)K * Nsl + 1);
-    const double wk = wts_all[kl];
+    const double wk = (EXACT && p.rc_unweighted) ? 1.0 : wts_all[kl];
 
     // ---------------------------------------------------------------- 1: chunk product
     CMat<N> Q, P, T;
@@ -110,9 +121,12 @@ __global__ __launch_bounds__(MAXT) void running_cost_kernel(const double2 *__res
             Xhi = Xs;
             for (int jj = 0; jj < cnt; ++jj) {
                 rc_load_mat(P, Pw + (size_t)jj * NN * stride, stride);
+                if constexpr (EXACT)
+                    rstore_ws(Xw + (size_t)jj * NM * stride, stride, Xhi);  // the state BEFORE slice lo + jj
                 rmul(Xs, P, Xhi);
                 Xhi = Xs;
-                rstore_ws(Xw + (size_t)jj * NM * stride, stride, Xhi);      // the state AFTER slice lo + jj
+                if constexpr (!EXACT)
+                    rstore_ws(Xw + (size_t)jj * NM * stride, stride, Xhi);  // the state AFTER slice lo + jj
             }
         }
     }
@@ -127,8 +141,10 @@ __global__ __launch_bounds__(MAXT) void running_cost_kernel(const double2 *__res
             CRect<N, M> X = Xhi, Tm;
             for (int jj = cnt - 1; jj >= 0; --jj) {
                 const int t = lo + jj;               // slice index; the state behind it is X_{t+1}, weighted by rho[t]
-                if (!UNI)
-                    rload_ws(X, Xw + (size_t)jj * NM * stride, stride);
+                if constexpr (!EXACT) {
+                    if (!UNI)
+                        rload_ws(X, Xw + (size_t)jj * NM * stride, stride);
+                }
                 rc_load_mat(P, Pw + (size_t)jj * NN * stride, stride);
                 double yr = 0.0, yi = 0.0;           // y = tr(R' X)
 #pragma unroll
@@ -147,7 +163,51 @@ __global__ __launch_bounds__(MAXT) void running_cost_kernel(const double2 *__res
                     Lam.re[e] = fma(cr, R.re[e], fma(-ci, R.im[e], Lam.re[e]));
                     Lam.im[e] = fma(cr, R.im[e], fma(ci, R.re[e], Lam.im[e]));
                 }
-                if (emit) {
+                if constexpr (EXACT) {
+                    if (UNI) {
+                        rmul_ah(Tm, P, X);           // X_t = P_t' X_{t+1}
+                        X = Tm;
+                    } else {
+                        rload_ws(X, Xw + (size_t)jj * NM * stride, stride);
+                    }
+                    if (emit) {
+                        // W_t = X_t Lam_{t+1}' of this term, column by column (rmul_a_bh's sums): a column is stored
+                        // (term 0) or added to the block (later terms) before the next one is formed -- the scheduling
+                        // barriers keep the whole block and its n^2 loads from being live at once
+                        double2 *__restrict__ wp = p.traj_w + ((size_t)k * S + jj) * NN * stride + L;
+#pragma unroll
+                        for (int b2 = 0; b2 < N; ++b2) {
+                            double wr[N], wi[N];
+#pragma unroll
+                            for (int a2 = 0; a2 < N; ++a2) {
+                                double sr = 0.0, si = 0.0;
+#pragma unroll
+                                for (int q = 0; q < M; ++q) {
+                                    const double ar = X.re[a2 + q * N], ai = X.im[a2 + q * N];
+                                    const double br = Lam.re[b2 + q * N], bi = -Lam.im[b2 + q * N];
+                                    sr = fma(ar, br, sr);
+                                    sr = fma(-ai, bi, sr);
+                                    si = fma(ar, bi, si);
+                                    si = fma(ai, br, si);
+                                }
+                                wr[a2] = sr;
+                                wi[a2] = si;
+                            }
+                            if (j == 0) {
+#pragma unroll
+                                for (int a2 = 0; a2 < N; ++a2)
+                                    wp[(a2 + b2 * N) * stride] = make_double2(wr[a2], wi[a2]);
+                            } else {
+#pragma unroll
+                                for (int a2 = 0; a2 < N; ++a2) {
+                                    const double2 v = wp[(a2 + b2 * N) * stride];
+                                    wp[(a2 + b2 * N) * stride] = make_double2(v.x + wr[a2], v.y + wi[a2]);
+                                }
+                            }
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                    }
+                } else if (emit) {
                     CMat<N> Mx;
                     rmul_a_bh(Mx, X, Lam);           // X Lam'
                     for (int c = 0; c < K; ++c) {
@@ -167,9 +227,11 @@ __global__ __launch_bounds__(MAXT) void running_cost_kernel(const double2 *__res
                 }
                 rmul_ah(Tm, P, Lam);                 // pull the costate back over slice t
                 Lam = Tm;
-                if (UNI) {
-                    rmul_ah(Tm, P, X);
-                    X = Tm;
+                if constexpr (!EXACT) {
+                    if (UNI) {
+                        rmul_ah(Tm, P, X);
+                        X = Tm;
+                    }
                 }
             }
         };
@@ -271,6 +333,27 @@ __global__ __launch_bounds__(256) void running_cost_fold_kernel(const double *__
     block_out[(size_t)blockIdx.x * Q + q] = acc;
 }
 
+// gradient = exact contexts: rows[i] = member_rows[i] + rows[i] over the (K N + 1) entries of the launch's members -- the
+// unweighted [dJ_k/dx, J_k] join a private copy of the exact gradient's member rows, one addition per number; the weighted
+// ensemble reduction behind sums that copy in its own fixed order, and the context's member rows stay without J
+__global__ __launch_bounds__(256) void running_cost_join_kernel(const double *__restrict__ member_rows, double *__restrict__ rows,
+                                                                size_t total)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < total)
+        rows[i] = member_rows[i] + rows[i];
+}
+
+static hipError_t rc_launch_join(const SweepParams &p, hipStream_t stream)
+{
+    const size_t total = (size_t)p.E * ((size_t)p.K * p.N + 1);
+    if (!p.member_out || !p.rc_rows || p.E < 1 || p.K < 1 || p.N < 1 || p.n_x != 1 || (total + 255) / 256 > 0x7fffffffull)
+        return hipErrorInvalidConfiguration;
+    GRAPE_LAUNCH(running_cost_join_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p.member_out, p.rc_rows,
+                 total);
+    return hipGetLastError();
+}
+
 template <int N, int M>
 static hipError_t rc_launch_nm(const SweepParams &p, hipStream_t stream)
 {
@@ -280,15 +363,34 @@ static hipError_t rc_launch_nm(const SweepParams &p, hipStream_t stream)
         (!p.rc_unitary && !p.rc_xs) || p.rc_terms < 1)
         return hipErrorInvalidConfiguration;
     const dim3 grid(p.E * p.n_x), block(threads);
-    if (p.rc_unitary)
-        GRAPE_LAUNCH_AS("running_cost_kernel", (running_cost_kernel<N, M, true, MAXT>), grid, block, 0, stream, p.ops, p.rc_R,
-                        p.rc_rho, p.wts, p);
-    else
-        GRAPE_LAUNCH_AS("running_cost_kernel", (running_cost_kernel<N, M, false, MAXT>), grid, block, 0, stream, p.ops, p.rc_R,
-                        p.rc_rho, p.wts, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return e;
+    hipError_t e = hipSuccess;
+    if (p.rc_exact) {
+        // the exact derivative mode: W_t into traj_w, then one Frechet derivative per (member, slice) into the rows
+        if (!p.traj_w || !p.x || !p.wts || (p.rc_unweighted && p.n_x != 1))
+            return hipErrorInvalidConfiguration;
+        if (p.rc_unitary)
+            GRAPE_LAUNCH_AS("running_cost_exact_kernel", (running_cost_kernel<N, M, true, MAXT, true>), grid, block, 0, stream, p.ops,
+                            p.rc_R, p.rc_rho, p.wts, p);
+        else
+            GRAPE_LAUNCH_AS("running_cost_exact_kernel", (running_cost_kernel<N, M, false, MAXT, true>), grid, block, 0, stream, p.ops,
+                            p.rc_R, p.rc_rho, p.wts, p);
+        e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+        e = run_traj_frechet(N, false, p, stream);
+        if (e != hipSuccess || p.rc_unweighted)          // (gradient = exact contexts: the join follows the exact gradient)
+            return e;
+    } else {
+        if (p.rc_unitary)
+            GRAPE_LAUNCH_AS("running_cost_kernel", (running_cost_kernel<N, M, true, MAXT>), grid, block, 0, stream, p.ops, p.rc_R,
+                            p.rc_rho, p.wts, p);
+        else
+            GRAPE_LAUNCH_AS("running_cost_kernel", (running_cost_kernel<N, M, false, MAXT>), grid, block, 0, stream, p.ops, p.rc_R,
+                            p.rc_rho, p.wts, p);
+        e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
     const int Qr = p.K * p.N + 1;
     GRAPE_LAUNCH(running_cost_fold_kernel, dim3(p.BPX * p.n_x, (Qr + 255) / 256), dim3(256), 0, stream, p.rc_rows, p.block_out,
                  p.MPB, p.E, p.BPX, Qr);
@@ -297,6 +399,8 @@ static hipError_t rc_launch_nm(const SweepParams &p, hipStream_t stream)
 
 hipError_t run_running_cost(int n, const SweepParams &p, hipStream_t stream)
 {
+    if (p.rc_only == 2)
+        return rc_launch_join(p, stream);
     switch (n * 8 + p.rc_m) {
     case 2 * 8 + 1: return rc_launch_nm<2, 1>(p, stream);
     case 2 * 8 + 2: return rc_launch_nm<2, 2>(p, stream);

@@ -43,7 +43,7 @@ EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_oper
            "grape_comm_unique_id", "grape_comm_attach", "grape_ipc_export", "grape_ipc_attach",
            "grape_eval", "grape_eval_device", "grape_eval_batch", "grape_eval_batch_device", "grape_eval_fom", "grape_eval_observables",
            "grape_eval_vjp", "grape_eval_observables_device", "grape_eval_vjp_device", "grape_eval_jvp", "grape_eval_jvp_device",
-           "grape_set_trajectory_derivative",
+           "grape_set_trajectory_derivative", "grape_set_running_cost_derivative",
            "grape_lbfgs", "grape_lbfgs_get_trace",
            "grape_get_member_results", "grape_get_trajectory",
            "grape_get_kernel_time", "grape_get_kernel_samples", "grape_get_kernel_names", "grape_get_group_timing", "grape_get_phase_stamps",
@@ -150,6 +150,7 @@ def load_library():
     L.grape_eval_jvp.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
     L.grape_eval_jvp_device.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
     L.grape_set_trajectory_derivative.argtypes = [vp, i32]
+    L.grape_set_running_cost_derivative.argtypes = [vp, i32]
     L.grape_lbfgs.argtypes = [vp, vp, C.POINTER(GrapeLbfgsOptions), vp, C.POINTER(GrapeLbfgsResult)]
     L.grape_get_member_results.argtypes = [vp, vp, vp]
     L.grape_get_trajectory.argtypes = [vp, i32, vp, vp, vp]
@@ -244,6 +245,7 @@ class GrapeEngine:
                           {"reference": 0, "exact": 1}[gradient], {"fom": 0, "c1": 1}[objective])
         self.max_batch = max(1, int(max_batch))
         self._traj_derivative = "first_order"
+        self._rc_derivative = "first_order"
         h = C.c_void_p()
         rc = self._lib.grape_create(C.byref(cfg), C.byref(h))
         if rc:
@@ -285,8 +287,9 @@ class GrapeEngine:
         term, the same for every member; (E, n, m): one term per member; (n_terms, 1, n, m): shared by the members; at most 4
         terms.  rho: slice weights (n_terms, N), or (N,) / a scalar for every term; rho[j, s-1] weights the state after s
         slices.  From now on every evaluation returns F + sum_k w_k sum_j sum_s rho[j, s-1] |tr(R_kj' X_ks)|^2 and its
-        first-order gradient (include/grape_hip.h).  R=None switches the term off.  n = 2..4, UnitaryGate-type states,
-        single-device contexts; member_results() stays without it."""
+        gradient -- first order in dt, or exact after set_running_cost_derivative("exact") (include/grape_hip.h).  R=None
+        switches the term off.  n = 2..4, UnitaryGate-type states, single-device contexts (gradient="exact" ones in the
+        exact mode only); member_results() stays without it."""
         if R is None:
             self._check(self._lib.grape_set_running_cost(self._h, 0, None, None))
             return
@@ -364,7 +367,7 @@ class GrapeEngine:
         per slice (the Frechet derivative, exact to the rounding of the propagators): what torch.autograd.gradcheck on
         autograd.trajectory and a quasi-Newton solve on a custom loss need.  The contexts observe_vjp serves; a refused call
         (ValueError here, GrapeError from the library) leaves the previous mode in force.  The running cost's own
-        gradient stays first order."""
+        gradient follows set_running_cost_derivative."""
         if mode not in TRAJ_DERIVATIVE_CODES:
             raise ValueError(f"mode must be one of {sorted(TRAJ_DERIVATIVE_CODES)}")
         self._check(self._lib.grape_set_trajectory_derivative(self._h, TRAJ_DERIVATIVE_CODES[mode]))
@@ -374,6 +377,23 @@ class GrapeEngine:
     def trajectory_derivative(self):
         """the mode set_trajectory_derivative left in force: "first_order" or "exact" """
         return self._traj_derivative
+
+    def set_running_cost_derivative(self, mode):
+        """grape_set_running_cost_derivative: "first_order" (the default, the rule of set_running_cost) or "exact" -- the J part
+        of every gradient (eval, eval_device, the batched forms, lbfgs) then differentiates the sweep's own expm evaluation per
+        slice (the Frechet derivative, one per member and slice for all controls and terms); J itself keeps its bits.  Served
+        where set_running_cost is, and on contexts created with gradient="exact" (either objective), which take a running
+        cost in this mode only: set it BEFORE set_running_cost there, and switch the cost off before going back.  A refused
+        call (ValueError here, GrapeError from the library) leaves the previous mode in force."""
+        if mode not in TRAJ_DERIVATIVE_CODES:
+            raise ValueError(f"mode must be one of {sorted(TRAJ_DERIVATIVE_CODES)}")
+        self._check(self._lib.grape_set_running_cost_derivative(self._h, TRAJ_DERIVATIVE_CODES[mode]))
+        self._rc_derivative = mode
+
+    @property
+    def running_cost_derivative(self):
+        """the mode set_running_cost_derivative left in force: "first_order" or "exact" """
+        return self._rc_derivative
 
     def risk_weights(self):
         """grape_get_risk_weights: p (E,) of the last evaluation under set_risk (array 0 of a batch); sum p = sum w."""
