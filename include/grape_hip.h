@@ -657,6 +657,41 @@ int grape_eval_jvp(grape_ctx *ctx, const double *x, const double *xdot, int32_t 
 int grape_eval_jvp_device(grape_ctx *ctx, const double *d_x, const double *d_xdot, int32_t n_obs, int32_t per_member,
                           const double *d_O, double *d_ydot, double *d_Xdot_final, void *stream);
 
+/* ABI v8 (additive).  Several tangent directions per call: a block of Jacobian columns (Gauss-Newton / Levenberg-Marquardt on
+ * a least-squares trajectory loss, sensitivity and Fisher-type analyses) without repeating what does not depend on the
+ * direction -- the sweep, the chunk products, the prefix scan of the propagators, the walk of the states and the passes over
+ * the stored propagators.
+ *   xdot        f64  (K, cols, n_dir)   cols = N, or M in parameter mode; the direction index is slowest and every direction
+ *                                       has the shape and the coordinates grape_eval_jvp takes
+ *   ydot        c128 (N+1, n_obs, E, n_dir), Xdot_final c128 (n, m, E, n_dir): direction-slowest too; either may be NULL
+ * 1 <= n_dir <= GRAPE_MAX_JVP_DIRECTIONS, anything else GRAPE_ERR_INVALID_ARG with the value in the message.  Every other
+ * argument check, the refusals (the context's first), GRAPE_ERR_NOT_READY before grape_set_operators and the not-finite check
+ * of O and xdot are grape_eval_jvp's.
+ * DEFINING PROPERTY: block d of ydot / Xdot_final is bit for bit what grape_eval_jvp returns for direction d alone on the same
+ * context -- in both modes of grape_set_trajectory_derivative, under a basis and / or bounds, on member-chunked contexts (the
+ * unchunked bits), with forced slices_per_lane / waves_per_member and under a standing running cost, penalties or risk (none
+ * of which enter).  Exact linearity in xdot and the transpose identity with grape_eval_vjp follow from it.
+ * trajectory_jvp_multi_kernel carries a block of directions (2 to 8, by operator dimension and state columns) next to one
+ * state walk; per direction its operations and their order are trajectory_jvp_kernel's.  Where it did not measure faster per
+ * direction than the single kernel, and for decompositions of more than 256 time chunks per member, the library runs
+ * trajectory_jvp_kernel once per direction behind the ONE sweep: the same bits, and grape_get_kernel_names tells which ran
+ * (environment GRAPE_JVP_MULTI=0 / 1 forces the choice).  In the exact mode every direction of a block has its own E_t image
+ * in the context's scratch (shared with the exact pull-back and the exact running cost; stream order separates the users).
+ * An eval -> jvp_multi -> eval sequence returns the first evaluation's bits. */
+#define GRAPE_MAX_JVP_DIRECTIONS 8
+int grape_eval_jvp_multi(grape_ctx *ctx, const double *x, int32_t n_dir, const double *xdot, int32_t n_obs, int32_t per_member,
+                         const double *O, double *ydot, double *Xdot_final);
+
+/* ABI v8 (additive).  The device form of grape_eval_jvp_multi under the rules of grape_eval_jvp_device: device arrays in the
+ * layouts above, asynchronous on `stream`, no staging beyond the single device form's (under a pulse map the physical
+ * directions go into scratch of the context, which grows only behind a pending device call and is counted in
+ * grape_info.workspace_bytes, as are the further E_t images of the exact mode), device arrays not checked for non-finite
+ * entries, results bit for bit the host form's.  The "trajectory valid" flag is set under grape_eval_jvp_device's conditions;
+ * d_x = NULL runs along the stored trajectory with no sweep, keeps the flag set and returns the bits of the call with d_x;
+ * with the flag clear or on a member-chunked context GRAPE_ERR_NOT_READY with the existing messages. */
+int grape_eval_jvp_multi_device(grape_ctx *ctx, const double *d_x, int32_t n_dir, const double *d_xdot, int32_t n_obs,
+                                int32_t per_member, const double *d_O, double *d_ydot, double *d_Xdot_final, void *stream);
+
 /* ABI v8 (additive).  The derivative rule of the pull-back and the push-forward along the trajectory: all six entry points --
  * grape_eval_vjp, grape_eval_vjp_device, grape_eval_jvp, grape_eval_jvp_device and the d_x = NULL reuse forms of both device
  * calls.  GRAPE_TRAJ_FIRST_ORDER (the default) takes dP_t/dx[c,t] as (-i dt B_c) P_t, as documented above.  GRAPE_TRAJ_EXACT

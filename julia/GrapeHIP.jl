@@ -291,6 +291,39 @@ function observables_jvp_device(ctx::GrapeContext, d_x::Ptr{Cvoid}, d_xdot::Ptr{
     ctx
 end
 
+# grape_eval_jvp_multi: `observables_jvp` for a block of directions behind ONE evaluation of x.  xdot is (K, N, n_dir) (the
+# direction index slowest, 1 <= n_dir <= 8); ydot (N+1, n_obs, E, n_dir) and Xdf (n, m, E, n_dir) are written in place and
+# returned.  Slice [:, :, :, d] of either is bit for bit what `observables_jvp` returns for xdot[:, :, d].  (Written, NOT
+# executed, like `observables_jvp`; the Python binding makes the same call and is tested on the GPU.)
+function eval_jvp_multi!(ydot::Array{ComplexF64,4}, Xdf::Array{ComplexF64,4}, ctx::GrapeContext, x::Matrix{Float64},
+                         xdot::Array{Float64,3}, O::Array{ComplexF64})
+    size(x) == (ctx.K, ctx.N) || throw(DimensionMismatch("x must be (n_controls, n_slices)"))
+    n_dir = size(xdot, 3)
+    size(xdot) == (ctx.K, ctx.N, n_dir) || throw(DimensionMismatch("xdot must be (n_controls, n_slices, n_dir)"))
+    1 <= n_dir <= 8 || throw(ArgumentError("eval_jvp_multi!: 1 to 8 directions (GRAPE_MAX_JVP_DIRECTIONS)"))
+    n_obs = size(O, ndims(O))
+    (ndims(O) == 3 && size(O) == (ctx.n, ctx.m, n_obs)) || (ndims(O) == 4 && size(O) == (ctx.n, ctx.m, ctx.E, n_obs)) ||
+        throw(DimensionMismatch("O must be (n, m, n_obs) or (n, m, E, n_obs) with the context's n, m and E"))
+    1 <= n_obs <= 16 || throw(ArgumentError("eval_jvp_multi!: 1 to 16 probes"))
+    size(ydot) == (ctx.N + 1, n_obs, ctx.E, n_dir) || throw(DimensionMismatch("ydot must be (N+1, n_obs, E, n_dir)"))
+    size(Xdf) == (ctx.n, ctx.m, ctx.E, n_dir) || throw(DimensionMismatch("Xdf must be (n, m, E, n_dir)"))
+    GC.@preserve x xdot O ydot Xdf check(ctx, ccall((:grape_eval_jvp_multi, libgrape), Cint,
+                                                    (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Int32, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{ComplexF64}),
+                                                    ctx.handle, x, Int32(n_dir), xdot, Int32(n_obs), Int32(ndims(O) == 4 ? 1 : 0), O, ydot, Xdf))
+    ydot, Xdf
+end
+
+# grape_eval_jvp_multi_device: the same on device memory (raw device pointers in the layouts above), asynchronous on `stream`;
+# d_x = C_NULL runs along the stored trajectory without a sweep.
+function eval_jvp_multi_device!(ctx::GrapeContext, d_x::Ptr{Cvoid}, n_dir::Integer, d_xdot::Ptr{Cvoid}, n_obs::Integer,
+                                per_member::Bool, d_O::Ptr{Cvoid}, d_ydot::Ptr{Cvoid}, d_Xdot_final::Ptr{Cvoid};
+                                stream::Ptr{Cvoid} = C_NULL)
+    check(ctx, ccall((:grape_eval_jvp_multi_device, libgrape), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                     ctx.handle, d_x, Int32(n_dir), d_xdot, Int32(n_obs), Int32(per_member ? 1 : 0), d_O, d_ydot, d_Xdot_final, stream))
+    ctx
+end
+
 # grape_set_trajectory_derivative: :first_order (default) or :exact -- observables_vjp / observables_jvp, their device forms and
 # the reuse forms then use the Frechet derivative of the sweep's own expm evaluation per slice instead of (-i dt B) P
 function set_trajectory_derivative!(ctx::GrapeContext, mode::Symbol)

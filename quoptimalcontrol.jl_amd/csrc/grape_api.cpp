@@ -248,6 +248,9 @@ struct grape_ctx {
     const double2 *jvp_O_call = nullptr;
     const double *jvp_xdot_call = nullptr;
     double2 *jvp_ydot_call = nullptr, *jvp_xf_call = nullptr;
+    // grape_eval_jvp_multi: directions of the call in flight (0: the single call), each with the single call's arrays one
+    // behind the other; jvp_multi: trajectory_jvp_multi_kernel where it serves the shape (GRAPE_JVP_MULTI, else the table)
+    int jvp_ndir = 0, jvp_multi = 0;
     int lds_cap = 0;                          // LDS bytes a workgroup of this device may hold (queried by the first device form)
     // The workspace holds the complete trajectory (every member's propagators, and the slope array of a pulse map) of the last
     // device form: grape_eval_vjp_device may pull back along it without a sweep (d_x == NULL).  Set by a successful device form
@@ -2615,9 +2618,10 @@ static bool traj_exact(const grape_ctx *c) { return c->traj_mode == GRAPE_TRAJ_E
 
 // GRAPE_TRAJ_EXACT: the scratch of the exact instances behind the CURRENT workspace plan -- one n x n block per slice and
 // member of a workspace block (the size of one control array's propagators), shared by W_t and E_t, and the physical pulse
-static int traj_exact_ensure(grape_ctx *c, const char *who)
+// (images > 1: grape_eval_jvp_multi, one E_t image per direction of a block of trajectory_jvp_multi_kernel)
+static int traj_exact_ensure(grape_ctx *c, const char *who, int images = 1)
 {
-    const size_t w = sizeof(double2) * (size_t)c->Ec * c->S * c->CH * c->cfg.n * c->cfg.n;
+    const size_t w = sizeof(double2) * (size_t)c->Ec * c->S * c->CH * c->cfg.n * c->cfg.n * (size_t)images;
     if (int rc = grow(c, &c->d_traj_w, &c->traj_w_bytes, w, who, "the exact trajectory derivative's per-slice blocks")) return rc;
     return grow(c, &c->d_traj_x, &c->traj_x_bytes, sizeof(double) * KN(c), who, "the physical pulse of the stored trajectory");
 }
@@ -2673,7 +2677,31 @@ static SweepParams jvp_params(const grape_ctx *c, const SweepParams &q, int lo)
     v.jvp_ydot = c->jvp_has_y ? c->jvp_ydot_call : nullptr;
     v.jvp_xf = c->jvp_has_x ? c->jvp_xf_call : nullptr;
     traj_exact_params(c, v);
+    if (c->jvp_ndir > 0) {                                   // grape_eval_jvp_multi: the single call's arrays, direction-slowest
+        v.jvp_ndir = c->jvp_ndir;
+        v.jvp_multi = c->jvp_multi;
+        v.jvp_dir_xdot = (int64_t)(pulse_map(c) ? KN(c) : KP(c));
+        v.jvp_dir_ydot = (int64_t)((size_t)c->cfg.n_slices + 1) * c->jvp_n * c->cfg.n_ensemble;
+        v.jvp_dir_xf = (int64_t)c->cfg.n * c->m * c->cfg.n_ensemble;
+        v.jvp_dir_w = (int64_t)c->Ec * c->S * c->CH * c->cfg.n * c->cfg.n;
+    }
     return v;
+}
+
+// grape_eval_jvp_multi: the E_t images the exact mode keeps side by side (one per direction of a block of the multi kernel)
+static int jvp_exact_images(const grape_ctx *c)
+{
+    if (c->jvp_ndir < 1 || !c->jvp_multi) return 1;
+    return std::max(1, std::min(c->jvp_ndir, grape::jvp_multi_block(c->cfg.n, c->m)));
+}
+
+// GRAPE_JVP_MULTI=0 / 1 forces trajectory_jvp_kernel per direction / trajectory_jvp_multi_kernel (where an instance serves
+// the launch); otherwise the shapes at which the multi kernel measured faster per direction (grape_kernels.hpp)
+static int jvp_multi_choice(const grape_ctx *c)
+{
+    if (env_off("GRAPE_JVP_MULTI")) return 0;
+    if (env_on("GRAPE_JVP_MULTI")) return 2;                 // (forced: blocks of one direction too)
+    return grape::jvp_multi_default(c->cfg.n, c->m) ? 1 : 0;
 }
 
 // grape_eval_jvp under a pulse map: the caller's direction -> the coordinates of the physical pulse, slope * (xdot phi')
@@ -2686,6 +2714,8 @@ static int jvp_tangent_map(grape_ctx *c, hipStream_t stream)
     grape::DoneSignal d;
     d.basis = &op;
     HIP_TRY(c, grape::launch_copy(c->jvp_xdot_call, c->d_jvp_xphys, (int)KN(c), stream, d));
+    for (int dir = 1; dir < c->jvp_ndir; ++dir)              // grape_eval_jvp_multi: the same map, direction by direction
+        HIP_TRY(c, grape::launch_copy(c->jvp_xdot_call + (size_t)dir * KP(c), c->d_jvp_xphys + (size_t)dir * KN(c), (int)KN(c), stream, d));
     return GRAPE_OK;
 }
 
@@ -3606,10 +3636,14 @@ extern "C" int grape_set_trajectory_derivative(grape_ctx *c, int32_t mode)
 
 // grape_eval_jvp / grape_eval_jvp_device: vjp_check's order with the direction in place of G and the tangents in place of
 // the cotangents
+// (n_dir: grape_eval_jvp_multi's direction count; the single calls pass 1)
 static int jvp_check(grape_ctx *c, const std::string &who, const void *x, bool x_needed, const void *xdot, int32_t n_obs,
-                     int32_t per_member, const void *O, const void *ydot, const void *Xdot_final)
+                     int32_t per_member, const void *O, const void *ydot, const void *Xdot_final, int32_t n_dir = 1)
 {
     if (const char *why = why_linearisation_not_served(c)) return fail(c, GRAPE_ERR_UNSUPPORTED, who + ": " + why);
+    if (n_dir < 1 || n_dir > GRAPE_MAX_JVP_DIRECTIONS)
+        return fail(c, GRAPE_ERR_INVALID_ARG, who + ": n_dir = " + std::to_string(n_dir) + " (must be in 1.." +
+                                              std::to_string(GRAPE_MAX_JVP_DIRECTIONS) + ")");
     if (!x && x_needed) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": x is null");
     if (!xdot) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": xdot is null");
     if (!ydot && !Xdot_final) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": ydot and Xdot_final are both null");
@@ -3913,21 +3947,32 @@ extern "C" int grape_eval_vjp_device(grape_ctx *c, const double *d_x, int32_t n_
 }
 
 // ---- grape_eval_jvp: one evaluation + the push-forward of the caller's direction along its trajectory ------------------------
-extern "C" int grape_eval_jvp(grape_ctx *c, const double *x, const double *xdot, int32_t n_obs, int32_t per_member,
-                              const double *O, double *ydot, double *Xdot_final)
+// the direction count of a grape_eval_jvp_multi call in flight, back to 0 (the single call) on every way out
+struct JvpMultiScope {
+    grape_ctx *c;
+    JvpMultiScope(grape_ctx *c_, int ndir) : c(c_)
+    {
+        c->jvp_ndir = ndir;
+        c->jvp_multi = ndir > 0 ? jvp_multi_choice(c) : 0;
+    }
+    ~JvpMultiScope() { c->jvp_ndir = 0; c->jvp_multi = 0; }
+};
+
+// grape_eval_jvp (multi = false) and grape_eval_jvp_multi (n_dir directions, every array direction-slowest)
+static int eval_jvp_host(grape_ctx *c, const char *who, bool multi, const double *x, int32_t n_dir, const double *xdot, int32_t n_obs,
+                         int32_t per_member, const double *O, double *ydot, double *Xdot_final)
 {
-    DeviceGuard guard;
-    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_jvp: null context");
-    const char *who = "grape_eval_jvp";
     c->traj_valid = false;
-    if (int rc0 = jvp_check(c, who, x, true, xdot, n_obs, per_member, O, ydot, Xdot_final)) return rc0;
+    if (int rc0 = jvp_check(c, who, x, true, xdot, n_obs, per_member, O, ydot, Xdot_final, multi ? n_dir : 1)) return rc0;
+    const size_t nd = multi ? (size_t)n_dir : 1;
     const size_t n = (size_t)c->cfg.n, m = (size_t)c->m, E = (size_t)c->cfg.n_ensemble, N = (size_t)c->cfg.n_slices;
-    const size_t n_O = n * m * (per_member ? E : 1) * (size_t)n_obs, n_y = (N + 1) * (size_t)n_obs * E, n_X = n * m * E;
-    const size_t kn = KN(c), kp = KP(c);
+    const size_t n_O = n * m * (per_member ? E : 1) * (size_t)n_obs, n_y = (N + 1) * (size_t)n_obs * E * nd, n_X = n * m * E * nd;
+    const size_t kn = KN(c) * nd, kp = KP(c) * nd;
     int rc = check_finite(c, O, 2 * n_O, who, "O", 2);
     if (rc) return rc;
     rc = check_finite(c, xdot, kp, who, "xdot");
     if (rc) return rc;
+    JvpMultiScope scope(c, multi ? n_dir : 0);
     // the direction's buffers are the device form's too, and that one does not block: nothing of it is in flight from here on
     rc = drain(c, c);
     if (rc) return rc;
@@ -3947,6 +3992,10 @@ extern "C" int grape_eval_jvp(grape_ctx *c, const double *x, const double *xdot,
     if (rc) return rc;
     if (pulse_map(c)) {
         rc = grow(c, &c->d_jvp_xphys, &c->jvp_xphys_bytes, sizeof(double) * kn, who, "the direction of the physical pulse");
+        if (rc) return rc;
+    }
+    if (multi && traj_exact(c)) {                            // (one E_t image per direction of a block)
+        rc = traj_exact_ensure(c, who, jvp_exact_images(c));
         if (rc) return rc;
     }
     HIP_TRY(c, hipMemcpy(c->d_jvp_xdot, xdot, sizeof(double) * kp, hipMemcpyHostToDevice));
@@ -3970,16 +4019,31 @@ extern "C" int grape_eval_jvp(grape_ctx *c, const double *x, const double *xdot,
     return GRAPE_OK;
 }
 
-extern "C" int grape_eval_jvp_device(grape_ctx *c, const double *d_x, const double *d_xdot, int32_t n_obs, int32_t per_member,
-                                     const double *d_O, double *d_ydot, double *d_Xdot_final, void *stream)
+extern "C" int grape_eval_jvp(grape_ctx *c, const double *x, const double *xdot, int32_t n_obs, int32_t per_member,
+                              const double *O, double *ydot, double *Xdot_final)
 {
     DeviceGuard guard;
-    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_jvp_device: null context");
-    const char *who = "grape_eval_jvp_device";
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_jvp: null context");
+    return eval_jvp_host(c, "grape_eval_jvp", false, x, 0, xdot, n_obs, per_member, O, ydot, Xdot_final);
+}
+
+extern "C" int grape_eval_jvp_multi(grape_ctx *c, const double *x, int32_t n_dir, const double *xdot, int32_t n_obs,
+                                    int32_t per_member, const double *O, double *ydot, double *Xdot_final)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_jvp_multi: null context");
+    return eval_jvp_host(c, "grape_eval_jvp_multi", true, x, n_dir, xdot, n_obs, per_member, O, ydot, Xdot_final);
+}
+
+// grape_eval_jvp_device (multi = false) and grape_eval_jvp_multi_device
+static int eval_jvp_device(grape_ctx *c, const char *who, bool multi, const double *d_x, int32_t n_dir, const double *d_xdot, int32_t n_obs,
+                           int32_t per_member, const double *d_O, double *d_ydot, double *d_Xdot_final, void *stream)
+{
     const bool reuse = d_x == nullptr, was_valid = c->traj_valid;
     c->traj_valid = false;
-    int rc = jvp_check(c, who, d_x, false, d_xdot, n_obs, per_member, d_O, d_ydot, d_Xdot_final);
+    int rc = jvp_check(c, who, d_x, false, d_xdot, n_obs, per_member, d_O, d_ydot, d_Xdot_final, multi ? n_dir : 1);
     if (rc) return rc;
+    JvpMultiScope scope(c, multi ? n_dir : 0);
     if (reuse && chunked(c))
         return fail(c, GRAPE_ERR_NOT_READY, std::string(who) + ": d_x is null (reuse), but the workspace of a context under member_chunk "
                                             "holds one block of members only");
@@ -3990,9 +4054,14 @@ extern "C" int grape_eval_jvp_device(grape_ctx *c, const double *d_x, const doub
     rc = traj_device_prologue(c);
     if (rc) return rc;
     if (pulse_map(c)) {
-        rc = grow(c, &c->d_jvp_xphys, &c->jvp_xphys_bytes, sizeof(double) * KN(c), who, "the direction of the physical pulse");
+        rc = grow(c, &c->d_jvp_xphys, &c->jvp_xphys_bytes, sizeof(double) * KN(c) * (multi ? (size_t)n_dir : 1), who,
+                  "the direction of the physical pulse");
         if (rc) return rc;
         rc = grow(c, &c->d_vjp_out, &c->vjp_out_bytes, sizeof(double) * (KP(c) + 1), who, "the projected row");
+        if (rc) return rc;
+    }
+    if (multi && traj_exact(c)) {                            // (one E_t image per direction of a block)
+        rc = traj_exact_ensure(c, who, jvp_exact_images(c));
         if (rc) return rc;
     }
     const bool want_y = d_ydot != nullptr && n_obs > 0;
@@ -4012,7 +4081,7 @@ extern "C" int grape_eval_jvp_device(grape_ctx *c, const double *d_x, const doub
     } else {
         // the propagators (and the slope array) of the last device form are in place: the tangent map and the push-forward alone
         if (traj_exact(c)) {                                 // (the pulse is in place; the blocks, after a read-out alone)
-            rc = traj_exact_ensure(c, who);
+            rc = traj_exact_ensure(c, who, jvp_exact_images(c));
             if (rc) return rc;
         }
         KernelLogScope log_scope(&c->kernel_log);
@@ -4030,6 +4099,24 @@ extern "C" int grape_eval_jvp_device(grape_ctx *c, const double *d_x, const doub
     c->dev_pending = true;
     c->traj_valid = !chunked(c);
     return GRAPE_OK;
+}
+
+extern "C" int grape_eval_jvp_device(grape_ctx *c, const double *d_x, const double *d_xdot, int32_t n_obs, int32_t per_member,
+                                     const double *d_O, double *d_ydot, double *d_Xdot_final, void *stream)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_jvp_device: null context");
+    return eval_jvp_device(c, "grape_eval_jvp_device", false, d_x, 0, d_xdot, n_obs, per_member, d_O, d_ydot, d_Xdot_final, stream);
+}
+
+extern "C" int grape_eval_jvp_multi_device(grape_ctx *c, const double *d_x, int32_t n_dir, const double *d_xdot, int32_t n_obs,
+                                           int32_t per_member, const double *d_O, double *d_ydot, double *d_Xdot_final,
+                                           void *stream)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_jvp_multi_device: null context");
+    return eval_jvp_device(c, "grape_eval_jvp_multi_device", true, d_x, n_dir, d_xdot, n_obs, per_member, d_O, d_ydot, d_Xdot_final,
+                           stream);
 }
 
 // ---- ABI v8: the figure of merit without the gradient ----------------------------------------------------------------------

@@ -234,7 +234,30 @@ struct SweepParams {
     // (Appended: the offsets of every field above stay what they were.)
     int32_t rc_exact;
     int32_t rc_unweighted;
+    // grape_eval_jvp_multi (jvp.hip): a jvp_only launch with jvp_ndir > 0 pushes jvp_ndir directions forward.  Direction d
+    // reads jvp_xdot + d jvp_dir_xdot and writes jvp_ydot + d jvp_dir_ydot / jvp_xf + d jvp_dir_xf (elements of the arrays'
+    // own types); in the exact mode its E_t image lies at traj_w + d jvp_dir_w, and traj_w holds
+    // min(jvp_ndir, jvp_multi_block(n, m)) images.  jvp_multi != 0: trajectory_jvp_multi_kernel in blocks of
+    // jvp_multi_block(n, m) directions where an instance serves the launch, else (and with 0) trajectory_jvp_kernel once per
+    // direction -- the same bits either way; 1 leaves a block of ONE direction to the single kernel where that measured faster,
+    // 2 (GRAPE_JVP_MULTI=1) forces the multi kernel for every block.  jvp_ndir = 0: the single call, which reads none of these.
+    // (Appended.)
+    int32_t jvp_ndir;
+    int32_t jvp_multi;
+    int64_t jvp_dir_xdot, jvp_dir_ydot, jvp_dir_xf, jvp_dir_w;
 };
+// grape_eval_jvp_multi: the directions trajectory_jvp_multi_kernel<n, m> carries per launch (DB; chosen per shape from the
+// register file), its workgroup size limit (all n: 512 registers per lane), and whether the shape
+// dispatches to it by default (where it measured faster per direction than the single kernel; GRAPE_JVP_MULTI=0/1 forces)
+constexpr int kJvpMultiMaxThreads = 256;
+constexpr int jvp_multi_block(int n, int m)
+{
+    return n == 2 ? 8 : n == 3 ? 4 : n == 4 ? (m <= 2 ? 3 : 2) : 0;
+}
+constexpr bool jvp_multi_default(int n, int m)
+{
+    return jvp_multi_block(n, m) > 0;
+}
 // static LDS of observe_kernel (vjp = false) / trajectory_vjp_kernel (vjp = true) at operator dimension n with m state
 // columns: the scans' wave totals.  What the host layer subtracts from the device's LDS per workgroup to get the staged
 // instances' budget (the launchers check the sum against the kernel's own attributes).

@@ -29,6 +29,12 @@
 //
 // The ydot stores are observe_kernel's direct ones (lane c stores at s = c S + jj: neighbouring lanes S 16 B apart in a probe
 // row); there is no staged instance.
+//
+// grape_eval_jvp_multi: trajectory_jvp_multi_kernel<N, M, MAXT, DB, EXACT> carries DB tangents through the same four steps next
+// to ONE chunk product, ONE scan of Q and ONE state walk -- R once and Rdot per direction in step 1, the affine scan with one
+// matrix part and an offset per direction, X once and D per direction in step 4 -- so the propagators are read once per pass
+// for the block.  Per direction the operations and their order are this kernel's: block d holds the single call's bits.  It is
+// bound to 256 threads for every n (one wave per SIMD, 512 registers per lane); DB per (n, m) is jvp_multi_block.
 #include "cmat.hpp"
 #include "grape_kernels.hpp"
 #include "rc_mat.hpp"
@@ -336,6 +342,291 @@ __global__ __launch_bounds__(MAXT) void trajectory_jvp_kernel(const double2 *__r
     }
 }
 
+// ---- several directions per call (grape_eval_jvp_multi) -----------------------------------------------------------------------
+// trajectory_jvp_multi_kernel carries up to DB tangents next to ONE state walk: the propagators, the chunk products, the
+// prefix scan of Q and the walk of X are the block's, the tangents are each direction's.  Per direction every operation and
+// its order is trajectory_jvp_kernel's (the same inlined products, V_t built from zero in the registers P has left, one
+// direction after the other), so block d of the result is bit for bit the single kernel's for direction d alone.  nd <= DB
+// directions are live in a launch (the ragged last block); nd is uniform over the grid, so the guards are scalar branches.
+
+// one slice for the block:  X <- P X,  D_d <- P D_d + V_d X  (direction d's xdot row at xd + d xs)
+template <int N, int C, int DB>
+GRAPE_DEV void jvp_step_multi(CRect<N, C> &X, CRect<N, C> (&D)[DB], int nd, const double2 *__restrict__ Pt, size_t stride,
+                              const double *__restrict__ xd, size_t xs, const double2 *__restrict__ opB, int K)
+{
+    CMat<N> P;
+    rc_load_mat(P, Pt, stride);
+    rmul_inplace(X, P);
+#pragma unroll
+    for (int d = 0; d < DB; ++d)
+        if (d < nd)
+            rmul_inplace(D[d], P);
+#pragma unroll
+    for (int d = 0; d < DB; ++d) {
+        if (d < nd) {
+            const double *__restrict__ xdd = xd + (size_t)d * xs;
+#pragma unroll
+            for (int e = 0; e < N * N; ++e) {
+                P.re[e] = 0.0;
+                P.im[e] = 0.0;
+            }
+#pragma unroll 1
+            for (int c = 0; c < K; ++c) {
+                const double a = xdd[c];
+#pragma unroll
+                for (int e = 0; e < N * N; ++e) {
+                    const double2 b = opB[c * N * N + e];
+                    P.re[e] = fma(a, b.x, P.re[e]);
+                    P.im[e] = fma(a, b.y, P.im[e]);
+                }
+            }
+            rmul_acc(D[d], P, X);
+        }
+    }
+}
+
+// the exact derivative mode:  D_d <- P D_d + E_d X  with X the state BEFORE the slice, then X <- P X  (E_d: image d of traj_w)
+template <int N, int C, int DB>
+GRAPE_DEV void jvp_step_multi_exact(CRect<N, C> &X, CRect<N, C> (&D)[DB], int nd, const double2 *__restrict__ Pt,
+                                    const double2 *__restrict__ Et, size_t ws, size_t stride)
+{
+    CMat<N> P;
+    rc_load_mat(P, Pt, stride);
+#pragma unroll
+    for (int d = 0; d < DB; ++d)
+        if (d < nd)
+            rmul_inplace(D[d], P);
+#pragma unroll
+    for (int d = 0; d < DB; ++d) {
+        if (d < nd) {
+            rc_load_mat(P, Et + (size_t)d * ws, stride);
+            rmul_acc(D[d], P, X);
+        }
+    }
+    rc_load_mat(P, Pt, stride);
+    rmul_inplace(X, P);
+}
+
+template <int N, int M, int MAXT, int DB, bool EXACT = false>
+__global__ __launch_bounds__(MAXT) void trajectory_jvp_multi_kernel(const double2 *__restrict__ ops_all,
+                                                                    const double2 *__restrict__ o_all,
+                                                                    const double *__restrict__ xdot, const SweepParams p)
+{
+    constexpr int NN = N * N, NM = N * M, MAXW = MAXT / 64;
+    __shared__ double2 s_q[MAXW][NN];              // wave totals: prefix products, then the affine maps' matrices ...
+    __shared__ double2 s_v[MAXW][DB][NM];          // ... and their offsets, one per direction
+
+    const int CH = p.jvp_CH, S = p.S, K = p.K, Nsl = p.N, n_obs = p.jvp_ydot ? p.jvp_n : 0;
+    const int nd = p.jvp_ndir;                       // live directions of this launch, 1..DB
+    const size_t xs = (size_t)p.jvp_dir_xdot, ys = (size_t)p.jvp_dir_ydot, fs = (size_t)p.jvp_dir_xf, ws = (size_t)p.jvp_dir_w;
+    const int L = threadIdx.x, lane = L & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(L >> 6), W = blockDim.x >> 6;
+    const int k = blockIdx.x;
+    const int kg = k + p.jvp_E0;
+    const int lo = (L < CH && L * S < Nsl) ? L * S : Nsl;
+    const int hi = min(lo + S, Nsl);
+    const int cnt = hi - lo;
+    const size_t stride = (size_t)CH;
+    const double2 *__restrict__ Pw = p.props + (size_t)k * S * NN * stride + L;
+    const double2 *__restrict__ ops = ops_all + (size_t)k * (K + 3) * NN;
+    const double2 *__restrict__ opB = ops + NN;
+    const double2 *__restrict__ opXi = ops + (size_t)(1 + K) * NN;
+    const size_t o_step = p.jvp_per_member ? (size_t)p.jvp_Etot * NM : (size_t)NM;
+    const double2 *__restrict__ o_mem = o_all + (p.jvp_per_member ? (size_t)kg * NM : (size_t)0);
+    const size_t y_step = (size_t)Nsl + 1;
+    double2 *__restrict__ yk = p.jvp_ydot ? p.jvp_ydot + (size_t)kg * p.jvp_n * y_step : nullptr;
+    const double *__restrict__ xd = xdot + (size_t)lo * K;        // direction 0 (never read by a lane without a slice)
+    const double2 *__restrict__ Ew = EXACT ? p.traj_w + (size_t)k * S * NN * stride + L : nullptr;
+
+    // ---------------------------------------------------------------- 1: chunk product, and its tangent per direction
+    CMat<N> Q, T;
+    CRect<N, N> Rdot[DB];
+    {
+        CRect<N, N> R;
+#pragma unroll
+        for (int e = 0; e < NN; ++e) {
+            R.re[e] = ((e % N) == (e / N)) ? 1.0 : 0.0;
+            R.im[e] = 0.0;
+        }
+#pragma unroll
+        for (int d = 0; d < DB; ++d)
+            rzero(Rdot[d]);
+#pragma unroll 1
+        for (int jj = 0; jj < cnt; ++jj) {
+            if constexpr (EXACT)
+                jvp_step_multi_exact(R, Rdot, nd, Pw + (size_t)jj * NN * stride, Ew + (size_t)jj * NN * stride, ws, stride);
+            else
+                jvp_step_multi(R, Rdot, nd, Pw + (size_t)jj * NN * stride, stride, xd + (size_t)jj * K, xs, opB, K);
+        }
+#pragma unroll
+        for (int e = 0; e < NN; ++e) {
+            Q.re[e] = R.re[e];
+            Q.im[e] = R.im[e];
+        }
+    }
+    // ---------------------------------------------------------------- 2: exclusive prefix over lanes -> X at the chunk start, d_c
+    CRect<N, M> Xlo, dvec[DB];
+    {
+        CMat<N> inc = Q, oth;
+        for (int d = 1; d < 64; d <<= 1) {
+            shfl_up(oth, inc, d);
+            if (lane >= d) {
+                mul(T, inc, oth);
+                inc = T;
+            }
+        }
+        shfl_up(oth, inc, 1);
+        if (lane == 0)
+            set_identity(oth);
+        if (W > 1) {
+            if (lane == 63) {
+#pragma unroll
+                for (int e = 0; e < NN; ++e)
+                    s_q[wave][e] = make_double2(inc.re[e], inc.im[e]);
+            }
+            __syncthreads();
+            CMat<N> pre;
+            set_identity(pre);
+            for (int w = 0; w < wave; ++w) {
+                rc_load_lds(inc, &s_q[w][0]);
+                mul(T, inc, pre);
+                pre = T;
+            }
+            mul(T, oth, pre);
+            oth = T;
+        }
+        CRect<N, M> xi;
+        rload_uniform(xi, opXi);
+        rmul(Xlo, oth, xi);
+#pragma unroll
+        for (int d = 0; d < DB; ++d) {
+            if (d < nd) {
+                CMat<N> Rd;
+#pragma unroll
+                for (int e = 0; e < NN; ++e) {
+                    Rd.re[e] = Rdot[d].re[e];
+                    Rd.im[e] = Rdot[d].im[e];
+                }
+                rmul(dvec[d], Rd, Xlo);
+            } else {
+                rzero(dvec[d]);
+            }
+        }
+    }
+    // ---------------------------------------------------------------- 3: exclusive prefix scan of (Q, d_0 .. d_nd-1)
+    CRect<N, M> Din[DB];
+    {
+        CMat<N> G = Q, Go;
+        CRect<N, M> vo, Tm;
+        for (int s = 1; s < 64; s <<= 1) {           // the offsets first, each with the old G, then G itself
+#pragma unroll
+            for (int d = 0; d < DB; ++d) {
+                if (d < nd) {
+                    rshfl_up(vo, dvec[d], s);
+                    if (lane >= s)
+                        rmul_acc(dvec[d], G, vo);
+                }
+            }
+            shfl_up(Go, G, s);
+            if (lane >= s) {
+                mul(T, G, Go);
+                G = T;
+            }
+        }
+        shfl_up(Go, G, 1);                           // the lanes in front of this one, inside the wave
+        if (lane == 0)
+            set_identity(Go);
+        if (W > 1) {
+            __syncthreads();                         // (the readers of the prefix totals in s_q are done)
+            if (lane == 63) {
+#pragma unroll
+                for (int e = 0; e < NN; ++e)
+                    s_q[wave][e] = make_double2(G.re[e], G.im[e]);
+#pragma unroll
+                for (int d = 0; d < DB; ++d)
+                    if (d < nd) {
+#pragma unroll
+                        for (int e = 0; e < NM; ++e)
+                            s_v[wave][d][e] = make_double2(dvec[d].re[e], dvec[d].im[e]);
+                    }
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int d = 0; d < DB; ++d) {
+            if (d < nd) {
+                rshfl_up(vo, dvec[d], 1);
+                if (lane == 0)
+                    rzero(vo);
+                if (W > 1) {
+                    CRect<N, M> z;
+                    rzero(z);
+                    for (int w = 0; w < wave; ++w) { // what enters this wave on the left, first wave first
+                        rc_load_lds(G, &s_q[w][0]);
+                        rmul(Tm, G, z);
+#pragma unroll
+                        for (int e = 0; e < NM; ++e) {
+                            const double2 vv = s_v[w][d][e];
+                            z.re[e] = Tm.re[e] + vv.x;
+                            z.im[e] = Tm.im[e] + vv.y;
+                        }
+                    }
+                    rmul(Tm, Go, z);
+#pragma unroll
+                    for (int e = 0; e < NM; ++e) {
+                        Din[d].re[e] = Tm.re[e] + vo.re[e];
+                        Din[d].im[e] = Tm.im[e] + vo.im[e];
+                    }
+                } else {
+                    Din[d] = vo;
+                }
+            } else {
+                rzero(Din[d]);
+            }
+        }
+    }
+    // ---------------------------------------------------------------- 4: the true tangents, the traces
+    if (yk && L == 0) {                              // row 0: D_0 = 0
+        for (int d = 0; d < nd; ++d)
+            for (int j = 0; j < n_obs; ++j)
+                yk[(size_t)d * ys + (size_t)j * y_step] = make_double2(0.0, 0.0);
+    }
+#pragma unroll 1
+    for (int jj = 0; jj < cnt; ++jj) {
+        const int t = lo + jj;
+        if constexpr (EXACT)
+            jvp_step_multi_exact(Xlo, Din, nd, Pw + (size_t)jj * NN * stride, Ew + (size_t)jj * NN * stride, ws, stride);
+        else
+            jvp_step_multi(Xlo, Din, nd, Pw + (size_t)jj * NN * stride, stride, xd + (size_t)jj * K, xs, opB, K);
+#pragma unroll
+        for (int d = 0; d < DB; ++d) {
+            if (d < nd) {
+                double2 *__restrict__ yd = yk + (size_t)d * ys;
+#pragma unroll 1
+                for (int j = 0; j < n_obs; ++j) {    // ydot_j = tr(O_j' D_d), one probe at a time
+                    const double2 *__restrict__ o = o_mem + (size_t)j * o_step;
+                    double yr = 0.0, yi = 0.0;
+#pragma unroll
+                    for (int e = 0; e < NM; ++e) {
+                        const double2 v = o[e];
+                        yr = fma(v.x, Din[d].re[e], yr);
+                        yr = fma(v.y, Din[d].im[e], yr);
+                        yi = fma(v.x, Din[d].im[e], yi);
+                        yi = fma(-v.y, Din[d].re[e], yi);
+                    }
+                    yd[(size_t)(t + 1) + (size_t)j * y_step] = make_double2(yr, yi);
+                }
+                if (p.jvp_xf && t + 1 == Nsl) {
+                    double2 *__restrict__ xf = p.jvp_xf + (size_t)d * fs + (size_t)kg * NM;
+#pragma unroll
+                    for (int e = 0; e < NM; ++e)
+                        xf[e] = make_double2(Din[d].re[e], Din[d].im[e]);
+                }
+            }
+        }
+    }
+}
+
 template <int N, int M>
 static hipError_t jvp_launch_nm(const SweepParams &p, hipStream_t stream)
 {
@@ -361,8 +652,89 @@ static hipError_t jvp_launch_nm(const SweepParams &p, hipStream_t stream)
     return hipGetLastError();
 }
 
+// direction d0 of a multi-direction launch as a launch of its own (nd directions from there on)
+static SweepParams jvp_direction(const SweepParams &p, int d0, int nd)
+{
+    SweepParams q = p;
+    q.jvp_ndir = nd;
+    q.jvp_xdot = p.jvp_xdot + (size_t)d0 * p.jvp_dir_xdot;
+    if (p.jvp_ydot) q.jvp_ydot = p.jvp_ydot + (size_t)d0 * p.jvp_dir_ydot;
+    if (p.jvp_xf) q.jvp_xf = p.jvp_xf + (size_t)d0 * p.jvp_dir_xf;
+    return q;
+}
+
+// grape_eval_jvp_multi: p.jvp_ndir directions in blocks of DB through trajectory_jvp_multi_kernel, or (no instance for this
+// launch, or not asked for) one behind the other through trajectory_jvp_kernel -- the same bits either way
+template <int N, int M>
+static hipError_t jvp_launch_multi_nm(const SweepParams &p, hipStream_t stream)
+{
+    constexpr int DB = jvp_multi_block(N, M), MAXT = kJvpMultiMaxThreads;
+    const int threads = (p.jvp_CH + 63) & ~63, ndir = p.jvp_ndir;
+    if (ndir < 1 || ndir > 64 || p.jvp_dir_xdot < 0 || p.jvp_dir_ydot < 0 || p.jvp_dir_xf < 0 || p.jvp_dir_w < 0 || !p.jvp_xdot)
+        return hipErrorInvalidConfiguration;
+    if (!p.jvp_multi || threads > MAXT) {
+        for (int d = 0; d < ndir; ++d) {
+            const hipError_t e = jvp_launch_nm<N, M>(jvp_direction(p, d, 0), stream);
+            if (e != hipSuccess)
+                return e;
+        }
+        return hipSuccess;
+    }
+    if (threads > RcTraits<N>::MAXT || p.jvp_CH < 1 || (long long)p.S * p.jvp_CH < p.N || p.N < 1 || p.E < 1 || p.K < 1 || p.jvp_E0 < 0 ||
+        p.jvp_E0 + p.E > p.jvp_Etot || p.jvp_n < 0 || p.jvp_n > 16 || (!p.jvp_ydot && !p.jvp_xf) ||
+        (p.jvp_ydot && (p.jvp_n < 1 || !p.jvp_O)) || !p.props || !p.ops || (long long)p.K * p.N > 0x7fffff00ll)
+        return hipErrorInvalidConfiguration;
+    if (p.traj_exact && (!p.traj_w || !p.traj_x))
+        return hipErrorInvalidConfiguration;
+    // a block of ONE direction (n_dir = 1, or the ragged remainder) measured slower through the multi kernel than through the
+    // single one, but for n = 4 in the exact mode: it takes the single kernel unless the multi kernel is forced (jvp_multi = 2)
+    const bool lone_single = p.jvp_multi == 1 && !(N == 4 && p.traj_exact);
+    for (int d0 = 0; d0 < ndir; d0 += DB) {
+        const SweepParams q = jvp_direction(p, d0, ndir - d0 < DB ? ndir - d0 : DB);
+        if (q.jvp_ndir == 1 && lone_single) {
+            const hipError_t e = jvp_launch_nm<N, M>(jvp_direction(q, 0, 0), stream);
+            if (e != hipSuccess)
+                return e;
+            continue;
+        }
+        if (p.traj_exact) {
+            // E_t = DF_t[V_t] of every direction of the block into its own image of traj_w, then the instance that consumes them
+            for (int d = 0; d < q.jvp_ndir; ++d) {
+                SweepParams r = jvp_direction(q, d, 0);
+                r.traj_w = q.traj_w + (size_t)d * q.jvp_dir_w;
+                const hipError_t e = run_traj_frechet(N, true, r, stream);
+                if (e != hipSuccess)
+                    return e;
+            }
+            GRAPE_LAUNCH_AS("trajectory_jvp_multi_exact_kernel", (trajectory_jvp_multi_kernel<N, M, MAXT, DB, true>), dim3(q.E),
+                            dim3(threads), 0, stream, q.ops, q.jvp_O, q.jvp_xdot, q);
+        } else {
+            GRAPE_LAUNCH_AS("trajectory_jvp_multi_kernel", (trajectory_jvp_multi_kernel<N, M, MAXT, DB>), dim3(q.E), dim3(threads), 0,
+                            stream, q.ops, q.jvp_O, q.jvp_xdot, q);
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
+}
+
 hipError_t run_trajectory_jvp(int n, const SweepParams &p, hipStream_t stream)
 {
+    if (p.jvp_ndir > 0) {
+        switch (n * 8 + p.jvp_m) {
+        case 2 * 8 + 1: return jvp_launch_multi_nm<2, 1>(p, stream);
+        case 2 * 8 + 2: return jvp_launch_multi_nm<2, 2>(p, stream);
+        case 3 * 8 + 1: return jvp_launch_multi_nm<3, 1>(p, stream);
+        case 3 * 8 + 2: return jvp_launch_multi_nm<3, 2>(p, stream);
+        case 3 * 8 + 3: return jvp_launch_multi_nm<3, 3>(p, stream);
+        case 4 * 8 + 1: return jvp_launch_multi_nm<4, 1>(p, stream);
+        case 4 * 8 + 2: return jvp_launch_multi_nm<4, 2>(p, stream);
+        case 4 * 8 + 3: return jvp_launch_multi_nm<4, 3>(p, stream);
+        case 4 * 8 + 4: return jvp_launch_multi_nm<4, 4>(p, stream);
+        default: return hipErrorInvalidValue;
+        }
+    }
     switch (n * 8 + p.jvp_m) {
     case 2 * 8 + 1: return jvp_launch_nm<2, 1>(p, stream);
     case 2 * 8 + 2: return jvp_launch_nm<2, 2>(p, stream);

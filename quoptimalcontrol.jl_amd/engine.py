@@ -28,6 +28,7 @@ FLAG_FORCE_COLLECTIVE = 32
 FLAG_TIME_SAMPLED = 64
 FLAG_GROUP_PEER_SUM = 128
 MAX_DEVICES = 8
+MAX_JVP_DIRECTIONS = 8                                     # GRAPE_MAX_JVP_DIRECTIONS
 ABI_VERSION = 8
 
 STATUS = {0: "GRAPE_OK", -1: "GRAPE_ERR_INVALID_ARG", -2: "GRAPE_ERR_UNSUPPORTED",
@@ -43,6 +44,7 @@ EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_oper
            "grape_comm_unique_id", "grape_comm_attach", "grape_ipc_export", "grape_ipc_attach",
            "grape_eval", "grape_eval_device", "grape_eval_batch", "grape_eval_batch_device", "grape_eval_fom", "grape_eval_observables",
            "grape_eval_vjp", "grape_eval_observables_device", "grape_eval_vjp_device", "grape_eval_jvp", "grape_eval_jvp_device",
+           "grape_eval_jvp_multi", "grape_eval_jvp_multi_device",
            "grape_set_trajectory_derivative", "grape_set_running_cost_derivative",
            "grape_lbfgs", "grape_lbfgs_get_trace",
            "grape_get_member_results", "grape_get_trajectory",
@@ -149,6 +151,8 @@ def load_library():
     L.grape_eval_vjp_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.grape_eval_jvp.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
     L.grape_eval_jvp_device.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    L.grape_eval_jvp_multi.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp]
+    L.grape_eval_jvp_multi_device.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
     L.grape_set_trajectory_derivative.argtypes = [vp, i32]
     L.grape_set_running_cost_derivative.argtypes = [vp, i32]
     L.grape_lbfgs.argtypes = [vp, vp, C.POINTER(GrapeLbfgsOptions), vp, C.POINTER(GrapeLbfgsResult)]
@@ -177,6 +181,29 @@ def _cm(M):
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def jacobian_columns(size, columns=None):
+    """The flat indices of x (row-major over (K, cols)) whose Jacobian columns trajectory_jacobian returns, in the caller's
+    order: all `size` of them for None; negative indices count from the end; out of range or repeated ones are refused."""
+    if columns is None:
+        return list(range(int(size)))
+    out = []
+    for c in columns:
+        i = int(c)
+        if i != c or not -size <= i < size:
+            raise ValueError(f"trajectory_jacobian: column {c!r} is not an index into the {size} entries of x")
+        out.append(i % size)
+    if len(set(out)) != len(out):
+        raise ValueError("trajectory_jacobian: a column is listed twice")
+    if not out:
+        raise ValueError("trajectory_jacobian: no column is listed")
+    return out
+
+
+def jacobian_blocks(columns, block=MAX_JVP_DIRECTIONS):
+    """`columns` in consecutive blocks of at most `block`: the directions of one grape_eval_jvp_multi_device call each."""
+    return [list(columns[i:i + block]) for i in range(0, len(columns), block)]
 
 
 class _CountingLib:
@@ -739,6 +766,135 @@ class GrapeEngine:
         self._check(self._lib.grape_eval_jvp_device(self._h, C.c_void_p(d_x), C.c_void_p(d_xdot), n_obs, 1 if per_member else 0,
                                                     C.c_void_p(d_O), C.c_void_p(d_ydot), C.c_void_p(d_Xdot_final),
                                                     C.c_void_p(stream)))
+
+    def _jvp_probes(self, who, ops, per_member):
+        """(n_obs, O as (n_obs, n, m) / (E, n_obs, n, m) complex128) of the jvp forms; ops=None: (0, None)"""
+        if ops is None:
+            return 0, None
+        n, m, E = self.n, self.m, self.E
+        O = np.asarray(ops, dtype=np.complex128)
+        if not per_member and O.ndim == 2:
+            O = O[None]
+        want = (E, O.shape[1] if O.ndim == 4 else 0, n, m) if per_member else (O.shape[0] if O.ndim == 3 else 0, n, m)
+        if O.shape != want or not 1 <= O.shape[-3] <= 16:
+            raise ValueError(f"{who}: ops must be {'(E, n_obs, n, m)' if per_member else '(n_obs, n, m)'} with "
+                             f"E = {E}, n = {n}, m = {m} and 1 <= n_obs <= 16")
+        return O.shape[-3], O
+
+    def observe_jvp_multi(self, x, xdots, ops, per_member=False, final=False):
+        """grape_eval_jvp_multi: observe_jvp for several directions behind ONE evaluation of x.  xdots (n_dir, K, cols), every
+        direction of x's shape and coordinates.  Returns ydot (n_dir, E, n_obs, N+1) -- then Xdot_final (n_dir, E, n, m) with
+        final=True; block d is bit for bit observe_jvp(x, xdots[d], ...).  More than MAX_JVP_DIRECTIONS = 8 directions are
+        walked in blocks of 8 (one evaluation each)."""
+        x = np.asarray(x, dtype=np.float64)
+        xd = np.asarray(xdots, dtype=np.float64)
+        if x.shape != (self.K, self._cols):
+            raise ValueError(f"x must be ({self.K},{self._cols})")
+        if xd.ndim != 3 or xd.shape[1:] != x.shape or xd.shape[0] < 1:
+            raise ValueError(f"observe_jvp_multi: xdots must be (n_dir, {self.K}, {self._cols}) with n_dir >= 1")
+        if ops is None and not final:
+            raise ValueError("observe_jvp_multi: nothing asked for (ops=None needs final=True)")
+        n, m, E, N = self.n, self.m, self.E, self.N
+        n_obs, O = self._jvp_probes("observe_jvp_multi", ops, per_member)
+        Of = None if O is None else _cm(np.swapaxes(O, 0, 1) if per_member else O)
+        n_dir = xd.shape[0]
+        yd = np.empty((n_dir, E, n_obs, N + 1), np.complex128) if n_obs else None
+        Xf = np.empty((n_dir, E, m, n), np.complex128) if final else None
+        xf = np.ascontiguousarray(x.T)
+        for d0 in range(0, n_dir, MAX_JVP_DIRECTIONS):
+            d1 = min(n_dir, d0 + MAX_JVP_DIRECTIONS)
+            xdf = np.ascontiguousarray(np.swapaxes(xd[d0:d1], 1, 2))
+            yb = None if yd is None else yd[d0:d1]
+            Xb = None if Xf is None else Xf[d0:d1]
+            self._check(self._lib.grape_eval_jvp_multi(self._h, _p(xf), d1 - d0, _p(xdf), n_obs, 1 if per_member else 0, _p(Of),
+                                                       _p(yb), _p(Xb)))
+        if final:
+            return yd, np.ascontiguousarray(np.swapaxes(Xf, -1, -2))
+        return yd
+
+    def observe_jvp_multi_device(self, x, xdots, ops, per_member=False, final=False, stream=0):
+        """grape_eval_jvp_multi_device on CUDA tensors of the context's GPU: x float64 (K, cols), or None for reuse -- along the
+        trajectory the last device form left in the workspace, without a sweep (GrapeError NOT_READY when anything else has
+        touched the context since, or under a member chunk); xdots float64 (n_dir, K, cols); ops complex128 as in observe_jvp
+        (None with final=True).  Returns CUDA tensors ydot (n_dir, E, n_obs, N+1) -- then Xdot_final (n_dir, E, n, m) with
+        final=True -- written asynchronously on `stream` (0: the default stream; the layout copies of the inputs run on torch's
+        current stream, which must be the same or ordered in front of it).  More than 8 directions are walked in blocks of 8,
+        the blocks behind the first one by reuse.  Non-finite device entries are not checked."""
+        import torch
+
+        K, cols, n, m, E, N = self.K, self._cols, self.n, self.m, self.E, self.N
+        if x is not None and (not x.is_cuda or x.dtype != torch.float64 or tuple(x.shape) != (K, cols)):
+            raise ValueError(f"observe_jvp_multi_device: x must be a CUDA float64 tensor ({K},{cols}) or None")
+        if not xdots.is_cuda or xdots.dtype != torch.float64 or xdots.dim() != 3 or tuple(xdots.shape[1:]) != (K, cols) \
+                or xdots.shape[0] < 1:
+            raise ValueError(f"observe_jvp_multi_device: xdots must be a CUDA float64 tensor (n_dir, {K}, {cols}) with n_dir >= 1")
+        if ops is None and not final:
+            raise ValueError("observe_jvp_multi_device: nothing asked for (ops=None needs final=True)")
+        n_obs, d_O = 0, None
+        if ops is not None:
+            if not ops.is_cuda or ops.dtype != torch.complex128:
+                raise ValueError("observe_jvp_multi_device: ops must be a CUDA complex128 tensor")
+            O = ops[None] if (not per_member and ops.dim() == 2) else ops
+            want = (E, O.shape[1] if O.dim() == 4 else 0, n, m) if per_member else (O.shape[0] if O.dim() == 3 else 0, n, m)
+            if tuple(O.shape) != want or not 1 <= O.shape[-3] <= 16:
+                raise ValueError(f"observe_jvp_multi_device: ops must be {'(E, n_obs, n, m)' if per_member else '(n_obs, n, m)'} "
+                                 f"with E = {E}, n = {n}, m = {m} and 1 <= n_obs <= 16")
+            n_obs = O.shape[-3]
+            # column-major (n, m, [E,] n_obs): the probe index slowest, then the member
+            d_O = (O.transpose(0, 1) if per_member else O).transpose(-1, -2).contiguous()
+        dev = xdots.device
+        n_dir = xdots.shape[0]
+        d_x = None if x is None else x.t().contiguous()
+        d_xd = xdots.transpose(1, 2).contiguous()
+        yd = torch.empty((n_dir, E, n_obs, N + 1), dtype=torch.complex128, device=dev) if n_obs else None
+        Xf = torch.empty((n_dir, E, m, n), dtype=torch.complex128, device=dev) if final else None
+        reuse_ok = n_dir <= MAX_JVP_DIRECTIONS or self._jacobian_reuse()      # (a member chunk: every block carries x)
+        for d0 in range(0, n_dir, MAX_JVP_DIRECTIONS):
+            d1 = min(n_dir, d0 + MAX_JVP_DIRECTIONS)
+            ptr = lambda t: C.c_void_p(0 if t is None else t[d0:d1].data_ptr())
+            first = d_x is not None and (d0 == 0 or not reuse_ok)
+            self._check(self._lib.grape_eval_jvp_multi_device(self._h, C.c_void_p(d_x.data_ptr() if first else 0), d1 - d0,
+                                                              ptr(d_xd), n_obs, 1 if per_member else 0,
+                                                              C.c_void_p(0 if d_O is None else d_O.data_ptr()), ptr(yd), ptr(Xf),
+                                                              C.c_void_p(stream)))
+        self._jvp_multi_keep = (d_x, d_xd, d_O)              # (alive until the stream has passed the call)
+        if final:
+            return yd, Xf.transpose(-1, -2).contiguous()
+        return yd
+
+    def trajectory_jacobian(self, x, ops, columns=None, per_member=False):
+        """dy/dx of observe(x, ops) for the listed flat indices of x (row-major over (K, cols); all by default): an array
+        (len(columns), E, n_obs, N+1) whose entry j is d y / d x.flat[columns[j]], built from unit directions in blocks of 8
+        through the device form -- the first block carries x, the rest reuse its trajectory (member-chunked contexts: every
+        block carries x).  In the derivative mode of set_trajectory_derivative."""
+        x = np.asarray(x, dtype=np.float64)
+        if x.shape != (self.K, self._cols):
+            raise ValueError(f"x must be ({self.K},{self._cols})")
+        cols = jacobian_columns(x.size, columns)
+        reuse_ok = self._jacobian_reuse()
+        out = []
+        for b, block in enumerate(jacobian_blocks(cols, MAX_JVP_DIRECTIONS)):
+            dirs = np.zeros((len(block), x.size))
+            dirs[np.arange(len(block)), block] = 1.0
+            out.append(self._jacobian_block(x, b == 0 or not reuse_ok, dirs.reshape((len(block),) + x.shape), ops, per_member))
+        return np.concatenate(out, axis=0)
+
+    def _jacobian_reuse(self):
+        """the blocks behind the first may reuse its trajectory: not under a member chunk"""
+        return self.info["member_chunk"] >= self.E
+
+    def _jacobian_block(self, x, carry_x, dirs, ops, per_member):
+        """one block of trajectory_jacobian through the device form: ydot (len(dirs), E, n_obs, N+1) as a NumPy array"""
+        import torch
+
+        dev = torch.device("cuda", self.info["device"])
+        state = getattr(self, "_jacobian_dev", None)
+        if carry_x or state is None:                         # (x and the probes go up once per walk)
+            state = self._jacobian_dev = (torch.as_tensor(x, device=dev), torch.as_tensor(np.asarray(ops, np.complex128), device=dev))
+        yd = self.observe_jvp_multi_device(state[0] if carry_x else None, torch.as_tensor(dirs, device=dev), state[1],
+                                           per_member=per_member)
+        torch.cuda.synchronize(dev)
+        return yd.cpu().numpy()
 
     @staticmethod
     def _traj_device_args(who, d_x, n_obs, d_O, d_a, d_b, names):
