@@ -197,7 +197,9 @@ typedef struct grape_info {
                                       GRAPE_MAX_WORKSPACE_BYTES): an evaluation then walks the ensemble in blocks of this
                                       many members (src/solve.jl:166-187 is a serial loop with no such limit) -- same
                                       results bit for bit; grape_get_trajectory is not available on such a context */
-    int32_t reserved0;
+    int32_t pair_antiherm;         /* (the slot ABI v5 reserved; 0 before) 1: lane_pair, unitary_flow, n = 4, UnitaryGate, first-order
+                                      gradient -- the backward sweep carries only the anti-Hermitian part of z M_t, all that the
+                                      gradient traces see of it (GRAPE_PAIR_AH=0 in the environment at grape_create: the full M_t) */
     /* ---- ABI v6 ---- */
     uint64_t workspace_budget_bytes; /* what the workspace arrays may take: 0.9 x the device memory free at grape_create minus the
                                       other buffers, or GRAPE_MAX_WORKSPACE_BYTES -- with member_chunk, what makes a run's

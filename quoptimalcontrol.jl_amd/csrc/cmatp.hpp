@@ -316,6 +316,191 @@ GRAPE_DEV void psquare_antihermitian(PMat<N> &c, const PMat<N> &g, const PMat<N>
     }
 }
 
+// ---- anti-Hermitian matrices in the pair layout -------------------------------------------------------------------------
+// The backward sweep of the unitary UnitaryGate flow carries A_t = P_t' A_{t+1} P_t, the anti-Hermitian part of z M_t (the only
+// part the gradient traces see: sweep_pair.hip, PMODE_UNITARY_AH).  One triangle of A determines the other, so a lane keeps
+//   * its diagonal block D = A[own block, own block]: the imaginary parts of the diagonal (the real parts are zero) and the
+//     entries above the diagonal (rl < jl); below it D[jl, rl] = -conj(D[rl, jl]);
+//   * its off-diagonal block O[rl, jl] = A_loc[(1, rl), jl] (rows of the partner's index block, own columns) in full.
+// The partner's off-diagonal block is -O', so only the partner's diagonal block crosses by DPP (N^2/4 doubles where
+// fetch_partner moves N^2).  Own-block-first order as everywhere: every index below is a compile-time constant.
+template <int N>
+struct PAntiH {
+    static constexpr int NC = N / 2;
+    double di[NC];                        // Im D[jl, jl]
+    double ur[NC * NC], ui[NC * NC];      // D[rl, jl], rl < jl, at rl + jl NC (the other slots are never touched)
+    double ore[NC * NC], oim[NC * NC];    // O[rl, jl] at rl + jl NC
+};
+
+// the stored entries, taken out of a full own half (whatever else `m` holds is not read: a product whose result only
+// passes through here is computed for these entries alone)
+template <int N>
+GRAPE_DEV void pah_from_mat(PAntiH<N> &h, const PMat<N> &m)
+{
+    constexpr int NC = N / 2;
+#pragma unroll
+    for (int jl = 0; jl < NC; ++jl)
+#pragma unroll
+        for (int rl = 0; rl < NC; ++rl) {
+            if (rl == jl)
+                h.di[jl] = m.im[jl + jl * N];
+            if (rl < jl) {
+                h.ur[rl + jl * NC] = m.re[rl + jl * N];
+                h.ui[rl + jl * NC] = m.im[rl + jl * N];
+            }
+            h.ore[rl + jl * NC] = m.re[NC + rl + jl * N];
+            h.oim[rl + jl * NC] = m.im[NC + rl + jl * N];
+        }
+}
+
+// A = (z C - conj(z) C') / 2 from the own half of any C: the own diagonal block from my own entries, the off-diagonal
+// block needs the partner's block-1 rows (its entries [own block of mine, its columns])
+template <int N>
+GRAPE_DEV void pah_of_scaled(PAntiH<N> &h, const PMat<N> &c, double zr, double zi)
+{
+    constexpr int NC = N / 2, NE = N * NC;
+    PMat<N> Z;
+#pragma unroll
+    for (int e = 0; e < NE; ++e) {
+        Z.re[e] = fma(c.re[e], zr, -c.im[e] * zi);
+        Z.im[e] = fma(c.re[e], zi, c.im[e] * zr);
+    }
+#pragma unroll
+    for (int jl = 0; jl < NC; ++jl)
+#pragma unroll
+        for (int rl = 0; rl < NC; ++rl) {
+            if (rl == jl)
+                h.di[jl] = Z.im[jl + jl * N];
+            if (rl < jl) {
+                h.ur[rl + jl * NC] = 0.5 * (Z.re[rl + jl * N] - Z.re[jl + rl * N]);
+                h.ui[rl + jl * NC] = 0.5 * (Z.im[rl + jl * N] + Z.im[jl + rl * N]);
+            }
+            // Z[partner block rl, own jl] - conj(Z[own jl, partner block rl]): the latter is the partner's local (1, jl) of column rl
+            h.ore[rl + jl * NC] = 0.5 * (Z.re[NC + rl + jl * N] - pair_swap(Z.re[NC + jl + rl * N]));
+            h.oim[rl + jl * NC] = 0.5 * (Z.im[NC + rl + jl * N] + pair_swap(Z.im[NC + jl + rl * N]));
+        }
+}
+
+// the full own half (the real parts of the diagonal are written as zeros; pmul_antih_a never reads them)
+template <int N>
+GRAPE_DEV void pah_own(PMat<N> &a, const PAntiH<N> &h)
+{
+    constexpr int NC = N / 2;
+#pragma unroll
+    for (int jl = 0; jl < NC; ++jl)
+#pragma unroll
+        for (int rl = 0; rl < NC; ++rl) {
+            if (rl == jl) {
+                a.re[rl + jl * N] = 0.0;
+                a.im[rl + jl * N] = h.di[jl];
+            } else if (rl < jl) {
+                a.re[rl + jl * N] = h.ur[rl + jl * NC];
+                a.im[rl + jl * N] = h.ui[rl + jl * NC];
+            } else {
+                a.re[rl + jl * N] = -h.ur[jl + rl * NC];
+                a.im[rl + jl * N] = h.ui[jl + rl * NC];
+            }
+            a.re[NC + rl + jl * N] = h.ore[rl + jl * NC];
+            a.im[NC + rl + jl * N] = h.oim[rl + jl * NC];
+        }
+}
+
+// the partner's half as fetch_partner would deliver it: its diagonal block by DPP, its off-diagonal block = -O'
+template <int N>
+GRAPE_DEV void pah_partner(PMat<N> &par, const PAntiH<N> &h)
+{
+    constexpr int NC = N / 2;
+#pragma unroll
+    for (int jl = 0; jl < NC; ++jl)
+#pragma unroll
+        for (int rl = 0; rl < NC; ++rl) {
+            if (rl == jl) {
+                par.re[rl + jl * N] = 0.0;
+                par.im[rl + jl * N] = pair_swap(h.di[jl]);
+            } else if (rl < jl) {
+                const double vr = pair_swap(h.ur[rl + jl * NC]), vi = pair_swap(h.ui[rl + jl * NC]);
+                par.re[rl + jl * N] = vr;
+                par.im[rl + jl * N] = vi;
+                par.re[jl + rl * N] = -vr;
+                par.im[jl + rl * N] = vi;
+            }
+            par.re[NC + rl + jl * N] = -h.ore[jl + rl * NC];
+            par.im[NC + rl + jl * N] = h.oim[jl + rl * NC];
+        }
+}
+
+// C = A * B for an anti-Hermitian A given by pah_own / pah_partner: pmul without the FMAs whose A operand is a zero real
+// part -- the diagonal of my block (r = kl) and of the partner's (rbar = kl): two per entry of C
+template <int N>
+GRAPE_DEV void pmul_antih_a(PMat<N> &c, const PMat<N> &a, const PMat<N> &apar, const PMat<N> &b)
+{
+    constexpr int NC = N / 2;
+#pragma unroll
+    for (int jl = 0; jl < NC; ++jl)
+#pragma unroll
+        for (int r = 0; r < N; ++r) {
+            double sr = 0.0, si = 0.0;
+#pragma unroll
+            for (int kl = 0; kl < NC; ++kl) {
+                {
+                    const double ar = a.re[r + kl * N], ai = a.im[r + kl * N];
+                    const double br = b.re[kl + jl * N], bi = b.im[kl + jl * N];
+                    if (r != kl) sr = fma(ar, br, sr);
+                    sr = fma(-ai, bi, sr);
+                    if (r != kl) si = fma(ar, bi, si);
+                    si = fma(ai, br, si);
+                }
+                {
+                    const int rb = flip_block<N>(r);
+                    const double ar = apar.re[rb + kl * N], ai = apar.im[rb + kl * N];
+                    const double br = b.re[NC + kl + jl * N], bi = b.im[NC + kl + jl * N];
+                    if (rb != kl) sr = fma(ar, br, sr);
+                    sr = fma(-ai, bi, sr);
+                    if (rb != kl) si = fma(ar, bi, si);
+                    si = fma(ai, br, si);
+                }
+            }
+            c.re[r + jl * N] = sr;
+            c.im[r + jl * N] = si;
+        }
+}
+
+// H = A^H * B where the result is known to be anti-Hermitian (A' = P' (A P)): pmul_ah_b for the stored entries only -- the
+// off-diagonal block in full, of the own diagonal block the imaginary parts of the diagonal and the entries above it
+template <int N>
+GRAPE_DEV void pmul_ah_b_antih(PAntiH<N> &h, const PMat<N> &a, const PMat<N> &apar, const PMat<N> &b)
+{
+    constexpr int NC = N / 2;
+#pragma unroll
+    for (int jl = 0; jl < NC; ++jl)
+#pragma unroll
+        for (int rl = 0; rl < NC; ++rl) {
+            double sr = 0.0, si = 0.0, tr = 0.0, ti = 0.0;
+#pragma unroll
+            for (int s = 0; s < N; ++s) {
+                const double br = b.re[s + jl * N], bi = b.im[s + jl * N];
+                if (rl <= jl) {
+                    const double ar = a.re[s + rl * N], ai = -a.im[s + rl * N];
+                    if (rl < jl) { sr = fma(ar, br, sr); sr = fma(-ai, bi, sr); }
+                    si = fma(ar, bi, si); si = fma(ai, br, si);
+                }
+                {
+                    const double ar = apar.re[flip_block<N>(s) + rl * N], ai = -apar.im[flip_block<N>(s) + rl * N];
+                    tr = fma(ar, br, tr); tr = fma(-ai, bi, tr);
+                    ti = fma(ar, bi, ti); ti = fma(ai, br, ti);
+                }
+            }
+            if (rl == jl)
+                h.di[jl] = si;
+            if (rl < jl) {
+                h.ur[rl + jl * NC] = sr;
+                h.ui[rl + jl * NC] = si;
+            }
+            h.ore[rl + jl * NC] = tr;
+            h.oim[rl + jl * NC] = ti;
+        }
+}
+
 // p = exp(g), degree-8 Taylor polynomial in 3 products + scaling/squaring: cmat.hpp's expm_t8 on pair matrices, with the
 // combination passes trimmed to one FMA per term:
 //   * the polynomial's low part I + g + y2 a2 SEEDS the accumulators of the last product (pmul_add) instead of being added

@@ -291,6 +291,7 @@ struct grape_ctx {
     int risk_slot = 0;                         // the array of a batch that runs array by array: which p / F_beta it writes
     bool risk_evaluated = false;               // d_risk_p holds the weights of an evaluation under the current setting
     std::vector<double> h_wts;                 // host copy of the ensemble weights (grape_set_risk validates them)
+    bool pair_ah_env = true;                   // GRAPE_PAIR_AH=0: the lane-pair unitary sweep carries the full M_t backwards (PMODE_UNITARY)
     bool mf_publish = true;                    // GRAPE_MF_PUBLISH=0: reduce_rows_kernel's staged publication instead of per-workgroup host flags
     unsigned long long seq = 0;
     std::string kernel_log;                    // names of the kernels the last evaluation launched (grape_get_kernel_names)
@@ -965,6 +966,7 @@ static int create_shard(const grape_config *cfg, int dev, grape_ctx **out)
         const char *dp = std::getenv("GRAPE_DIRECT_PUBLISH");
         c->direct_publish = !(dp && dp[0] == '0');
         c->mf_publish = !env_off("GRAPE_MF_PUBLISH");
+        c->pair_ah_env = !env_off("GRAPE_PAIR_AH");
     }
     {
         // x upload path.  Default: if the device exposes its memory to the CPU (large BAR), the host
@@ -2488,6 +2490,14 @@ static SweepParams sweep_params(const grape_ctx *c, const double *d_x, int n_x)
     return p;
 }
 
+// The lane-pair kernel's unitary flow of a 4 x 4 UnitaryGate problem sweeps back on the anti-Hermitian part of z M_t alone
+// (sweep_pair.hip, PMODE_UNITARY_AH) -- all the first-order gradient sees of it; the exact gradient needs the full M_t (W_t dump)
+static bool pair_antiherm(const grape_ctx *c)
+{
+    return c->family == 0 && c->pair && c->unitary && c->cfg.n == 4 && c->cfg.sys_type == GRAPE_UNITARY_GATE && !c->exact_w1 &&
+           c->cfg.gradient != GRAPE_GRADIENT_EXACT && c->pair_ah_env;
+}
+
 // ... and its two launchers: the lane-pair kernels (sweep_pair.hip) or the lane-per-chunk ones (sweep_small.hip)
 static hipError_t launch_small_family(const grape_ctx *c, int sandwich, int mode, const SweepParams &p, hipStream_t stream)
 {
@@ -2835,7 +2845,7 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
             q.E = cnt;
             q.BPX = (cnt + c->MPB - 1) / c->MPB;
             const int mode = c->unitary ? 2 : (c->d_costates ? 1 : 0), sand = c->cfg.sys_type != GRAPE_UNITARY_GATE;
-            HIP_TRY(c, launch_small_family(c, sand, mode, q, stream));
+            HIP_TRY(c, launch_small_family(c, sand, (mode == 2 && pair_antiherm(c)) ? 3 : mode, q, stream));
             if (rc_on) {                                     // running cost of these members, from the propagators just stored
                 SweepParams r = q;
                 r.rc_only = 1;
@@ -5139,6 +5149,7 @@ extern "C" int grape_get_info(const grape_ctx *c, grape_info *info)
         info->expm_action = s0->action ? 1 : 0;
         info->prop_chain = s0->thin_dpp ? 1 : 0;
         info->member_chunk = s0->Ec;
+        info->pair_antiherm = pair_antiherm(s0) ? 1 : 0;
         info->workspace_budget_bytes = s0->ws_budget;
         info->scaled_controls = s0->ctrl_scaled ? 1 : 0;
         info->propagator_blocks = s0->family == 2 ? s0->any_blocks : 0;

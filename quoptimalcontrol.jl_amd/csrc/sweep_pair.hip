@@ -10,6 +10,10 @@
 // and the scan's products are shared by the pair.  At the headline config (E = 1024 members on 1024
 // SIMDs) a member is W = 2 waves = 64 chunks of 8 slices.
 //
+// PMODE_UNITARY_AH (n = 4, UnitaryGate): tr M_t is the same for every t (P_t unitary) and the gradient traces see only the
+// anti-Hermitian part A_t of z M_t, so phase D carries one triangle of A_t = P_t' A_{t+1} P_t (cmatp.hpp: PAntiH) -- no z pass,
+// no trace, a quarter of the partner traffic for the carried matrix, 10 FMAs per control in the gradient.
+//
 // Operators: the two lanes of a pair need DIFFERENT entries of the member's (wave-uniform) operators, so
 // the scalar-load trick of sweep_small.hip does not apply; instead the workgroup stages, per member, a
 // parity-relative image of [A' | B'_c | B'_c^T | Xi | Xt] in LDS once (2 x (2K+3) x n*n/2 double2 = 2.8 KB
@@ -44,7 +48,10 @@
 
 namespace grape {
 
-enum { PMODE_GENERAL = 0, PMODE_GENERAL_KEEPL = 1, PMODE_UNITARY = 2 };
+// PMODE_UNITARY_AH: the unitary flow of UnitaryGate problems (not the sandwich) with the backward sweep on the anti-Hermitian
+// part of z M_t alone (phase D, below) -- chosen by the host in place of PMODE_UNITARY (GRAPE_PAIR_AH=0 keeps that one)
+enum { PMODE_GENERAL = 0, PMODE_GENERAL_KEEPL = 1, PMODE_UNITARY = 2, PMODE_UNITARY_AH = 3 };
+constexpr int kAhImage = 5;            // double2 slots per control of the anti-Hermitian sweep's gradient image (n = 4)
 constexpr int kParityPad = 8;          // double2 slots (128 B = half an LDS row of 64 banks) between a member's two parity images
 
 // global element index i + j n of local element (r, jl) as seen by a lane of parity q
@@ -265,6 +272,52 @@ GRAPE_DEV void pwrite_gradient(double *out, const double2 *s_bt, int K, const PM
     }
 }
 
+// The same entries from the anti-Hermitian part A of z M alone (PMODE_UNITARY_AH, n = 4): tr(B'_c A) with B'_c anti-Hermitian
+// is real and needs one triangle of each -- per lane the two diagonal entries of its block, the entry above them and three
+// entries of the off-diagonal block (the pair (0,1) / (1,0) of that block is split between the two lanes).
+// s_img: kAhImage double2 per control, [w_d0 w_d1 | w_u | w_O00 | w_O11 | w_O01], built in the prologue.
+GRAPE_DEV void pwrite_gradient_antih(double *out, const double2 *s_img, int K, const PAntiH<4> &h, double gs, int p)
+{
+    auto dot = [&](const double2 (&w)[kAhImage]) {
+        double re = w[0].x * h.di[0];
+        re = fma(w[0].y, h.di[1], re);
+        re = fma(w[1].x, h.ur[2], re);
+        re = fma(w[1].y, h.ui[2], re);
+        re = fma(w[2].x, h.ore[0], re);
+        re = fma(w[2].y, h.oim[0], re);
+        re = fma(w[3].x, h.ore[3], re);
+        re = fma(w[3].y, h.oim[3], re);
+        re = fma(w[4].x, h.ore[2], re);
+        re = fma(w[4].y, h.oim[2], re);
+        return re + pair_swap(re);
+    };
+    // operand reads one control ahead, as in pwrite_gradient
+    double2 b0[kAhImage], b1[kAhImage];
+#pragma unroll
+    for (int e = 0; e < kAhImage; ++e)
+        b0[e] = s_img[e];
+    for (int c = 0; c < K; c += 2) {
+        if (c + 1 < K) {
+#pragma unroll
+            for (int e = 0; e < kAhImage; ++e)
+                b1[e] = s_img[(c + 1) * kAhImage + e];
+        }
+        const double re = dot(b0);
+        if (p == 0)
+            out[c] = gs * re;
+        if (c + 1 < K) {
+            if (c + 2 < K) {
+#pragma unroll
+                for (int e = 0; e < kAhImage; ++e)
+                    b0[e] = s_img[(c + 2) * kAhImage + e];
+            }
+            const double r1 = dot(b1);
+            if (p == 0)
+                out[c + 1] = gs * r1;
+        }
+    }
+}
+
 // VEC (general flow, left multiplication, n = 4, at most kVecSlices slices per lane): the states are n x 1 -- column 0 of the
 // zero-padded matrices -- and the sweep back runs on VECTORS (phase D, below); phase A then stores no in-chunk prefixes.
 constexpr int kVecSlices = 16;
@@ -276,8 +329,10 @@ __global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restr
 {
     constexpr int NN = N * N, NC = N / 2, NE = N * NC;
     constexpr int MAXW = MAXT / 64;
-    constexpr bool UNI = (MODE == PMODE_UNITARY);
+    constexpr bool AH = (MODE == PMODE_UNITARY_AH);
+    constexpr bool UNI = (MODE == PMODE_UNITARY) || AH;
     constexpr bool KEEPL = (MODE == PMODE_GENERAL_KEEPL);
+    static_assert(!AH || (N == 4 && !SAND && !DUMPW && !VEC), "the anti-Hermitian sweep serves UnitaryGate at n = 4, first-order gradient");
     // the backward sweep counts its own propagator loads (PBuf): only where they are the sweep's ONLY vector-memory operations
     // -- gradient entries staged in LDS (XGLDS), no W_t dump
     constexpr bool PDASM = (GRAPE_PD == 2) && UNI && N == 4 && !DUMPW && XGLDS;
@@ -354,8 +409,8 @@ __global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restr
         for (int idx = L; idx < 2 * NM * NE; idx += LT) {
             const int q = idx / (NM * NE), rem = idx - q * NM * NE;
             const int mat = rem / NE, e = rem - mat * NE;
-            if (mat == 2 * K + 3)
-                continue;                            // Xi Xt': filled below
+            if (mat == 2 * K + 3 || (AH && mat > K && mat <= 2 * K))
+                continue;                            // Xi Xt' / the anti-Hermitian sweep's gradient image: filled below
             const int r = e % N, jl = e / N;
             const int i = (((r / NC) ^ q) * NC) + (r % NC), j = q * NC + jl;
             int src;
@@ -363,6 +418,29 @@ __global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restr
             else if (mat <= 2 * K)   src = (mat - K) * NN + j + i * N;           // B'_c transposed
             else                     src = (mat - K) * NN + i + j * N;           // Xi, Xt
             s_ops[(size_t)q * PS + rem] = ops[src];
+        }
+    }
+    if constexpr (AH) {
+        // gradient image in place of the B'_c^T images: the weights of pwrite_gradient_antih, from Bs = (B' - B'^H) / 2 so that both
+        // triangles of an operator that is anti-Hermitian only to rounding enter alike.  tr(Bs A) = -sum_i Im Bs[i,i] Im A[i,i]
+        // + sum_{i<j} 2 Re(Bs[j,i] A[i,j]); a lane of parity q holds A[i,j] for (i,j) = (P0, P0+1) [weight 2], (Q0, P0) and
+        // (Q0+1, P0+1) [weight 1: the partner holds the mirrored entry and adds the same], (Q0, P0+1) [weight 2], P0 = 2q, Q0 = 2 - 2q
+        const double2 *__restrict__ ops = ops_all + (size_t)kl * (K + 3) * NN;
+        for (int idx = L; idx < 2 * K * 2 * kAhImage; idx += LT) {
+            const int q = idx / (K * 2 * kAhImage), rem = idx - q * (K * 2 * kAhImage);
+            const int c = rem / (2 * kAhImage), sl = rem - c * (2 * kAhImage);
+            const int P0 = q * NC, Q0 = (1 - q) * NC;
+            int jj, ii;
+            double wt = 1.0;
+            if (sl < 2)       { jj = ii = P0 + sl; }
+            else if (sl < 4)  { jj = P0 + 1; ii = P0; wt = 2.0; }
+            else if (sl < 6)  { jj = P0; ii = Q0; }
+            else if (sl < 8)  { jj = P0 + 1; ii = Q0 + 1; }
+            else              { jj = P0 + 1; ii = Q0; wt = 2.0; }
+            const double2 b1 = ops[(size_t)(1 + c) * NN + jj + ii * N], b2 = ops[(size_t)(1 + c) * NN + ii + jj * N];
+            const double bsr = 0.5 * (b1.x - b2.x), bsi = 0.5 * (b1.y + b2.y);        // Bs[jj, ii]
+            const double v = sl < 2 ? -bsi : ((sl & 1) ? -wt * bsi : wt * bsr);
+            reinterpret_cast<double *>(s_ops + (size_t)q * PS + (size_t)(1 + K) * NE)[c * 2 * kAhImage + sl] = v;
         }
     }
     if (L < 2 * NE) {                                // Xi Xt' (unitary UnitaryGate fix-up), one entry per lane, from the global operators
@@ -560,6 +638,7 @@ __global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restr
     // through LDS.  Unitary flow: M at the chunk end from the inclusive prefix U and the total T;
     // general flow: state at the chunk start and costate at the chunk end from prefix and suffix.
     PMat<N> Xs, Le;
+    PAntiH<N> Ah;                                    // PMODE_UNITARY_AH: what the backward sweep carries in place of M
     double zr = 0.0, zi = 0.0;
     {
         PMat<N> inc = Q, oth, tmp, ipar;
@@ -651,11 +730,25 @@ __global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restr
                 pload_lds(xi_o, sXX_o);
                 pmul(C0, xi_m, xi_o, T);
             }
+            if constexpr (AH) {
+                // tr M_t = tr C0 for every t (the P_t are unitary): z is one number per member, and of Z = z M_t only the
+                // anti-Hermitian part reaches Re tr(B'_c Z).  Conjugation by a unitary keeps it anti-Hermitian, so the sweep
+                // carries A_t = P_t' A_{t+1} P_t from A at the chunk end = U A0 U', A0 = (z C0 - conj(z) C0') / 2
+                double tr_r, tr_i;
+                ptrace(tr_r, tr_i, C0);
+                zr = tr_r;
+                zi = -tr_i;
+                PAntiH<N> a0;
+                pah_of_scaled(a0, C0, zr, zi);
+                pah_own(C0, a0);
+            }
             fetch_partner(ipar, inc);
             pmul(tmp, inc, ipar, C0);
             PMat<N> tp;
             fetch_partner(tp, tmp);
             pmul_a_bh(Xs, tmp, tp, inc, ipar);       // Xs := M at the chunk end = U C0 U'
+            if constexpr (AH)
+                pah_from_mat(Ah, Xs);                // (the product above is then formed for the stored entries only)
         } else {
             PMat<N> xi_m;
             pload_lds(xi_m, sXi);
@@ -725,6 +818,17 @@ __global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restr
         // partner by DPP; slice j-1's load is issued BEFORE slice j's products (two register buffers,
         // loop unrolled by two), so the HBM latency hides under ~300 VALU instructions of both waves.
         PMat<N> M = Xs, Mp, tmp, PA, PB, Pp;
+        // PMODE_UNITARY_AH: A_t = P' A_{t+1} P on the stored entries -- the partner's half of A costs 8 DPP moves (its diagonal
+        // block), the first product skips the zero real parts of A's diagonal, the second forms one triangle; no z pass, no trace
+        auto products_ah = [&](const PMat<N> &P) {
+            if constexpr (AH) {
+                fetch_partner(Pp, P);
+                pah_own(M, Ah);
+                pah_partner(Mp, Ah);
+                pmul_antih_a(tmp, M, Mp, P);
+                pmul_ah_b_antih(Ah, P, Pp, tmp);
+            }
+        };
         auto step = [&](int j, const PMat<N> &P) {
             const int t = t0 + j;
             if ((GRAPE_ABL & 64) && t < Nsl) {           // loads only: no products, no gradient
@@ -738,6 +842,14 @@ __global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restr
                 for (int e = 0; e < NE; ++e)
                     acc += M.re[e] + M.im[e];
                 if (par == 0) xg[j * K] = acc;
+            } else
+            if constexpr (AH) {
+                if (t < Nsl) {
+                    products_ah(P);
+                    pwrite_gradient_antih(xg + j * K, sBT, K, Ah, gs, par);
+                    if (t == Nsl - 1 && par == 0)
+                        s_F[mb] = pfigure_of_merit<N, SAND>(zr, zi);
+                }
             } else
             if (t < Nsl) {
                 fetch_partner(Pp, P);
@@ -783,6 +895,7 @@ __global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restr
         // paces phase D at the rate HBM delivers; left as it was.)
         int j = S - 1;
 #if GRAPE_PD == 1
+        static_assert(!AH, "the anti-Hermitian sweep is written for GRAPE_PD 0 and 2");
         // products and gradient of a slice apart: the products are the last readers of the slice's propagator, so the load of
         // the slice after next goes out between them -- unconditionally, from a clamped (always valid) address, so that the
         // compiler's s_waitcnt bookkeeping sees the same history on every path and waits for the OLDER buffer only
@@ -833,14 +946,25 @@ __global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restr
         if constexpr (PDASM) {
             auto products = [&](int jj, const PMat<N> &P) {
                 if (t0 + jj < Nsl) {
-                    fetch_partner(Pp, P);
-                    fetch_partner(Mp, M);
-                    pmul(tmp, M, Mp, P);
-                    pmul_ah_b(M, P, Pp, tmp);            // M_t = P' M_{t+1} P
+                    if constexpr (AH) {
+                        products_ah(P);
+                    } else {
+                        fetch_partner(Pp, P);
+                        fetch_partner(Mp, M);
+                        pmul(tmp, M, Mp, P);
+                        pmul_ah_b(M, P, Pp, tmp);        // M_t = P' M_{t+1} P
+                    }
                 }
             };
             auto gradient = [&](int jj) {
                 const int t = t0 + jj;
+                if constexpr (AH) {
+                    if (t < Nsl) {
+                        pwrite_gradient_antih(xg + jj * K, sBT, K, Ah, gs, par);
+                        if (t == Nsl - 1 && par == 0)
+                            s_F[mb] = pfigure_of_merit<N, SAND>(zr, zi);
+                    }
+                } else
                 if (t < Nsl) {
                     if (!SAND) {
                         double tr_r, tr_i;
@@ -1193,7 +1317,7 @@ static hipError_t plaunch_one(const SweepParams &p0, hipStream_t stream)
         static const int tune_env = [] { const char *e = getenv("GRAPE_PAIR_TUNE"); return e ? atoi(e) : 0; }();
         p.tune = tune_env;
     }
-    if (MODE == PMODE_UNITARY && XGLDS && p.S > 1) {         // room for the chunks' last propagators?
+    if ((MODE == PMODE_UNITARY || MODE == PMODE_UNITARY_AH) && XGLDS && p.S > 1) {         // room for the chunks' last propagators?
         const size_t with = sweep_pair_lds_bytes(N, p.MPB, p.LT, p.S, p.K, true, true);
         if (with <= 160 * 1024) {
             p.plast_lds = 1;
@@ -1251,6 +1375,11 @@ static hipError_t plaunch_ns(int mode, const SweepParams &p, hipStream_t stream)
                    : plaunch_one<N, SAND, PMODE_GENERAL_KEEPL, false>(p, stream);
     case PMODE_UNITARY:
         return lds ? plaunch_one<N, SAND, PMODE_UNITARY, true>(p, stream) : plaunch_one<N, SAND, PMODE_UNITARY, false>(p, stream);
+    case PMODE_UNITARY_AH:                           // (the host asks for it at n = 4 without the sandwich only)
+        if constexpr (N == 4 && SAND == 0)
+            return lds ? plaunch_one<N, SAND, PMODE_UNITARY_AH, true>(p, stream)
+                       : plaunch_one<N, SAND, PMODE_UNITARY_AH, false>(p, stream);
+        return hipErrorInvalidConfiguration;
     default:
         return hipErrorInvalidValue;
     }

@@ -79,7 +79,7 @@ class GrapeInfo(C.Structure):
                 ("states_stored", C.c_int32), ("rank_one_chain", C.c_int32),
                 ("sparse_controls", C.c_int32), ("fused_forward", C.c_int32),
                 ("time_chunks", C.c_int32), ("hoisted_controls", C.c_int32),
-                ("expm_action", C.c_int32), ("prop_chain", C.c_int32), ("member_chunk", C.c_int32), ("reserved0", C.c_int32),
+                ("expm_action", C.c_int32), ("prop_chain", C.c_int32), ("member_chunk", C.c_int32), ("pair_antiherm", C.c_int32),
                 ("workspace_budget_bytes", C.c_uint64), ("scaled_controls", C.c_int32), ("propagator_blocks", C.c_int32)]
 
 
