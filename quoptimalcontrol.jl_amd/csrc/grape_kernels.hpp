@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace grape {
 
@@ -246,8 +247,8 @@ struct SweepParams {
     int32_t jvp_multi;
     int64_t jvp_dir_xdot, jvp_dir_ydot, jvp_dir_xf, jvp_dir_w;
 };
-// grape_eval_jvp_multi: the directions trajectory_jvp_multi_kernel<n, m> carries per launch (DB; chosen per shape from the
-// register file), its workgroup size limit (all n: 512 registers per lane), and whether the shape
+// grape_eval_jvp_multi: the directions trajectory_jvp_multi_kernel (trajectory_jvp_kernel<n, m, ..., DB> at DB > 1) carries
+// per launch (DB; chosen per shape from the register file), its workgroup size limit (all n: 512 registers per lane), and whether the shape
 // dispatches to it by default (where it measured faster per direction than the single kernel; GRAPE_JVP_MULTI=0/1 forces)
 constexpr int kJvpMultiMaxThreads = 256;
 constexpr int jvp_multi_block(int n, int m)
@@ -258,12 +259,38 @@ constexpr bool jvp_multi_default(int n, int m)
 {
     return jvp_multi_block(n, m) > 0;
 }
+// workgroup size limit of the kernels that run behind the small-n sweeps (running_cost.hip, observe.hip, vjp.hip, jvp.hip;
+// RcTraits<n>::MAXT): the chunk count of the largest decomposition the sweeps of this n run with
+constexpr int traj_max_threads(int n)
+{
+    return n == 2 ? 1024 : n == 3 ? 512 : 256;
+}
 // static LDS of observe_kernel (vjp = false) / trajectory_vjp_kernel (vjp = true) at operator dimension n with m state
 // columns: the scans' wave totals.  What the host layer subtracts from the device's LDS per workgroup to get the staged
 // instances' budget (the launchers check the sum against the kernel's own attributes).
 constexpr size_t traj_static_lds(int n, int m, bool vjp)
 {
-    return (size_t)((n == 2 ? 1024 : n == 3 ? 512 : 256) / 64) * (size_t)(n * n + (vjp ? n * m : 0)) * 16;
+    return (size_t)(traj_max_threads(n) / 64) * (size_t)(n * n + (vjp ? n * m : 0)) * 16;
+}
+// the nine (n, m) pairs of the small-n family with n x m states: f(integral_constant<int, n>, integral_constant<int, m>)
+template <typename F>
+hipError_t dispatch_nm(int n, int m, F &&f)
+{
+#define GRAPE_NM_CASE(N, M) \
+    case N * 8 + M: return f(std::integral_constant<int, N>{}, std::integral_constant<int, M>{})
+    switch (n * 8 + m) {
+        GRAPE_NM_CASE(2, 1);
+        GRAPE_NM_CASE(2, 2);
+        GRAPE_NM_CASE(3, 1);
+        GRAPE_NM_CASE(3, 2);
+        GRAPE_NM_CASE(3, 3);
+        GRAPE_NM_CASE(4, 1);
+        GRAPE_NM_CASE(4, 2);
+        GRAPE_NM_CASE(4, 3);
+        GRAPE_NM_CASE(4, 4);
+    default: return hipErrorInvalidValue;
+    }
+#undef GRAPE_NM_CASE
 }
 // observe.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::obs_only) only
 hipError_t run_observe(int n, int sandwich, const SweepParams &p, hipStream_t stream);

@@ -7,13 +7,13 @@
 //
 // It runs behind the sweep of the same launch (and behind the running-cost kernels, if any) and reads the propagators P_t
 // that sweep left in the workspace (chunk-major: element e of slice t = c S + jj of member k at ((k S + jj) n^2 + e) CH + c).
-// The decomposition is running_cost_kernel's: one workgroup per member of the launch, one lane per time chunk of S
-// consecutive slices, so every workspace access is lane-contiguous:
-//   1  chunk product Q_c = P_hi-1 ... P_lo
-//   2  exclusive prefix scan of the Q_c over lanes (wave shuffles in a fixed tree, wave totals through LDS, combined in wave
+// The decomposition and the steps marked * are traj_chunk.hpp's: one workgroup per member of the launch, one lane per time
+// chunk of S consecutive slices, so every workspace access is lane-contiguous:
+//   1* chunk product Q_c = P_hi-1 ... P_lo
+//   2* exclusive prefix scan of the Q_c over lanes (wave shuffles in a fixed tree, wave totals through LDS, combined in wave
 //      order): U_start, the cumulative propagator at the chunk start
 //   3  X = U_start Xi [U_start'], then the walk X <- P_t X [P_t'] over the chunk (P read a second time)
-//   4  behind every slice the n_obs traces, one probe at a time (the probes are wave-uniform: scalar loads), stored to y
+//   4  behind every slice the n_obs traces*, one probe at a time (the probes are wave-uniform: scalar loads), stored to y
 //   5  lane 0 also stores the s = 0 entry, the lane that owns slice N - 1 stores X_N
 // Ragged decompositions: a lane whose chunk starts at or behind N, and the padding lanes behind chunk CH - 1, own no slice
 // (Q = 1, nothing stored); the last chunk may be short.  Plain vector stores, no atomics; every number has one fixed
@@ -27,6 +27,7 @@
 #include "cmat.hpp"
 #include "grape_kernels.hpp"
 #include "rc_mat.hpp"
+#include "traj_chunk.hpp"
 
 namespace grape {
 
@@ -76,92 +77,41 @@ __global__ __launch_bounds__(MAXT) void observe_kernel(const double2 *__restrict
     __shared__ double2 s_q[MAXW][NN];              // wave totals of the prefix scan
     extern __shared__ double2 s_img[];             // STAGED: the member's y block, [j][s] as the caller lays it out
 
-    const int CH = p.obs_CH, S = p.S, K = p.K, Nsl = p.N, n_obs = p.obs_n;
-    const int L = threadIdx.x, lane = L & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(L >> 6), W = blockDim.x >> 6;
+    const int Nsl = p.N, n_obs = p.obs_n;
     const int k = blockIdx.x;                        // member within the launch: row of the workspace
     const int kg = k + p.obs_E0;                     // member of the ensemble: row of the probes and of the outputs
-    // the lane's slices [lo, hi): none for chunks that start at or behind N and for the padding lanes behind chunk CH - 1
-    const int lo = (L < CH && L * S < Nsl) ? L * S : Nsl;
-    const int hi = min(lo + S, Nsl);
-    const int cnt = hi - lo;
-    const size_t stride = (size_t)CH;
-    const double2 *__restrict__ Pw = p.props + (size_t)k * S * NN * stride + L;
-    const double2 *__restrict__ opXi = ops_all + (size_t)k * (K + 3) * NN + (size_t)(1 + K) * NN;
-    // probe j of this member: shared (n, m, n_obs) or per member (n, m, Etot, n_obs)
-    const size_t o_step = p.obs_per_member ? (size_t)p.obs_Etot * NM : (size_t)NM;
-    const double2 *__restrict__ o_mem = o_all + (p.obs_per_member ? (size_t)kg * NM : (size_t)0);
-    double2 *__restrict__ yk = p.obs_y ? p.obs_y + (size_t)kg * n_obs * ((size_t)Nsl + 1) : nullptr;
+    const TrajLane<N> ln = traj_lane<N>(p.obs_CH, p.S, Nsl, p.props, k);
+    const int L = ln.L, lo = ln.lo, hi = ln.hi, cnt = ln.cnt;
+    const TrajProbes pr = traj_probes<N, M>(o_all, p.obs_per_member, p.obs_Etot, kg, Nsl);
+    double2 *__restrict__ yk = p.obs_y ? p.obs_y + (size_t)kg * n_obs * pr.y_step : nullptr;
 
-    // ---------------------------------------------------------------- 1: chunk product
-    CMat<N> P, T, oth;
+    // ---------------------------------------------------------------- 1, 2: chunk product, U at the chunk start
+    CMat<N> P, U;
     {
         CMat<N> Q;
-        set_identity(Q);
-        for (int jj = 0; jj < cnt; ++jj) {
-            rc_load_mat(P, Pw + (size_t)jj * NN * stride, stride);
-            mul(T, P, Q);
-            Q = T;
-        }
-        // ------------------------------------------------------------ 2: exclusive prefix over lanes -> U at the chunk start
-        CMat<N> inc = Q;
-        for (int d = 1; d < 64; d <<= 1) {
-            shfl_up(oth, inc, d);
-            if (lane >= d) {
-                mul(T, inc, oth);
-                inc = T;
-            }
-        }
-        shfl_up(oth, inc, 1);
-        if (lane == 0)
-            set_identity(oth);
-        if (W > 1) {
-            if (lane == 63) {
-#pragma unroll
-                for (int e = 0; e < NN; ++e)
-                    s_q[wave][e] = make_double2(inc.re[e], inc.im[e]);
-            }
-            __syncthreads();
-            CMat<N> pre;
-            set_identity(pre);
-            for (int w = 0; w < wave; ++w) {
-                rc_load_lds(inc, &s_q[w][0]);
-                mul(T, inc, pre);
-                pre = T;
-            }
-            mul(T, oth, pre);
-            oth = T;
-        }
+        traj_chunk_product(Q, ln);
+        traj_prefix_start(U, Q, ln, s_q);
     }
     // ---------------------------------------------------------------- 3: the state at the chunk start
     CRect<N, M> X;
-    rload_uniform(X, opXi);                          // (the first m columns of the zero-padded n x n block)
-    obs_apply<N, M, SAND>(X, oth);
+    rload_uniform(X, traj_ops<N>(ops_all, k, p.K).opXi);
+    obs_apply<N, M, SAND>(X, U);
 
     // the n_obs traces y_j = tr(O_j' X) of the state behind s slices, one probe at a time
     auto emit = [&](int s) {
         for (int j = 0; j < n_obs; ++j) {
-            const double2 *__restrict__ o = o_mem + (size_t)j * o_step;
-            double yr = 0.0, yi = 0.0;
-#pragma unroll
-            for (int e = 0; e < NM; ++e) {
-                const double2 v = o[e];
-                yr = fma(v.x, X.re[e], yr);
-                yr = fma(v.y, X.im[e], yr);
-                yi = fma(v.x, X.im[e], yi);
-                yi = fma(-v.y, X.re[e], yi);
-            }
+            const double2 y = traj_probe_trace(pr.probe(j), X);
             if constexpr (STAGED)
-                s_img[s + j * (Nsl + 1)] = make_double2(yr, yi);
+                s_img[s + j * (Nsl + 1)] = y;
             else
-                yk[(size_t)s + (size_t)j * ((size_t)Nsl + 1)] = make_double2(yr, yi);
+                yk[(size_t)s + (size_t)j * pr.y_step] = y;
         }
     };
     if (yk && L == 0)
         emit(0);                                     // (U_start = 1: X is Xi)
     // ---------------------------------------------------------------- 4: the walk
     for (int jj = 0; jj < cnt; ++jj) {
-        rc_load_mat(P, Pw + (size_t)jj * NN * stride, stride);
+        rc_load_mat(P, ln.P(jj), ln.stride);
         obs_apply<N, M, SAND>(X, P);
         if (yk)
             emit(lo + jj + 1);
@@ -224,18 +174,9 @@ hipError_t run_observe(int n, int sandwich, const SweepParams &p, hipStream_t st
         default: return hipErrorInvalidValue;
         }
     }
-    switch (n * 8 + p.obs_m) {
-    case 2 * 8 + 1: return obs_launch_nm<2, 1, false>(p, stream);
-    case 2 * 8 + 2: return obs_launch_nm<2, 2, false>(p, stream);
-    case 3 * 8 + 1: return obs_launch_nm<3, 1, false>(p, stream);
-    case 3 * 8 + 2: return obs_launch_nm<3, 2, false>(p, stream);
-    case 3 * 8 + 3: return obs_launch_nm<3, 3, false>(p, stream);
-    case 4 * 8 + 1: return obs_launch_nm<4, 1, false>(p, stream);
-    case 4 * 8 + 2: return obs_launch_nm<4, 2, false>(p, stream);
-    case 4 * 8 + 3: return obs_launch_nm<4, 3, false>(p, stream);
-    case 4 * 8 + 4: return obs_launch_nm<4, 4, false>(p, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_nm(n, p.obs_m, [&](auto N, auto M) {
+        return obs_launch_nm<decltype(N)::value, decltype(M)::value, false>(p, stream);
+    });
 }
 
 }  // namespace grape

@@ -8,15 +8,15 @@
 // It runs behind the sweep of the same launch and reads the propagators P_t that sweep left in the workspace (chunk-major:
 // element e of slice t = c S + jj of member k at ((k S + jj) n^2 + e) CH + c).  One workgroup per (control array, member),
 // one lane per time chunk of S consecutive slices -- the sweep's own decomposition, so every workspace access is
-// lane-contiguous:
-//   1  chunk product Q_c = P_hi-1 ... P_lo                                   (P read once)
-//   2  inclusive/exclusive prefix scan of the Q_c over lanes (wave shuffles, wave totals through LDS): X at the chunk start
+// lane-contiguous; the decomposition and the steps marked * are traj_chunk.hpp's, shared with observe.hip, vjp.hip and jvp.hip:
+//   1* chunk product Q_c = P_hi-1 ... P_lo                                   (P read once)
+//   2* inclusive/exclusive prefix scan of the Q_c over lanes (wave shuffles, wave totals through LDS): X at the chunk start
 //   3  the states of the chunk: unitary flow (every generator Hermitian): only X at the chunk END = Q_c X_start is kept and
-//      the walks below step back with X_s = P_s' X_s+1; general flow: a forward walk stores X_s+1 per slice in a scratch
+//      the walks below step back with X_s = P_s' X_s+1; general flow: a forward walk* stores X_s+1 per slice in a scratch
 //      array of the chunk-major layout (there is no P' to walk back with)
 //   then per term j (the recurrences of different terms share nothing but P and X):
 //   4  backward walk from Lam = 0: b_c, the chunk's own contribution to the costate that leaves it on the left
-//   5  suffix scan of the affine maps z -> Q_c' z + b_c over lanes, composition (Q1' Q2', Q1' b2 + b1) in a fixed tree
+//   5* suffix scan of the affine maps z -> Q_c' z + b_c over lanes, composition (Q1' Q2', Q1' b2 + b1) in a fixed tree
 //      (shuffles inside a wave, wave totals through LDS, combined last wave first)
 //   6  the same backward walk from the true incoming costate: Lam_t+1 at every slice, M = X_t+1 Lam_t+1', and the K traces
 //      2 Re tr(B'_c M) weighted by w_k -- stored to (term 0) or added to (later terms; same lane, program order) the
@@ -30,6 +30,7 @@
 #include "cmat.hpp"
 #include "grape_kernels.hpp"
 #include "rc_mat.hpp"
+#include "traj_chunk.hpp"
 
 namespace grape {
 
@@ -54,80 +55,33 @@ __global__ __launch_bounds__(MAXT) void running_cost_kernel(const double2 *__res
     __shared__ double2 s_v[MAXW][NM];              // ... and their offsets
     __shared__ double s_j[MAXW];
 
-    const int CH = p.rc_CH, S = p.S, K = p.K, Nsl = p.N;
-    const int L = threadIdx.x, lane = L & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(L >> 6), W = blockDim.x >> 6;
+    const int K = p.K, Nsl = p.N;
     const int k = blockIdx.x;                        // row of the workspace and of the output: (control array, member)
     const int kl = k % p.E;                          // member within the launch
-    // the lane's slices [lo, hi): none for chunks that start at or behind N and for the padding lanes behind chunk CH - 1
-    const int lo = (L < CH && L * S < Nsl) ? L * S : Nsl;
-    const int hi = min(lo + S, Nsl);
-    const int cnt = hi - lo;
-    const size_t stride = (size_t)CH;
-    const double2 *__restrict__ Pw = p.props + (size_t)k * S * NN * stride + L;
-    double2 *__restrict__ Xw = UNI ? nullptr : p.rc_xs + (size_t)k * S * NM * stride + L;
-    const double2 *__restrict__ ops = ops_all + (size_t)kl * (K + 3) * NN;
-    const double2 *__restrict__ opB = ops + NN;
-    const double2 *__restrict__ opXi = ops + (size_t)(1 + K) * NN;
+    const TrajLane<N> ln = traj_lane<N>(p.rc_CH, p.S, Nsl, p.props, k);
+    const int L = ln.L, lane = ln.lane, wave = ln.wave, W = ln.W, lo = ln.lo, cnt = ln.cnt;
+    const size_t stride = ln.stride;
+    double2 *__restrict__ Xw = UNI ? nullptr : ln.template ws<NM>(p.rc_xs);
+    const TrajOps op = traj_ops<N>(ops_all, kl, K);
+    const double2 *__restrict__ opB = op.opB;
     double *__restrict__ row = p.rc_rows + (size_t)k * ((size_t)K * Nsl + 1);
     const double wk = (EXACT && p.rc_unweighted) ? 1.0 : wts_all[kl];
 
-    // ---------------------------------------------------------------- 1: chunk product
-    CMat<N> Q, P, T;
-    set_identity(Q);
-    for (int jj = 0; jj < cnt; ++jj) {
-        rc_load_mat(P, Pw + (size_t)jj * NN * stride, stride);
-        mul(T, P, Q);
-        Q = T;
-    }
-    // ---------------------------------------------------------------- 2: exclusive prefix over lanes -> X at the chunk start
+    // ---------------------------------------------------------------- 1, 2: chunk product, X at the chunk start
+    CMat<N> Q, P;
+    traj_chunk_product(Q, ln);
     CRect<N, M> Xhi;
     {
-        CMat<N> inc = Q, oth;
-        for (int d = 1; d < 64; d <<= 1) {
-            shfl_up(oth, inc, d);
-            if (lane >= d) {
-                mul(T, inc, oth);
-                inc = T;
-            }
-        }
-        shfl_up(oth, inc, 1);
-        if (lane == 0)
-            set_identity(oth);
-        if (W > 1) {
-            if (lane == 63) {
-#pragma unroll
-                for (int e = 0; e < NN; ++e)
-                    s_q[wave][e] = make_double2(inc.re[e], inc.im[e]);
-            }
-            __syncthreads();
-            CMat<N> pre;
-            set_identity(pre);
-            for (int w = 0; w < wave; ++w) {
-                rc_load_lds(inc, &s_q[w][0]);
-                mul(T, inc, pre);
-                pre = T;
-            }
-            mul(T, oth, pre);
-            oth = T;
-        }
-        CRect<N, M> xi, Xs;
-        rload_uniform(xi, opXi);                     // (the first m columns of the zero-padded n x n block)
-        rmul(Xs, oth, xi);
+        CMat<N> U;
+        traj_prefix_start(U, Q, ln, s_q);
+        CRect<N, M> Xs;
+        traj_start_state(Xs, U, op.opXi);
         // ------------------------------------------------------------ 3: the chunk's states
         if (UNI) {
             rmul(Xhi, Q, Xs);
         } else {
             Xhi = Xs;
-            for (int jj = 0; jj < cnt; ++jj) {
-                rc_load_mat(P, Pw + (size_t)jj * NN * stride, stride);
-                if constexpr (EXACT)
-                    rstore_ws(Xw + (size_t)jj * NM * stride, stride, Xhi);  // the state BEFORE slice lo + jj
-                rmul(Xs, P, Xhi);
-                Xhi = Xs;
-                if constexpr (!EXACT)
-                    rstore_ws(Xw + (size_t)jj * NM * stride, stride, Xhi);  // the state AFTER slice lo + jj
-            }
+            traj_walk_store<N, M, EXACT>(Xhi, ln, Xw);
         }
     }
 
@@ -145,7 +99,7 @@ __global__ __launch_bounds__(MAXT) void running_cost_kernel(const double2 *__res
                     if (!UNI)
                         rload_ws(X, Xw + (size_t)jj * NM * stride, stride);
                 }
-                rc_load_mat(P, Pw + (size_t)jj * NN * stride, stride);
+                rc_load_mat(P, ln.P(jj), stride);
                 double yr = 0.0, yi = 0.0;           // y = tr(R' X)
 #pragma unroll
                 for (int e = 0; e < NM; ++e) {
@@ -174,7 +128,7 @@ __global__ __launch_bounds__(MAXT) void running_cost_kernel(const double2 *__res
                         // W_t = X_t Lam_{t+1}' of this term, column by column (rmul_a_bh's sums): a column is stored
                         // (term 0) or added to the block (later terms) before the next one is formed -- the scheduling
                         // barriers keep the whole block and its n^2 loads from being live at once
-                        double2 *__restrict__ wp = p.traj_w + ((size_t)k * S + jj) * NN * stride + L;
+                        double2 *__restrict__ wp = ln.template slot<NN>(p.traj_w, jj);
 #pragma unroll
                         for (int b2 = 0; b2 < N; ++b2) {
                             double wr[N], wi[N];
@@ -241,62 +195,7 @@ __global__ __launch_bounds__(MAXT) void running_cost_kernel(const double2 *__res
         walk(bvec, false);
         // ------------------------------------------------------------ 5: suffix scan of (Q', b)
         CRect<N, M> Lin;
-        {
-            CMat<N> G = Q, Go;
-            CRect<N, M> v = bvec, vo, Tm;
-            for (int d = 1; d < 64; d <<= 1) {
-                shfl_down(Go, G, d);
-                rshfl_down(vo, v, d);
-                if (lane + d < 64) {                 // [L, L+d) then [L+d, L+2d):  (Go G)' z + (G' vo + v)
-                    rmul_ah(Tm, G, vo);
-#pragma unroll
-                    for (int e = 0; e < NM; ++e) {
-                        v.re[e] += Tm.re[e];
-                        v.im[e] += Tm.im[e];
-                    }
-                    mul(T, Go, G);
-                    G = T;
-                }
-            }
-            shfl_down(Go, G, 1);                     // the lanes behind this one, inside the wave
-            rshfl_down(vo, v, 1);
-            if (lane == 63) {
-                set_identity(Go);
-                rzero(vo);
-            }
-            if (W > 1) {
-                __syncthreads();                     // (the previous readers of s_q / s_v are done)
-                if (lane == 0) {
-#pragma unroll
-                    for (int e = 0; e < NN; ++e)
-                        s_q[wave][e] = make_double2(G.re[e], G.im[e]);
-#pragma unroll
-                    for (int e = 0; e < NM; ++e)
-                        s_v[wave][e] = make_double2(v.re[e], v.im[e]);
-                }
-                __syncthreads();
-                CRect<N, M> z;
-                rzero(z);
-                for (int w = W - 1; w > wave; --w) { // what enters this wave on the right, last wave first
-                    rc_load_lds(G, &s_q[w][0]);
-                    rmul_ah(Tm, G, z);
-#pragma unroll
-                    for (int e = 0; e < NM; ++e) {
-                        const double2 vv = s_v[w][e];
-                        z.re[e] = Tm.re[e] + vv.x;
-                        z.im[e] = Tm.im[e] + vv.y;
-                    }
-                }
-                rmul_ah(Tm, Go, z);
-#pragma unroll
-                for (int e = 0; e < NM; ++e) {
-                    Lin.re[e] = Tm.re[e] + vo.re[e];
-                    Lin.im[e] = Tm.im[e] + vo.im[e];
-                }
-            } else {
-                Lin = vo;
-            }
-        }
+        traj_affine_suffix(Lin, Q, bvec, ln, s_q, s_v);
         // ------------------------------------------------------------ 6: the true costates, the traces
         walk(Lin, true);
     }
@@ -401,18 +300,9 @@ hipError_t run_running_cost(int n, const SweepParams &p, hipStream_t stream)
 {
     if (p.rc_only == 2)
         return rc_launch_join(p, stream);
-    switch (n * 8 + p.rc_m) {
-    case 2 * 8 + 1: return rc_launch_nm<2, 1>(p, stream);
-    case 2 * 8 + 2: return rc_launch_nm<2, 2>(p, stream);
-    case 3 * 8 + 1: return rc_launch_nm<3, 1>(p, stream);
-    case 3 * 8 + 2: return rc_launch_nm<3, 2>(p, stream);
-    case 3 * 8 + 3: return rc_launch_nm<3, 3>(p, stream);
-    case 4 * 8 + 1: return rc_launch_nm<4, 1>(p, stream);
-    case 4 * 8 + 2: return rc_launch_nm<4, 2>(p, stream);
-    case 4 * 8 + 3: return rc_launch_nm<4, 3>(p, stream);
-    case 4 * 8 + 4: return rc_launch_nm<4, 4>(p, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_nm(n, p.rc_m, [&](auto N, auto M) {
+        return rc_launch_nm<decltype(N)::value, decltype(M)::value>(p, stream);
+    });
 }
 
 }  // namespace grape

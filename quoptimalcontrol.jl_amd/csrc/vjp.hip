@@ -7,15 +7,15 @@
 //   G[c,t]    = sum_k Re tr(Lam_{k,t+1}' B'_{k,c} X_{k,t+1}) ,   B' = -i dt B  (first order in dt, as grad_func!)
 //
 // It runs behind the sweep of the same launch and reads the propagators P_t that sweep left in the workspace (chunk-major:
-// element e of slice t = c S + jj of member k at ((k S + jj) n^2 + e) CH + c).  The decomposition is running_cost_kernel's:
-// one workgroup per member of the launch, one lane per time chunk of S consecutive slices, every workspace access
-// lane-contiguous:
-//   1  chunk product Q_c = P_hi-1 ... P_lo
-//   2  exclusive prefix scan of the Q_c over lanes (wave shuffles, wave totals through LDS): X at the chunk start
+// element e of slice t = c S + jj of member k at ((k S + jj) n^2 + e) CH + c).  The decomposition and the steps marked * are
+// traj_chunk.hpp's: one workgroup per member of the launch, one lane per time chunk of S consecutive slices, every workspace
+// access lane-contiguous:
+//   1* chunk product Q_c = P_hi-1 ... P_lo
+//   2* exclusive prefix scan of the Q_c over lanes (wave shuffles, wave totals through LDS): X at the chunk start
 //   3  the states of the chunk: unitary flow: only X at the chunk END is kept and the last walk steps back with
-//      X_s = P_s' X_s+1; general flow: a forward walk stores X_s+1 per slice in the scratch of the chunk-major layout
+//      X_s = P_s' X_s+1; general flow: a forward walk* stores X_s+1 per slice in the scratch of the chunk-major layout
 //   4  backward walk from Lam = 0: b_c, the chunk's own contribution to the costate that leaves it on the left
-//   5  suffix scan of the affine maps z -> Q_c' z + b_c over lanes, composition (Q1' Q2', Q1' b2 + b1) in a fixed tree
+//   5* suffix scan of the affine maps z -> Q_c' z + b_c over lanes, composition (Q1' Q2', Q1' b2 + b1) in a fixed tree
 //   6  the same walk from the true incoming costate: Lam_t+1 at every slice and the K traces Re tr(B'_c X_t+1 Lam_t+1')
 // The source of the recurrence does not depend on the states and is linear in the cotangents: ONE pair of walks serves any
 // number of probes (running_cost_kernel walks once per term).  The probes are wave-uniform (scalar loads); ybar is read in
@@ -32,6 +32,7 @@
 #include "cmat.hpp"
 #include "grape_kernels.hpp"
 #include "rc_mat.hpp"
+#include "traj_chunk.hpp"
 
 namespace grape {
 
@@ -52,25 +53,17 @@ __global__ __launch_bounds__(MAXT) void trajectory_vjp_kernel(const double2 *__r
     __shared__ double2 s_v[MAXW][NM];              // ... and their offsets
     extern __shared__ double2 s_img[];             // STAGED: the member's ybar block, [j][s] as the caller lays it out
 
-    const int CH = p.vjp_CH, S = p.S, K = p.K, Nsl = p.N, n_obs = ybar_all ? p.vjp_n : 0;
-    const int L = threadIdx.x, lane = L & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(L >> 6), W = blockDim.x >> 6;
+    const int K = p.K, Nsl = p.N, n_obs = ybar_all ? p.vjp_n : 0;
     const int k = blockIdx.x;                        // member within the launch: row of the workspace and of the rows
     const int kg = k + p.vjp_E0;                     // member of the ensemble: row of the probes and of the cotangents
-    // the lane's slices [lo, hi): none for chunks that start at or behind N and for the padding lanes behind chunk CH - 1
-    const int lo = (L < CH && L * S < Nsl) ? L * S : Nsl;
-    const int hi = min(lo + S, Nsl);
-    const int cnt = hi - lo;
-    const size_t stride = (size_t)CH;
-    const double2 *__restrict__ Pw = p.props + (size_t)k * S * NN * stride + L;
-    double2 *__restrict__ Xw = UNI ? nullptr : p.vjp_xs + (size_t)k * S * NM * stride + L;
-    const double2 *__restrict__ ops = ops_all + (size_t)k * (K + 3) * NN;
-    const double2 *__restrict__ opB = ops + NN;
-    const double2 *__restrict__ opXi = ops + (size_t)(1 + K) * NN;
-    // probe j of this member: shared (n, m, n_obs) or per member (n, m, Etot, n_obs)
-    const size_t o_step = p.vjp_per_member ? (size_t)p.vjp_Etot * NM : (size_t)NM;
-    const double2 *__restrict__ o_mem = o_all + (p.vjp_per_member ? (size_t)kg * NM : (size_t)0);
-    const size_t y_step = (size_t)Nsl + 1;
+    const TrajLane<N> ln = traj_lane<N>(p.vjp_CH, p.S, Nsl, p.props, k);
+    const int L = ln.L, lo = ln.lo, cnt = ln.cnt;
+    const size_t stride = ln.stride;
+    double2 *__restrict__ Xw = UNI ? nullptr : ln.template ws<NM>(p.vjp_xs);
+    const TrajOps op = traj_ops<N>(ops_all, k, K);
+    const double2 *__restrict__ opB = op.opB;
+    const TrajProbes pr = traj_probes<N, M>(o_all, p.vjp_per_member, p.vjp_Etot, kg, Nsl);
+    const size_t y_step = pr.y_step;
     const double2 *__restrict__ yb = ybar_all ? ybar_all + (size_t)kg * p.vjp_n * y_step : nullptr;
     double *__restrict__ row = p.vjp_rows + (size_t)k * K * Nsl;
     if constexpr (STAGED) {                          // (the barrier in front of the first walk publishes the image)
@@ -91,62 +84,21 @@ __global__ __launch_bounds__(MAXT) void trajectory_vjp_kernel(const double2 *__r
         }
     }
 
-    // ---------------------------------------------------------------- 1: chunk product
-    CMat<N> Q, P, T;
-    set_identity(Q);
-    for (int jj = 0; jj < cnt; ++jj) {
-        rc_load_mat(P, Pw + (size_t)jj * NN * stride, stride);
-        mul(T, P, Q);
-        Q = T;
-    }
-    // ---------------------------------------------------------------- 2: exclusive prefix over lanes -> X at the chunk start
+    // ---------------------------------------------------------------- 1, 2: chunk product, X at the chunk start
+    CMat<N> Q, P;
+    traj_chunk_product(Q, ln);
     CRect<N, M> Xhi;
     {
-        CMat<N> inc = Q, oth;
-        for (int d = 1; d < 64; d <<= 1) {
-            shfl_up(oth, inc, d);
-            if (lane >= d) {
-                mul(T, inc, oth);
-                inc = T;
-            }
-        }
-        shfl_up(oth, inc, 1);
-        if (lane == 0)
-            set_identity(oth);
-        if (W > 1) {
-            if (lane == 63) {
-#pragma unroll
-                for (int e = 0; e < NN; ++e)
-                    s_q[wave][e] = make_double2(inc.re[e], inc.im[e]);
-            }
-            __syncthreads();
-            CMat<N> pre;
-            set_identity(pre);
-            for (int w = 0; w < wave; ++w) {
-                rc_load_lds(inc, &s_q[w][0]);
-                mul(T, inc, pre);
-                pre = T;
-            }
-            mul(T, oth, pre);
-            oth = T;
-        }
-        CRect<N, M> xi, Xs;
-        rload_uniform(xi, opXi);                     // (the first m columns of the zero-padded n x n block)
-        rmul(Xs, oth, xi);
+        CMat<N> U;
+        traj_prefix_start(U, Q, ln, s_q);
+        CRect<N, M> Xs;
+        traj_start_state(Xs, U, op.opXi);
         // ------------------------------------------------------------ 3: the chunk's states
         if (UNI) {
             rmul(Xhi, Q, Xs);
         } else {
             Xhi = Xs;
-            for (int jj = 0; jj < cnt; ++jj) {
-                rc_load_mat(P, Pw + (size_t)jj * NN * stride, stride);
-                if constexpr (EXACT)
-                    rstore_ws(Xw + (size_t)jj * NM * stride, stride, Xhi);  // the state BEFORE slice lo + jj
-                rmul(Xs, P, Xhi);
-                Xhi = Xs;
-                if constexpr (!EXACT)
-                    rstore_ws(Xw + (size_t)jj * NM * stride, stride, Xhi);  // the state AFTER slice lo + jj
-            }
+            traj_walk_store<N, M, EXACT>(Xhi, ln, Xw);
         }
     }
 
@@ -156,7 +108,7 @@ __global__ __launch_bounds__(MAXT) void trajectory_vjp_kernel(const double2 *__r
         CRect<N, M> X = Xhi, Tm;
         for (int jj = cnt - 1; jj >= 0; --jj) {
             const int t = lo + jj;                   // slice index; the state behind it is X_{t+1}, cotangent row s = t + 1
-            rc_load_mat(P, Pw + (size_t)jj * NN * stride, stride);
+            rc_load_mat(P, ln.P(jj), stride);
             if (xbar_all && t + 1 == Nsl) {          // Lam_N starts from Xbar
                 const double2 *__restrict__ xb = xbar_all + (size_t)kg * NM;
 #pragma unroll
@@ -172,7 +124,7 @@ __global__ __launch_bounds__(MAXT) void trajectory_vjp_kernel(const double2 *__r
                     c = s_img[(t + 1) + j * (Nsl + 1)];
                 else
                     c = yb[(size_t)(t + 1) + (size_t)j * y_step];
-                const double2 *__restrict__ o = o_mem + (size_t)j * o_step;
+                const double2 *__restrict__ o = pr.probe(j);
 #pragma unroll
                 for (int e = 0; e < NM; ++e) {
                     const double2 v = o[e];
@@ -190,7 +142,7 @@ __global__ __launch_bounds__(MAXT) void trajectory_vjp_kernel(const double2 *__r
                     }
                     CMat<N> Mx;
                     rmul_a_bh(Mx, X, Lam);           // W_t = X_t Lam_{t+1}'
-                    double2 *__restrict__ wp = p.traj_w + ((size_t)k * S + jj) * NN * stride + L;
+                    double2 *__restrict__ wp = ln.template slot<NN>(p.traj_w, jj);
 #pragma unroll
                     for (int e = 0; e < NN; ++e)
                         wp[e * stride] = make_double2(Mx.re[e], Mx.im[e]);
@@ -229,62 +181,7 @@ __global__ __launch_bounds__(MAXT) void trajectory_vjp_kernel(const double2 *__r
     walk(bvec, false);
     // ---------------------------------------------------------------- 5: suffix scan of (Q', b)
     CRect<N, M> Lin;
-    {
-        CMat<N> G = Q, Go;
-        CRect<N, M> v = bvec, vo, Tm;
-        for (int d = 1; d < 64; d <<= 1) {
-            shfl_down(Go, G, d);
-            rshfl_down(vo, v, d);
-            if (lane + d < 64) {                     // [L, L+d) then [L+d, L+2d):  (Go G)' z + (G' vo + v)
-                rmul_ah(Tm, G, vo);
-#pragma unroll
-                for (int e = 0; e < NM; ++e) {
-                    v.re[e] += Tm.re[e];
-                    v.im[e] += Tm.im[e];
-                }
-                mul(T, Go, G);
-                G = T;
-            }
-        }
-        shfl_down(Go, G, 1);                         // the lanes behind this one, inside the wave
-        rshfl_down(vo, v, 1);
-        if (lane == 63) {
-            set_identity(Go);
-            rzero(vo);
-        }
-        if (W > 1) {
-            __syncthreads();                         // (the readers of the prefix totals in s_q are done)
-            if (lane == 0) {
-#pragma unroll
-                for (int e = 0; e < NN; ++e)
-                    s_q[wave][e] = make_double2(G.re[e], G.im[e]);
-#pragma unroll
-                for (int e = 0; e < NM; ++e)
-                    s_v[wave][e] = make_double2(v.re[e], v.im[e]);
-            }
-            __syncthreads();
-            CRect<N, M> z;
-            rzero(z);
-            for (int w = W - 1; w > wave; --w) {     // what enters this wave on the right, last wave first
-                rc_load_lds(G, &s_q[w][0]);
-                rmul_ah(Tm, G, z);
-#pragma unroll
-                for (int e = 0; e < NM; ++e) {
-                    const double2 vv = s_v[w][e];
-                    z.re[e] = Tm.re[e] + vv.x;
-                    z.im[e] = Tm.im[e] + vv.y;
-                }
-            }
-            rmul_ah(Tm, Go, z);
-#pragma unroll
-            for (int e = 0; e < NM; ++e) {
-                Lin.re[e] = Tm.re[e] + vo.re[e];
-                Lin.im[e] = Tm.im[e] + vo.im[e];
-            }
-        } else {
-            Lin = vo;
-        }
-    }
+    traj_affine_suffix(Lin, Q, bvec, ln, s_q, s_v);
     // ---------------------------------------------------------------- 6: the true costates, the traces
     walk(Lin, true);
 }
@@ -401,18 +298,9 @@ hipError_t run_trajectory_vjp(int n, const SweepParams &p, hipStream_t stream)
 {
     if (p.vjp_only == 2)
         return vjp_launch_total(p, stream);
-    switch (n * 8 + p.vjp_m) {
-    case 2 * 8 + 1: return vjp_launch_nm<2, 1>(p, stream);
-    case 2 * 8 + 2: return vjp_launch_nm<2, 2>(p, stream);
-    case 3 * 8 + 1: return vjp_launch_nm<3, 1>(p, stream);
-    case 3 * 8 + 2: return vjp_launch_nm<3, 2>(p, stream);
-    case 3 * 8 + 3: return vjp_launch_nm<3, 3>(p, stream);
-    case 4 * 8 + 1: return vjp_launch_nm<4, 1>(p, stream);
-    case 4 * 8 + 2: return vjp_launch_nm<4, 2>(p, stream);
-    case 4 * 8 + 3: return vjp_launch_nm<4, 3>(p, stream);
-    case 4 * 8 + 4: return vjp_launch_nm<4, 4>(p, stream);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_nm(n, p.vjp_m, [&](auto N, auto M) {
+        return vjp_launch_nm<decltype(N)::value, decltype(M)::value>(p, stream);
+    });
 }
 
 }  // namespace grape
