@@ -875,10 +875,12 @@ int grape_get_kernel_names(const grape_ctx *ctx, char *buf, int32_t capacity);
  * the grouped ncclAllReduce + publication), out[4] waiting for [G, F], out[5] the whole call.  out: double[6]. */
 int grape_get_group_timing(grape_ctx *ctx, double *out, int32_t reset);
 
-/* Diagnostic (GRAPE_FLAG_PHASE_STAMPS): the stamps of the last evaluation, 8 uint64 per wave,
+/* Diagnostic (GRAPE_FLAG_PHASE_STAMPS): the stamps of the last evaluation, 10 uint64 per wave,
  * waves ordered (member, wave-in-member): [0..4] shader clock at start / after propagators /
  * after scan / after forward sweep / end, [5],[6] 100 MHz real-time counter at start / end,
- * [7] where the wave ran: HW_REG_XCC_ID << 32 | HW_REG_HW_ID.
+ * [7] where the wave ran: HW_REG_XCC_ID << 32 | HW_REG_HW_ID, [8],[9] real-time counter and shader
+ * clock at kernel entry, in front of the prologue that stages the operators ([0] and [5] are taken
+ * behind it; lane-pair kernel only, 0 from the lane kernel).
  * out: host uint64[capacity]; *count receives the number of values available. */
 int grape_get_phase_stamps(grape_ctx *ctx, uint64_t *out, int64_t capacity, int64_t *count);
 

@@ -92,6 +92,8 @@ struct grape_ctx {
     uint64_t bytes = 0;
     // device
     double2 *d_ops = nullptr;
+    double2 *d_pair_img = nullptr;             // lane-pair sweep: the members' image records, rebuilt wherever d_ops is written
+    bool pair_image_env = true;                // GRAPE_PAIR_IMAGE=0: no records, the sweep builds the images in its prologue
     double *d_wts = nullptr;
     double *d_x = nullptr;
     double *d_fg = nullptr;
@@ -645,7 +647,7 @@ static void free_all(grape_ctx *c)
     if (c->ev_dev) (void)hipEventDestroy(c->ev_dev);
     if (c->ev_done) (void)hipEventDestroy(c->ev_done);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    (void)hipFree(c->d_ops); (void)hipFree(c->d_wts); (void)hipFree(c->d_x); (void)hipFree(c->d_fg);
+    (void)hipFree(c->d_ops); (void)hipFree(c->d_pair_img); (void)hipFree(c->d_wts); (void)hipFree(c->d_x); (void)hipFree(c->d_fg);
     (void)hipFree(c->d_props); (void)hipFree(c->d_states); (void)hipFree(c->d_costates); (void)hipFree(c->d_zphi);
     (void)hipFree(c->d_ctrl_scale);
     (void)hipFree(c->d_member_out); (void)hipFree(c->d_partial); (void)hipFree(c->d_stamps); (void)hipFree(c->d_block_out); (void)hipFree(c->d_xg_scratch);
@@ -967,6 +969,7 @@ static int create_shard(const grape_config *cfg, int dev, grape_ctx **out)
         c->direct_publish = !(dp && dp[0] == '0');
         c->mf_publish = !env_off("GRAPE_MF_PUBLISH");
         c->pair_ah_env = !env_off("GRAPE_PAIR_AH");
+        c->pair_image_env = !env_off("GRAPE_PAIR_IMAGE");
     }
     {
         // x upload path.  Default: if the device exposes its memory to the CPU (large BAR), the host
@@ -2342,6 +2345,21 @@ extern "C" int grape_set_operators(grape_ctx *c, const double *A, const double *
         if (int rc = grow(c, &c->d_states, &c->states_bytes, sizeof(double2) * c->ws_elems * ws_batch(c), who, "the forward states")) return rc;
     }
     HIP_TRY(c, hipMemcpy(c->d_ops, packed.data(), sizeof(double) * packed.size(), hipMemcpyHostToDevice));
+    if (c->family == 0 && c->pair && c->pair_image_env) {   // the lane-pair sweep's image records follow every upload
+        const size_t ib = sizeof(double2) * (size_t)grape::pair_image_d2(c->cfg.n, c->cfg.n_controls) * E;
+        if (!c->d_pair_img) {
+            c->bytes += ib;
+            HIP_TRY(c, hipMalloc((void **)&c->d_pair_img, ib));
+        }
+        SweepParams ip{};
+        ip.ops = c->d_ops;
+        ip.pair_img = c->d_pair_img;
+        ip.img_only = 1;
+        ip.K = c->cfg.n_controls;
+        ip.E = c->cfg.n_ensemble;
+        HIP_TRY(c, grape::launch_sweep_pair(c->cfg.n, 0, 0, ip, nullptr));
+        HIP_TRY(c, hipStreamSynchronize(nullptr));
+    }
     HIP_TRY(c, hipMemcpy(c->d_wts, wts, sizeof(double) * E, hipMemcpyHostToDevice));
     c->h_wts.assign(wts, wts + E);
     c->ops_set = true;
@@ -2473,6 +2491,7 @@ static SweepParams sweep_params(const grape_ctx *c, const double *d_x, int n_x)
 {
     SweepParams p{};
     p.ops = c->d_ops;
+    p.pair_img = c->d_pair_img;
     p.x = d_x;
     p.wts = c->d_wts;
     p.MPB = c->MPB;
@@ -2838,6 +2857,7 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
         if (c->family == 0) {
             SweepParams q = p;
             q.ops = p.ops + (size_t)lo * (Kc + 3) * nn;
+            if (p.pair_img) q.pair_img = p.pair_img + (size_t)lo * grape::pair_image_d2(c->cfg.n, (int)Kc);
             q.wts = p.wts + lo;
             if (p.member_out) q.member_out = p.member_out + (size_t)lo * Qrow;
             q.block_out = p.block_out + (size_t)(lo / c->MPB) * Qrow;

@@ -101,7 +101,8 @@ constexpr int kMaxMflags = 1000;               // flags behind grape_ctx::h_flag
 // workgroups (= host flags) reduce_rows_mf_kernel publishes with for Q outputs x n_x control arrays; 0: not applicable
 int reduce_rows_mflags(int Q, int n_x);
 
-constexpr int kStampSlots = 8;   // [0..4] shader clock at phase boundaries, [5],[6] 100 MHz real time
+constexpr int kStampSlots = 10;  // [0..4] shader clock at phase boundaries, [5],[6] 100 MHz real time, [7] hardware ids,
+                                 // [8],[9] real time and shader clock at kernel entry (pair kernel; 0 elsewhere)
 
 // Device-side view of one context.  All complex data is interleaved double2 {re, im}.
 struct SweepParams {
@@ -246,7 +247,23 @@ struct SweepParams {
     int32_t jvp_ndir;
     int32_t jvp_multi;
     int64_t jvp_dir_xdot, jvp_dir_ydot, jvp_dir_xf, jvp_dir_w;
+    // Lane-pair sweep: the members' prebuilt image records (pair_image_d2, below), addressed like `ops` by the member's number
+    // inside the launch; the sweep's prologue copies the member's record instead of building the images from `ops`.
+    // nullptr (GRAPE_PAIR_IMAGE=0): it builds them.  launch_sweep_pair hands a launch with img_only set to pair_image_kernel
+    // INSTEAD of the sweep: it writes the E records at pair_img from the E members' operators at `ops` (K, E: the only other
+    // fields it reads) -- wherever those are uploaded.  (Appended.)
+    double2 *pair_img;
+    int32_t img_only;
 };
+// A member's image record: what the lane-pair sweep's prologue puts into LDS, laid out as the LDS holds it.
+//   [0, 2 PS)        both parity images of A', B'_c, B'_c^T, Xi, Xt, Xi Xt' (every mode but the anti-Hermitian sweep), pads zero
+//   [2 PS, 4 PS)     n = 4: the same with the anti-Hermitian sweep's gradient weights in place of the B'_c^T images
+//   then             the K + 1 one-norm bounds (doubles, rounded up to whole double2)
+// PS = (2 K + 4) n n / 2 + kParityPad double2 (kParityPad = 128 B = half an LDS row of 64 banks between the two parity images).
+constexpr int kParityPad = 8;
+constexpr int pair_image_ps(int n, int K) { return (2 * K + 4) * (n * (n / 2)) + kParityPad; }
+constexpr int pair_image_nrm_at(int n, int K) { return (n == 4 ? 4 : 2) * pair_image_ps(n, K); }
+constexpr int pair_image_d2(int n, int K) { return pair_image_nrm_at(n, K) + (K + 2) / 2; }     // double2 per member
 // grape_eval_jvp_multi: the directions trajectory_jvp_multi_kernel (trajectory_jvp_kernel<n, m, ..., DB> at DB > 1) carries
 // per launch (DB; chosen per shape from the register file), its workgroup size limit (all n: 512 registers per lane), and whether the shape
 // dispatches to it by default (where it measured faster per direction than the single kernel; GRAPE_JVP_MULTI=0/1 forces)

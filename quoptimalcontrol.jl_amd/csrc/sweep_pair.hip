@@ -52,7 +52,6 @@ namespace grape {
 // part of z M_t alone (phase D, below) -- chosen by the host in place of PMODE_UNITARY (GRAPE_PAIR_AH=0 keeps that one)
 enum { PMODE_GENERAL = 0, PMODE_GENERAL_KEEPL = 1, PMODE_UNITARY = 2, PMODE_UNITARY_AH = 3 };
 constexpr int kAhImage = 5;            // double2 slots per control of the anti-Hermitian sweep's gradient image (n = 4)
-constexpr int kParityPad = 8;          // double2 slots (128 B = half an LDS row of 64 banks) between a member's two parity images
 
 // global element index i + j n of local element (r, jl) as seen by a lane of parity q
 template <int N>
@@ -321,11 +320,18 @@ GRAPE_DEV void pwrite_gradient_antih(double *out, const double2 *s_img, int K, c
 // VEC (general flow, left multiplication, n = 4, at most kVecSlices slices per lane): the states are n x 1 -- column 0 of the
 // zero-padded matrices -- and the sweep back runs on VECTORS (phase D, below); phase A then stores no in-chunk prefixes.
 constexpr int kVecSlices = 16;
-template <int N, int SAND, int MODE, int MAXT, bool XGLDS, bool DUMPW = false, bool VEC = false>
-__global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restrict__ ops_all,
-                                                          const double *__restrict__ x_all,
-                                                          const double *__restrict__ wts_all,
-                                                          const SweepParams p)
+
+// (The member's prebuilt image record, SweepParams::pair_img: layout and sizes in grape_kernels.hpp, pair_image_d2.)
+// The copying prologue keeps every load of a lane in registers in front of its one wait: at most kPairXBatch passes over x
+// (K N <= kPairXBatch LT) and kPairImgBatch over the record (2 PS <= kPairImgBatch LT); the launcher sends larger shapes to
+// sweep_pair_build_kernel
+constexpr int kPairXBatch = 16, kPairImgBatch = 4;
+
+// IMG: the prologue copies the member's prebuilt image record (one wait, one barrier); !IMG: it builds the images from the
+// operators itself (the form before the record existed: GRAPE_PAIR_IMAGE=0, and the shapes beyond the copy's register batch)
+template <int N, int SAND, int MODE, int MAXT, bool XGLDS, bool DUMPW, bool VEC, bool IMG>
+GRAPE_DEV void sweep_pair_body(const double2 *__restrict__ ops_all, const double *__restrict__ x_all,
+                               const double *__restrict__ wts_all, const SweepParams &p)
 {
     constexpr int NN = N * N, NC = N / 2, NE = N * NC;
     constexpr int MAXW = MAXT / 64;
@@ -343,6 +349,12 @@ __global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restr
     //               s_F    MPB double
     extern __shared__ double2 s_dyn[];
     double2(*s_tot)[MAXW][NN] = reinterpret_cast<double2(*)[MAXW][NN]>(s_dyn);
+    // stamped builds: both counters at kernel entry, kept in scalar registers across the prologue (stored with st[5] below)
+    unsigned long long t_in_real = 0, t_in_cyc = 0;
+    if (p.stamps) {
+        t_in_real = __builtin_amdgcn_s_memrealtime();
+        t_in_cyc = __builtin_readcyclecounter();
+    }
 
     const int LT = p.LT, W = LT >> 6, CH = LT >> 1;
     const int mb = __builtin_amdgcn_readfirstlane(threadIdx.x / LT);   // member within the block
@@ -387,6 +399,37 @@ __global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restr
         if (hi)
             __builtin_amdgcn_s_setprio(2);
     }
+    if constexpr (IMG) {
+        // One round trip: every load of the lane -- its passes over x and its share of the member's image record -- is issued
+        // before the first wait; then the LDS writes and one barrier.  No branches: an index past the end is clamped to the last
+        // element, for the load AND the write -- such lanes store the value the element's own lane stores, where it stores it.
+        const double *__restrict__ xsrc = x_all + (size_t)xi * K * Nsl;
+        const int KNs = K * Nsl, REC = 2 * PS;
+        const double2 *__restrict__ rec0 = p.pair_img + (size_t)kl * pair_image_d2(N, K);
+        const double2 *__restrict__ rec = rec0 + (AH ? REC : 0);
+        const double *__restrict__ rnrm = reinterpret_cast<const double *>(rec0 + pair_image_nrm_at(N, K));
+        double v[kPairXBatch];
+        d2v im[kPairImgBatch];                        // (plain vectors: the array stays in registers)
+        const int sk1 = SK == 1 ? -1 : 0;             // S K = 1: sk_magic wraps to 1, __umulhi gives 0 and the chunk of q is q itself
+#pragma unroll
+        for (int u = 0; u < kPairImgBatch; ++u)
+            im[u] = reinterpret_cast<const d2v *>(rec)[min(u * LT + L, REC - 1)];
+        const double nr = rnrm[min(L, K)];
+#pragma unroll
+        for (int u = 0; u < kPairXBatch; ++u)
+            v[u] = xsrc[min(u * LT + L, KNs - 1)];
+        __builtin_amdgcn_sched_barrier(0);            // (no LDS write, with its wait, moves up between the loads)
+#pragma unroll
+        for (int u = 0; u < kPairImgBatch; ++u)        // in the order the loads went out
+            reinterpret_cast<d2v *>(s_ops)[min(u * LT + L, REC - 1)] = im[u];
+        s_nrm[min(L, K)] = nr;
+#pragma unroll
+        for (int u = 0; u < kPairXBatch; ++u) {
+            const int q = min(u * LT + L, KNs - 1);
+            s_xg[q + (int)__umulhi((unsigned)q, magic) + (q & sk1)] = v[u];              // q + chunk_of(q) without its branch
+        }
+        __syncthreads();
+    } else {
     {
         const double *__restrict__ xsrc = x_all + (size_t)xi * K * Nsl;
         const int KNs = K * Nsl;
@@ -472,6 +515,7 @@ __global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restr
         s_nrm[L] = best;
     }
     __syncthreads();
+    }
     const double2 *sA = s_ops + (size_t)par * PS;               // my parity's images
     const double2 *sB = sA + NE;
     const double2 *sBT = sA + (size_t)(1 + K) * NE;
@@ -495,9 +539,12 @@ __global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restr
                                 (unsigned)((1 - par) * NC + par * NC * N) * p_rowb + (unsigned)ch * 16u};
     double2 *__restrict__ const p_Pk = p.props + (size_t)k * (GRAPE_PLAYOUT ? 1 : S) * NN * stride;
     unsigned long long *__restrict__ st =
-        p.stamps ? p.stamps + ((size_t)k * W + wave) * kStampSlots : nullptr;
-    if (st && lane == 0)
+        p.stamps ? p.stamps + ((size_t)k * W + __builtin_amdgcn_readfirstlane(wave)) * kStampSlots : nullptr;   // (a scalar pointer)
+    if (st && lane == 0) {
+        st[8] = t_in_real;
+        st[9] = t_in_cyc;
         st[5] = __builtin_amdgcn_s_memrealtime();
+    }
     pstamp(st, 0);
 
     // ---------------------------------------------------------------- phase A
@@ -1277,6 +1324,122 @@ __global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restr
     }
 }
 
+// the product kernel: the prologue copies the prebuilt record.  (!XGLDS -- x and the gradient staged in global scratch, the
+// shapes with many slices per lane: the x scatter is a pass of global stores there and the prologue a small part of a long
+// kernel; it keeps the building prologue.)
+template <int N, int SAND, int MODE, int MAXT, bool XGLDS, bool DUMPW = false, bool VEC = false>
+__global__ __launch_bounds__(MAXT) void sweep_pair_kernel(const double2 *__restrict__ ops_all,
+                                                          const double *__restrict__ x_all,
+                                                          const double *__restrict__ wts_all,
+                                                          const SweepParams p)
+{
+    sweep_pair_body<N, SAND, MODE, MAXT, XGLDS, DUMPW, VEC, XGLDS>(ops_all, x_all, wts_all, p);
+}
+
+// the same sweep with the images built in the prologue
+template <int N, int SAND, int MODE, int MAXT, bool XGLDS, bool DUMPW = false, bool VEC = false>
+__global__ __launch_bounds__(MAXT) void sweep_pair_build_kernel(const double2 *__restrict__ ops_all,
+                                                                const double *__restrict__ x_all,
+                                                                const double *__restrict__ wts_all,
+                                                                const SweepParams p)
+{
+    sweep_pair_body<N, SAND, MODE, MAXT, XGLDS, DUMPW, VEC, false>(ops_all, x_all, wts_all, p);
+}
+
+// One workgroup of 64 lanes per member writes the member's image record (layout: pair_image_d2 above) from its operators,
+// with the arithmetic of the building prologue, expression by expression: the copy leaves in LDS the bits that prologue leaves.
+template <int N>
+__global__ __launch_bounds__(64) void pair_image_kernel(const double2 *__restrict__ ops_all, double2 *__restrict__ img_all,
+                                                        int K, int E)
+{
+    constexpr int NN = N * N, NC = N / 2, NE = N * NC;
+    constexpr bool AH = (N == 4);
+    const int kl = blockIdx.x, L = threadIdx.x, LT = blockDim.x;
+    if (kl >= E)
+        return;
+    const int NM = 2 * K + 4, PS = pair_image_ps(N, K), REC = 2 * PS;
+    const double2 *__restrict__ ops = ops_all + (size_t)kl * (K + 3) * NN;
+    double2 *__restrict__ rec = img_all + (size_t)kl * pair_image_d2(N, K);
+    // one double of the anti-Hermitian sweep's gradient image (sweep_pair_body's building prologue)
+    auto ah_weight = [&](int q, int c, int sl) {
+        const int P0 = q * NC, Q0 = (1 - q) * NC;
+        int jj, ii;
+        double wt = 1.0;
+        if (sl < 2)       { jj = ii = P0 + sl; }
+        else if (sl < 4)  { jj = P0 + 1; ii = P0; wt = 2.0; }
+        else if (sl < 6)  { jj = P0; ii = Q0; }
+        else if (sl < 8)  { jj = P0 + 1; ii = Q0 + 1; }
+        else              { jj = P0 + 1; ii = Q0; wt = 2.0; }
+        const double2 b1 = ops[(size_t)(1 + c) * NN + jj + ii * N], b2 = ops[(size_t)(1 + c) * NN + ii + jj * N];
+        const double bsr = 0.5 * (b1.x - b2.x), bsi = 0.5 * (b1.y + b2.y);        // Bs[jj, ii]
+        const double v = sl < 2 ? -bsi : ((sl & 1) ? -wt * bsi : wt * bsr);
+        return v;
+    };
+    for (int idx = L; idx < REC; idx += LT) {
+        const int q = idx / PS, rem = idx - q * PS;
+        const int mat = rem / NE, e = rem - mat * NE;
+        double2 val = make_double2(0.0, 0.0), val_ah = val;             // (the pad between the parity images)
+        if (mat == 2 * K + 3) {                      // Xi Xt'
+            const double2 *__restrict__ gXi = ops + (size_t)(1 + K) * NN, *__restrict__ gXt = gXi + NN;
+            const int r = e % N, jl = e / N;
+            const int i = (((r / NC) ^ q) * NC) + (r % NC), j = q * NC + jl;
+            double sr = 0.0, si = 0.0;
+            for (int kk = 0; kk < N; ++kk) {
+                const double2 a = gXi[i + kk * N], b = gXt[j + kk * N];      // Xi[i,k] conj(Xt[j,k])
+                sr = fma(a.x, b.x, sr); sr = fma(a.y, b.y, sr);
+                si = fma(a.y, b.x, si); si = fma(-a.x, b.y, si);
+            }
+            val = val_ah = make_double2(sr, si);
+        } else if (mat < NM) {
+            const int r = e % N, jl = e / N;
+            const int i = (((r / NC) ^ q) * NC) + (r % NC), j = q * NC + jl;
+            int src;
+            if (mat <= K)            src = mat * NN + i + j * N;                 // A', B'_c
+            else if (mat <= 2 * K)   src = (mat - K) * NN + j + i * N;           // B'_c transposed
+            else                     src = (mat - K) * NN + i + j * N;           // Xi, Xt
+            val = val_ah = ops[src];
+            if (AH && mat > K && mat <= 2 * K) {     // the gradient weights lie where the B'_c^T images are, 2 kAhImage doubles per control
+                const int d0 = 2 * (rem - (1 + K) * NE);
+                val_ah = make_double2(0.0, 0.0);
+                if (d0 < K * 2 * kAhImage) {
+                    const int c = d0 / (2 * kAhImage), sl = d0 - c * (2 * kAhImage);
+                    val_ah = make_double2(ah_weight(q, c, sl), ah_weight(q, c, sl + 1));
+                }
+            }
+        }
+        rec[idx] = val;
+        if (AH)
+            rec[REC + idx] = val_ah;
+    }
+    if (L <= K) {                                    // one lane per generator: max column sum of |re| + |im|
+        double best = 0.0;
+        for (int q = 0; q < 2; ++q)
+            for (int jl = 0; jl < NC; ++jl) {
+                double cs = 0.0;
+                for (int r = 0; r < N; ++r) {
+                    const double2 v = ops[(size_t)L * NN + gelem<N>(q, r, jl)];
+                    cs += fabs(v.x) + fabs(v.y);
+                }
+                best = fmax(best, cs);
+            }
+        reinterpret_cast<double *>(rec + pair_image_nrm_at(N, K))[L] = best;
+    }
+}
+
+// img_only launches: the p.E records at p.pair_img from the members' operators at p.ops
+static hipError_t run_pair_image(int n, const SweepParams &p, hipStream_t stream)
+{
+    if (!p.pair_img || p.E < 1)
+        return hipErrorInvalidValue;
+    if (n == 2)
+        GRAPE_LAUNCH_AS("pair_image_kernel", pair_image_kernel<2>, dim3(p.E), dim3(64), 0, stream, p.ops, p.pair_img, p.K, p.E);
+    else if (n == 4)
+        GRAPE_LAUNCH_AS("pair_image_kernel", pair_image_kernel<4>, dim3(p.E), dim3(64), 0, stream, p.ops, p.pair_img, p.K, p.E);
+    else
+        return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
 template <int N>
 struct PairTraits;
 template <> struct PairTraits<2> { static constexpr int MAXT = 1024; };
@@ -1303,6 +1466,16 @@ size_t sweep_pair_lds_bytes(int n, int MPB, int LT, int S, int K, bool xg_in_lds
     return b;
 }
 
+// an instantiation's kernel with the building prologue: sweep_pair_kernel itself where it has no copying one (!XGLDS)
+template <int N, int SAND, int MODE, int MAXT, bool XGLDS, bool DUMPW, bool VEC>
+static auto pair_build_kernel()
+{
+    if constexpr (XGLDS)
+        return sweep_pair_build_kernel<N, SAND, MODE, MAXT, XGLDS, DUMPW, VEC>;
+    else
+        return sweep_pair_kernel<N, SAND, MODE, MAXT, XGLDS, DUMPW, VEC>;
+}
+
 template <int N, int SAND, int MODE, bool XGLDS>
 static hipError_t plaunch_one(const SweepParams &p0, hipStream_t stream)
 {
@@ -1324,40 +1497,33 @@ static hipError_t plaunch_one(const SweepParams &p0, hipStream_t stream)
             lds = with;
         }
     }
+    // the copying prologue where the context holds the image records and a lane's share of x and of the record fits its
+    // register batch; the building one otherwise
+    const bool copy = XGLDS && p.pair_img && (long long)p.K * p.N <= (long long)kPairXBatch * p.LT &&
+                      2 * pair_image_ps(N, p.K) <= kPairImgBatch * p.LT;
+    auto go = [&](auto kern_copy, auto kern_build, const char *name) -> hipError_t {
+        auto kern = copy ? kern_copy : kern_build;
+        if (lds > 64 * 1024) {
+            hipError_t e = ensure_dynamic_lds((const void *)kern, lds);
+            if (e != hipSuccess)
+                return e;
+        }
+        GRAPE_LAUNCH_AS(name, kern, grid, block, lds, stream, p.ops, p.x, p.wts, p);
+        return hipGetLastError();
+    };
     if constexpr (MODE == PMODE_UNITARY && SAND == 0) {
         if (p.dump_w1) {
-            auto kern_w = sweep_pair_kernel<N, SAND, MODE, MAXT, XGLDS, true>;
-            if (lds > 64 * 1024) {
-                hipError_t e = ensure_dynamic_lds((const void *)kern_w, lds);
-                if (e != hipSuccess)
-                    return e;
-            }
-            GRAPE_LAUNCH_AS("sweep_pair_kernel", kern_w, grid, block, lds, stream, p.ops, p.x, p.wts, p);
-            return hipGetLastError();
+            return go(sweep_pair_kernel<N, SAND, MODE, MAXT, XGLDS, true>, pair_build_kernel<N, SAND, MODE, MAXT, XGLDS, true, false>(), "sweep_pair_kernel");
         }
     }
     if (p.dump_w1)
         return hipErrorInvalidConfiguration;
     if constexpr (N == 4 && SAND == 0 && MODE == PMODE_GENERAL && XGLDS) {
         if (p.vec && p.S <= kVecSlices) {                    // n x 1 states: the sweep back on vectors
-            auto kern_v = sweep_pair_kernel<N, SAND, MODE, MAXT, XGLDS, false, true>;
-            if (lds > 64 * 1024) {
-                hipError_t e = ensure_dynamic_lds((const void *)kern_v, lds);
-                if (e != hipSuccess)
-                    return e;
-            }
-            GRAPE_LAUNCH_AS("sweep_pair_vec_kernel", kern_v, grid, block, lds, stream, p.ops, p.x, p.wts, p);
-            return hipGetLastError();
+            return go(sweep_pair_kernel<N, SAND, MODE, MAXT, XGLDS, false, true>, pair_build_kernel<N, SAND, MODE, MAXT, XGLDS, false, true>(), "sweep_pair_vec_kernel");
         }
     }
-    auto kern = sweep_pair_kernel<N, SAND, MODE, MAXT, XGLDS>;
-    if (lds > 64 * 1024) {
-        hipError_t e = ensure_dynamic_lds((const void *)kern, lds);
-        if (e != hipSuccess)
-            return e;
-    }
-    GRAPE_LAUNCH_AS("sweep_pair_kernel", kern, grid, block, lds, stream, p.ops, p.x, p.wts, p);
-    return hipGetLastError();
+    return go(sweep_pair_kernel<N, SAND, MODE, MAXT, XGLDS>, pair_build_kernel<N, SAND, MODE, MAXT, XGLDS, false, false>(), "sweep_pair_kernel");
 }
 
 template <int N, int SAND>
@@ -1387,6 +1553,8 @@ static hipError_t plaunch_ns(int mode, const SweepParams &p, hipStream_t stream)
 
 hipError_t launch_sweep_pair(int n, int sandwich, int mode, const SweepParams &p, hipStream_t stream)
 {
+    if (p.img_only)                                  // grape_set_operators: the members' image records (pair_image_kernel, above)
+        return run_pair_image(n, p, stream);
     if (p.fom_only)                                  // grape_eval_fom: the forward-only kernel (fom_small.hip)
         return launch_fom_small(n, sandwich, mode, true, p, stream);
     if (p.rc_only)                                   // grape_set_running_cost: the kernels behind the sweep (running_cost.hip)

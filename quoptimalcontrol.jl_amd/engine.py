@@ -935,12 +935,14 @@ class GrapeEngine:
         return (sw(P), sw(X), sw(Lc)) if costates else (sw(P), sw(X))
 
     def phase_stamps(self):
-        """(E*W, 8) uint64 stamps of the last evaluation (FLAG_PHASE_STAMPS)."""
+        """(E*W, 10) uint64 stamps of the last evaluation (FLAG_PHASE_STAMPS): columns 0..4 shader clock at the phase
+        boundaries, 5 and 6 the 100 MHz counter behind the prologue and at the end, 7 hardware ids, 8 and 9 the 100 MHz
+        counter and the shader clock at kernel entry (lane-pair kernel; 0 from the lane kernel)."""
         cnt = C.c_int64()
         self._check(self._lib.grape_get_phase_stamps(self._h, None, 0, C.byref(cnt)))
         out = np.empty(cnt.value, dtype=np.uint64)
         self._check(self._lib.grape_get_phase_stamps(self._h, _p(out), cnt.value, C.byref(cnt)))
-        return out.reshape(-1, 8)
+        return out.reshape(-1, 10)
 
     def group_timing(self, reset=False):
         """multi-device contexts: mean host-side microseconds per grape_eval since the last reset."""

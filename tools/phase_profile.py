@@ -43,6 +43,15 @@ out["percentiles_0_10_50_90_100"] = {
     "wave_end_ns_after_first_start": pc((st[:, 6] - st[:, 5].min()) * 10.0),
     "wave_real_ns": pc(real), "wave_total_cycles": pc(tot),
     **{n: pc(d[:, i]) for i, n in enumerate(names)}}
+if st.shape[1] > 9 and st[:, 8].min() > 0:          # entry stamps (lane-pair kernel): everything in front of phase A
+    pro_ns = (st[:, 5] - st[:, 8]) * 10.0           # 100 MHz counter: 10 ns steps
+    pro_cy = st[:, 0] - st[:, 9]
+    out["prologue"] = {"ns_median": float(np.median(pro_ns)), "ns_p100": float(pro_ns.max()),
+                       "cycles_median": float(np.median(pro_cy)), "cycles_p100": float(pro_cy.max()),
+                       "kernel_span_from_entry_ns": float((st[:, 6].max() - st[:, 8].min()) * 10.0)}
+    out["percentiles_0_10_50_90_100"]["prologue_ns"] = pc(pro_ns)
+    out["percentiles_0_10_50_90_100"]["prologue_cycles"] = pc(pro_cy)
+    out["percentiles_0_10_50_90_100"]["wave_entry_ns_after_first"] = pc((st[:, 8] - st[:, 8].min()) * 10.0)
 hw = eng_stamps_raw[:, 7]
 xcc = ((hw >> np.uint64(32)) & np.uint64(0xF)).astype(int)
 out["per_xcc_wave_total_cycles_median"] = {int(x): float(np.median(tot[xcc == x])) for x in sorted(set(xcc.tolist()))}
