@@ -694,6 +694,60 @@ int grape_eval_jvp_multi(grape_ctx *ctx, const double *x, int32_t n_dir, const d
 int grape_eval_jvp_multi_device(grape_ctx *ctx, const double *d_x, int32_t n_dir, const double *d_xdot, int32_t n_obs,
                                 int32_t per_member, const double *d_O, double *d_ydot, double *d_Xdot_final, void *stream);
 
+/* ABI v8 (additive).  Second-order products along the trajectory: the directional derivative of grape_eval_vjp's program.
+ * Given a direction xdot in control space and the tangent (ybar_dot, Xbar_final_dot) of the cotangents it returns how the
+ * pull-back G = grape_eval_vjp(ybar, Xbar_final) moves to first order -- for a loss l(y(x), X_N(x)) with ybar = dl/dy,
+ * ybar_dot = l'' (ydot, Xdot_N) and (ydot, Xdot_N) from grape_eval_jvp this is the Hessian-vector product H_l xdot, what a
+ * Newton-CG or trust-region step on a custom loss and a curvature analysis need.
+ *   x, n_obs, per_member, O, ybar, Xbar_final   exactly as in grape_eval_vjp (same layouts, same cotangent convention)
+ *   xdot            host f64, the shape and coordinates of x, as in grape_eval_jvp
+ *   ybar_dot        host c128 (N+1, n_obs, E), the layout of ybar; NULL: zero
+ *   Xbar_final_dot  host c128 (n, m, E), the layout of Xbar_final; NULL: zero (each alone or both)
+ *   Gdot            host f64 (K, N), or (K, M) in parameter mode
+ * With B'_kc = -i dt B_kc, V_ks = sum_c xdot_phys[c,s] B'_kc, the propagators P and states X of the physical pulse and the
+ * costate Lam of grape_eval_vjp for (ybar, Xbar_final):
+ *   Xdot_0  = 0 ,    Xdot_{s+1} = P_s Xdot_s + V_s X_{s+1}                                          (grape_eval_jvp's tangent)
+ *   Lamd_N  = Xbar_final_dot + sum_j ybar_dot[N,j] O_j
+ *   Lamd_s  = P_s' ( Lamd_{s+1} + V_s' Lam_{s+1} ) + sum_j ybar_dot[s,j] O_j                       s = N-1 .. 1
+ *   Gdot[c,t] = sum_k Re tr( Lamd_{k,t+1}' B'_kc X_{k,t+1} ) + Re tr( Lam_{k,t+1}' B'_kc Xdot_{k,t+1} )      t = 0 .. N-1
+ * FIRST ORDER in dt like the pair it joins: Gdot is exactly the derivative of grape_eval_vjp's G under the rule that pair uses,
+ * Pdot_s = V_s P_s (central differences of the VJP recurrence over P_s(eps) = expm(eps V_s) P_s agree to the difference
+ * quotient's own error); against the true directional derivative of G the deviation falls by ~4 per 4x in N.  With xdot = 0
+ * the result is grape_eval_vjp(ybar_dot, Xbar_final_dot).  The same-slice block of this operator is NOT symmetric: it holds
+ * B_c B_d, not the symmetrised product (the rule differentiates P_s once more on the left only).  That changes the rate of a
+ * Newton iteration, not its fixed point.
+ * Gdot carries no ensemble weight, penalty, running cost or risk.  Under grape_set_basis xdot_phys is the tangent expansion
+ * grape_eval_jvp uses and Gdot goes through the projection grape_eval_vjp uses (basis_project_kernel).
+ * The call runs ONE evaluation of x exactly as the context is configured and discards its [G, F]; behind the sweep of every
+ * member block trajectory_hvp_kernel reads the stored propagators -- one workgroup per member, one lane per time chunk -- and
+ * vjp_sum_kernel adds the members' rows in grape_eval_vjp's fixed tree.  Blocking, ordered behind an in-flight
+ * grape_eval_device; afterwards grape_get_kernel_names includes trajectory_hvp_kernel.  An eval -> hvp -> eval sequence returns
+ * the first evaluation's bits; results are bitwise reproducible call to call; a member-chunked context returns the unchunked
+ * context's bits; a standing running cost, penalties or risk do not change a bit.  Every operation is linear in the triple
+ * (xdot, ybar_dot, Xbar_final_dot): twice the triple returns twice the bits, the negated triple the negated bits.
+ * Served: the contexts grape_eval_vjp serves, refused with its reasons first.  Two refusals of this call alone follow them,
+ * GRAPE_ERR_UNSUPPORTED: grape_set_bounds in force ("bounds": the saturation's second derivative and the first-order G would
+ * enter) and grape_set_trajectory_derivative(GRAPE_TRAJ_EXACT) in force ("trajectory_derivative": a second Frechet derivative
+ * would be needed).
+ * GRAPE_ERR_INVALID_ARG: null x, xdot or Gdot; ybar and Xbar_final both NULL; n_obs outside 0..16; n_obs = 0 with a non-NULL
+ * ybar or ybar_dot; n_obs > 0 with a NULL O; per_member other than 0 or 1; a non-finite entry of a host array ("not finite").
+ * Before grape_set_operators: GRAPE_ERR_NOT_READY.  After any refusal the context evaluates exactly as before. */
+int grape_eval_hvp(grape_ctx *ctx, const double *x, const double *xdot, int32_t n_obs, int32_t per_member, const double *O,
+                   const double *ybar, const double *Xbar_final, const double *ybar_dot, const double *Xbar_final_dot,
+                   double *Gdot);
+
+/* ABI v8 (additive).  The device form of grape_eval_hvp under the rules of grape_eval_vjp_device / grape_eval_jvp_device: every
+ * array lives in device memory of the context's GPU, the call is asynchronous on `stream`, nothing is synchronised; device
+ * arrays are NOT checked for non-finite entries, everything else is validated as in the host form.  Results are bit for bit
+ * the host form's.  With a non-NULL d_x on a context that is not member-chunked the call sets the "trajectory valid" flag;
+ * d_x = NULL runs along the stored trajectory of the last device form with no sweep and the same bits, and keeps the flag set,
+ * so the other reuse calls may follow (a Newton-CG inner loop: one grape_eval_jvp_device(NULL) and one grape_eval_hvp_device(NULL)
+ * per iteration at one linearisation point).  With the flag clear, or on a member-chunked context, GRAPE_ERR_NOT_READY with
+ * grape_eval_vjp_device's messages. */
+int grape_eval_hvp_device(grape_ctx *ctx, const double *d_x, const double *d_xdot, int32_t n_obs, int32_t per_member,
+                          const double *d_O, const double *d_ybar, const double *d_Xbar_final, const double *d_ybar_dot,
+                          const double *d_Xbar_final_dot, double *d_Gdot, void *stream);
+
 /* ABI v8 (additive).  The derivative rule of the pull-back and the push-forward along the trajectory: all six entry points --
  * grape_eval_vjp, grape_eval_vjp_device, grape_eval_jvp, grape_eval_jvp_device and the d_x = NULL reuse forms of both device
  * calls.  GRAPE_TRAJ_FIRST_ORDER (the default) takes dP_t/dx[c,t] as (-i dt B_c) P_t, as documented above.  GRAPE_TRAJ_EXACT

@@ -22,7 +22,12 @@ the transpose of a first-order linearisation, not of the forward's true derivati
 eng.set_trajectory_derivative("exact") the backward and the jvp differentiate the propagators the forward used, exactly:
 gradcheck passes and a quasi-Newton solve on a custom loss converges to its own gradient tolerance.
 
-trajectory_device is the same for a workflow that lives on the GPU: x, y, X_final, the loss and x.grad are CUDA tensors on the
+Second order: trajectory(..., twice=True) makes the backward differentiable as well (GrapeEngine.observe_hvp, grape_eval_hvp),
+so torch.autograd.grad(..., create_graph=True) and torch.autograd.functional.hvp give Hessian-vector products of a loss on
+(y, X_final) -- first order in dt, engines without bounds in the first-order derivative mode.  twice=False (the default) is the
+once-differentiable function it always was.
+
+trajectory_device is the same for a workflow that lives on the GPU (once differentiable): x, y, X_final, the loss and x.grad are CUDA tensors on the
 engine's device, the read-out and the pull-back run on torch's current stream (GrapeEngine.observe_device /
 observe_vjp_device) and nothing crosses to the host.
 """
@@ -67,15 +72,108 @@ class _Trajectory(torch.autograd.Function):
         return torch.from_numpy(out)
 
 
-def trajectory(engine, x, ops, per_member=False, final=True):
+def _np(t):
+    return None if t is None else np.array(t.detach().resolve_conj().numpy(), copy=True)
+
+
+class _TrajectoryHVP(torch.autograd.Function):
+    """The backward of _TrajectoryVJP as a function of its upstream w (and of x, ybar, xbar, in which it is not differentiated
+    again): (observe_hvp(x, xdot=w, ybar, xbar), observe_jvp(x, w)) -- linear in w.  torch.autograd.functional.hvp
+    differentiates a backward with respect to its upstream (the double-backward trick), so this has a backward of its own:
+    for upstream (u_x, u_y, u_X) the gradient with respect to w is observe_hvp(x, xdot=u_x, ybar, xbar, ybar_dot=u_y,
+    xbar_final_dot=u_X) -- J' (u_y, u_X) exactly, and the curvature operator applied to u_x AS IT STANDS, where the transpose
+    belongs: the operator of grape_eval_hvp is symmetric up to its same-slice block (first order in dt, include/grape_hip.h)."""
+
+    @staticmethod
+    def forward(ctx, x, w, ybar, xbar, engine, ops, per_member):
+        xn, wn, yb, xb = _np(x), _np(w), _np(ybar), _np(xbar)
+        ctx.engine, ctx.ops, ctx.per_member = engine, ops, per_member
+        ctx.xn, ctx.yb, ctx.xb = xn, yb, xb
+        ctx.set_materialize_grads(False)
+        gx = engine.observe_hvp(xn, wn, ops, ybar=yb, xbar_final=xb, per_member=per_member)
+        yd, Xd = engine.observe_jvp(xn, wn, ops, per_member=per_member, final=True)
+        return torch.from_numpy(gx), torch.from_numpy(yd), torch.from_numpy(Xd)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, ux, uy, uX):
+        if ux is None and uy is None and uX is None:
+            return None, None, None, None, None, None, None
+        xd = np.zeros_like(ctx.xn) if ux is None else _np(ux)
+        gw = ctx.engine.observe_hvp(ctx.xn, xd, ctx.ops, ybar=ctx.yb, xbar_final=ctx.xb, ybar_dot=_np(uy), xbar_final_dot=_np(uX),
+                                    per_member=ctx.per_member)
+        return None, torch.from_numpy(gw), None, None, None, None, None
+
+
+class _TrajectoryVJP(torch.autograd.Function):
+    """G = observe_vjp(x; ybar, xbar) as a differentiable function of (x, ybar, xbar): the backward of _TrajectoryTwice.  Its
+    own backward, for an upstream w on G: observe_hvp(x, xdot=w, ybar, xbar) for x (grape_eval_hvp) and, G being linear in the
+    cotangents with the Jacobian's transpose, observe_jvp(x, w)'s (ydot, Xdot_final) for (ybar, xbar) -- through
+    _TrajectoryHVP, so that it can be differentiated with respect to w in turn."""
+
+    @staticmethod
+    def forward(ctx, x, ybar, xbar, engine, ops, per_member):
+        ctx.engine, ctx.ops, ctx.per_member = engine, ops, per_member
+        ctx.has_y, ctx.has_X = ybar is not None, xbar is not None
+        ctx.save_for_backward(x, *[t for t in (ybar, xbar) if t is not None])
+        return torch.from_numpy(engine.observe_vjp(_np(x), ops, ybar=_np(ybar), xbar_final=_np(xbar), per_member=per_member))
+
+    @staticmethod
+    def backward(ctx, w):
+        if w is None:
+            return None, None, None, None, None, None
+        saved = list(ctx.saved_tensors)
+        x = saved.pop(0)
+        ybar = saved.pop(0) if ctx.has_y else None
+        xbar = saved.pop(0) if ctx.has_X else None
+        gx, gy, gX = _TrajectoryHVP.apply(x, w, ybar, xbar, ctx.engine, ctx.ops, ctx.per_member)
+        return gx, gy if ctx.has_y else None, gX if ctx.has_X else None, None, None, None
+
+
+class _TrajectoryTwice(torch.autograd.Function):
+    """_Trajectory whose backward is itself differentiable: it runs through _TrajectoryVJP, so a backward with
+    create_graph=True (torch.autograd.functional.hvp, Newton-CG) reaches grape_eval_hvp."""
+
+    @staticmethod
+    def forward(ctx, x, engine, ops, per_member, final):
+        xn = x.detach().numpy()
+        out = engine.observe(xn, ops, per_member=per_member, final=final)
+        y, Xf = out if final else (out, None)
+        ctx.engine, ctx.ops, ctx.per_member, ctx.final = engine, ops, per_member, final
+        ctx.xn = np.array(xn, copy=True)
+        ctx.save_for_backward(x)
+        ctx.set_materialize_grads(False)
+        y_t = torch.from_numpy(y)
+        if final:
+            return y_t, torch.from_numpy(Xf)
+        return y_t
+
+    @staticmethod
+    def backward(ctx, ybar, xbar=None):
+        if ybar is None and xbar is None:
+            return None, None, None, None, None
+        (x,) = ctx.saved_tensors
+        G = _TrajectoryVJP.apply(x, ybar, xbar, ctx.engine, ctx.ops, ctx.per_member)
+        return G, None, None, None, None
+
+    jvp = _Trajectory.jvp
+
+
+def trajectory(engine, x, ops, per_member=False, final=True, twice=False):
     """y (E, n_obs, N+1) complex128 and -- final=True -- X_final (E, n, m) of the pulse x, a CPU float64 tensor of the shape
     engine.eval takes, differentiable with respect to x.  ops as in GrapeEngine.observe (at least one probe); it is not
-    differentiated.  Returns (y, X_final), or y alone with final=False."""
+    differentiated.  Returns (y, X_final), or y alone with final=False.
+    twice=True makes the backward differentiable too (a second Function around observe_vjp whose backward is
+    GrapeEngine.observe_hvp / observe_jvp): torch.autograd.grad(..., create_graph=True) and torch.autograd.functional.hvp work,
+    first order in dt like everything here.  The engine must serve observe_hvp (no bounds, first-order trajectory derivative).
+    trajectory_device stays once-differentiable."""
     if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.device.type != "cpu":
         raise TypeError("trajectory: x must be a CPU float64 tensor")
     if ops is None:
         raise ValueError("trajectory: at least one probe is needed (GrapeEngine.observe(final=True) gives X_final alone)")
     ops = np.array(ops.detach().numpy() if isinstance(ops, torch.Tensor) else ops, dtype=np.complex128, copy=True)
+    if twice:
+        return _TrajectoryTwice.apply(x, engine, ops, bool(per_member), bool(final))
     return _Trajectory.apply(x, engine, ops, bool(per_member), bool(final))
 
 

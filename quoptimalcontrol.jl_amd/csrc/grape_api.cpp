@@ -253,7 +253,19 @@ struct grape_ctx {
     // grape_eval_jvp_multi: directions of the call in flight (0: the single call), each with the single call's arrays one
     // behind the other; jvp_multi: trajectory_jvp_multi_kernel where it serves the shape (GRAPE_JVP_MULTI, else the table)
     int jvp_ndir = 0, jvp_multi = 0;
-    int lds_cap = 0;                          // LDS bytes a workgroup of this device may hold (queried by the first device form)
+    // grape_eval_hvp (hvp.hip): behind the sweep of every member block of ONE evaluation, trajectory_hvp_kernel differentiates
+    // the pull-back along the caller's direction and vjp_sum_kernel adds the members' rows as it does for grape_eval_vjp.  The
+    // call is described by the pull-back's fields above (vjp_n, vjp_per_member, vjp_has_*, vjp_*_call, d_vjp_part / _g / _out)
+    // and the push-forward's direction (jvp_xdot_call, d_jvp_xdot, d_jvp_xphys and the tangent map); its own are the tangents
+    // of the cotangents and the scratch of the kernel: [X | Xdot] per slice (general flow) or per chunk (unitary flow).
+    bool hvp_on = false;
+    bool hvp_has_yd = false, hvp_has_xd = false;
+    double2 *d_hvp_ybd = nullptr;              // (N + 1, n_obs, E)
+    double2 *d_hvp_xbd = nullptr;              // (n, m, E)
+    double2 *d_hvp_xs = nullptr;
+    size_t hvp_ybd_bytes = 0, hvp_xbd_bytes = 0, hvp_xs_bytes = 0;
+    const double2 *hvp_ybd_call = nullptr, *hvp_xbd_call = nullptr;
+    int lds_cap = 0;                         // LDS bytes a workgroup of this device may hold (queried by the first device form)
     // The workspace holds the complete trajectory (every member's propagators, and the slope array of a pulse map) of the last
     // device form: grape_eval_vjp_device may pull back along it without a sweep (d_x == NULL).  Set by a successful device form
     // that ran an evaluation on a context that is not member-chunked; cleared by everything else that evaluates or changes a
@@ -667,6 +679,7 @@ static void free_all(grape_ctx *c)
     (void)hipFree(c->d_vjp_O); (void)hipFree(c->d_vjp_ybar); (void)hipFree(c->d_vjp_xbar); (void)hipFree(c->d_vjp_part); (void)hipFree(c->d_vjp_g); (void)hipFree(c->d_vjp_out);
     (void)hipFree(c->d_traj_w); (void)hipFree(c->d_traj_x);
     (void)hipFree(c->d_jvp_O); (void)hipFree(c->d_jvp_xdot); (void)hipFree(c->d_jvp_xphys); (void)hipFree(c->d_jvp_ydot); (void)hipFree(c->d_jvp_xf);
+    (void)hipFree(c->d_hvp_ybd); (void)hipFree(c->d_hvp_xbd); (void)hipFree(c->d_hvp_xs);
     (void)hipFree(c->d_basis_phi); (void)hipFree(c->d_basis_x0);
     (void)hipFree(c->d_bounds); (void)hipFree(c->d_slope);
     (void)hipFree(c->d_fom_member); (void)hipFree(c->d_fom_rows);
@@ -2717,6 +2730,45 @@ static SweepParams jvp_params(const grape_ctx *c, const SweepParams &q, int lo)
     return v;
 }
 
+// grape_eval_hvp: the scratch of trajectory_hvp_kernel behind the CURRENT workspace plan -- general flow: [X | Xdot] per slice
+// and member of a workspace block; unitary flow: three n x m blocks per chunk and member
+static int hvp_ensure(grape_ctx *c, const char *who)
+{
+    const bool back = c->unitary && grape::hvp_walks_back(c->cfg.n, c->m);
+    const size_t per_member = (back ? (size_t)3 : (size_t)2 * c->S) * c->CH * c->cfg.n * c->m;
+    return grow(c, &c->d_hvp_xs, &c->hvp_xs_bytes, sizeof(double2) * (size_t)c->Ec * per_member, who, "the states and tangents of the chunks");
+}
+
+// grape_eval_hvp: the launch of trajectory_hvp_kernel + vjp_sum_kernel for the members from `lo` on that `q` sweeps (or swept:
+// grape_eval_hvp_device's reuse) -- the pull-back's launch, first order, with the direction and the cotangents' tangents
+static SweepParams hvp_params(const grape_ctx *c, const SweepParams &q, int lo)
+{
+    SweepParams v = vjp_params(c, q, lo);
+    v.vjp_only = 0;
+    v.vjp_staged = 0;
+    v.traj_exact = 0;
+    v.hvp_only = 1;
+    v.vjp_n = (c->vjp_has_y || c->hvp_has_yd) ? c->vjp_n : 0;
+    v.hvp_xdot = pulse_map(c) ? c->d_jvp_xphys : c->jvp_xdot_call;
+    v.hvp_ybar_dot = c->hvp_has_yd ? c->hvp_ybd_call : nullptr;
+    v.hvp_xbar_dot = c->hvp_has_xd ? c->hvp_xbd_call : nullptr;
+    v.hvp_xs = c->d_hvp_xs;
+    return v;
+}
+
+// the two launches of a member block: the rows and their groups' sums, and behind the last block the groups' sums into the row
+static int hvp_launch(grape_ctx *c, const SweepParams &q, int lo, bool last, int mode, hipStream_t stream)
+{
+    SweepParams v = hvp_params(c, q, lo);
+    HIP_TRY(c, launch_small_family(c, 0, mode, v, stream));
+    if (last) {
+        v.hvp_only = 0;
+        v.vjp_only = 2;
+        HIP_TRY(c, launch_small_family(c, 0, mode, v, stream));
+    }
+    return GRAPE_OK;
+}
+
 // grape_eval_jvp_multi: the E_t images the exact mode keeps side by side (one per direction of a block of the multi kernel)
 static int jvp_exact_images(const grape_ctx *c)
 {
@@ -2785,8 +2837,12 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
         const int rc = rc_ensure(c);
         if (rc) return rc;
     }
-    if (c->vjp_on) {                                         // (the rows, and the states of the general flow)
+    if (c->vjp_on || c->hvp_on) {                            // (the rows, and the states of the general flow)
         const int rc = rc_ensure(c);
+        if (rc) return rc;
+    }
+    if (c->hvp_on) {
+        const int rc = hvp_ensure(c, "grape_eval_hvp");
         if (rc) return rc;
     }
     // GRAPE_TRAJ_EXACT: every evaluation that may leave a trajectory for the pull-back / push-forward (the read-out's device
@@ -2798,7 +2854,7 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
     }
     KernelLogScope log_scope(&c->kernel_log);
     if (keep_x) HIP_TRY(c, grape::launch_copy(d_x, c->d_traj_x, (int)KN(c), stream));
-    if (c->jvp_on && pulse_map(c)) {                         // (the expansion in front has written this evaluation's slope array)
+    if ((c->jvp_on || c->hvp_on) && pulse_map(c)) {          // (the expansion in front has written this evaluation's slope array)
         const int rc = jvp_tangent_map(c, stream);
         if (rc) return rc;
     }
@@ -2914,6 +2970,10 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
             if (c->jvp_on) {                                 // grape_eval_jvp: the direction of these members, pushed forward
                 SweepParams v = jvp_params(c, q, lo);
                 HIP_TRY(c, launch_small_family(c, 0, mode, v, stream));
+            }
+            if (c->hvp_on) {                                 // grape_eval_hvp: the pull-back of these members, differentiated
+                const int rc = hvp_launch(c, q, lo, lo + cnt == c->cfg.n_ensemble, mode, stream);
+                if (rc) return rc;
             }
             if (exact) {                                     // exact gradient + objective from the stored trajectory
                 grape::ExactParams xq{};
@@ -4147,6 +4207,218 @@ extern "C" int grape_eval_jvp_multi_device(grape_ctx *c, const double *d_x, int3
     if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_jvp_multi_device: null context");
     return eval_jvp_device(c, "grape_eval_jvp_multi_device", true, d_x, n_dir, d_xdot, n_obs, per_member, d_O, d_ydot, d_Xdot_final,
                            stream);
+}
+
+// ---- grape_eval_hvp: one evaluation + the directional derivative of the pull-back along its trajectory -----------------------
+// vjp_check's order with the two refusals of this entry point behind the context's own and the direction behind x
+static int hvp_check(grape_ctx *c, const std::string &who, const void *x, bool x_needed, const void *xdot, int32_t n_obs,
+                     int32_t per_member, const void *O, const void *ybar, const void *Xbar_final, const void *ybar_dot,
+                     const void *Gdot)
+{
+    if (const char *why = why_linearisation_not_served(c)) return fail(c, GRAPE_ERR_UNSUPPORTED, who + ": " + why);
+    if (c->bounds_on)
+        return fail(c, GRAPE_ERR_UNSUPPORTED, who + ": bounds are in force (grape_set_bounds): the second derivative of the "
+                                              "saturation and the first-order G would enter");
+    if (traj_exact(c))
+        return fail(c, GRAPE_ERR_UNSUPPORTED, who + ": trajectory_derivative = exact is in force (grape_set_trajectory_derivative): "
+                                              "that mode would need a second Frechet derivative");
+    if (!x && x_needed) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": x is null");
+    if (!xdot) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": xdot is null");
+    if (!Gdot) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": Gdot is null");
+    if (!ybar && !Xbar_final) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": ybar and Xbar_final are both null");
+    if (n_obs < 0 || n_obs > 16)
+        return fail(c, GRAPE_ERR_INVALID_ARG, who + ": n_obs = " + std::to_string(n_obs) + " (must be in 0..16)");
+    if (n_obs == 0 && ybar) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": n_obs = 0 with a non-null ybar");
+    if (n_obs == 0 && ybar_dot) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": n_obs = 0 with a non-null ybar_dot");
+    if (n_obs > 0 && !O) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": n_obs > 0 with a null O");
+    if (per_member != 0 && per_member != 1)
+        return fail(c, GRAPE_ERR_INVALID_ARG, who + ": per_member = " + std::to_string(per_member) + " (must be 0 or 1)");
+    if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, who + ": operators not set");
+    return GRAPE_OK;
+}
+
+extern "C" int grape_eval_hvp(grape_ctx *c, const double *x, const double *xdot, int32_t n_obs, int32_t per_member, const double *O,
+                              const double *ybar, const double *Xbar_final, const double *ybar_dot, const double *Xbar_final_dot,
+                              double *Gdot)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_hvp: null context");
+    const char *who = "grape_eval_hvp";
+    c->traj_valid = false;
+    if (int rc0 = hvp_check(c, who, x, true, xdot, n_obs, per_member, O, ybar, Xbar_final, ybar_dot, Gdot)) return rc0;
+    const size_t n = (size_t)c->cfg.n, m = (size_t)c->m, E = (size_t)c->cfg.n_ensemble, N = (size_t)c->cfg.n_slices;
+    const size_t n_O = n * m * (per_member ? E : 1) * (size_t)n_obs, n_y = (N + 1) * (size_t)n_obs * E, n_X = n * m * E;
+    const size_t kn = KN(c), kp = KP(c);
+    int rc = check_finite(c, O, 2 * n_O, who, "O", 2);
+    if (rc) return rc;
+    rc = check_finite(c, xdot, kp, who, "xdot");
+    if (rc) return rc;
+    if (ybar) rc = check_finite(c, ybar, 2 * n_y, who, "ybar", 2);
+    if (rc) return rc;
+    if (Xbar_final) rc = check_finite(c, Xbar_final, 2 * n_X, who, "Xbar_final", 2);
+    if (rc) return rc;
+    if (ybar_dot) rc = check_finite(c, ybar_dot, 2 * n_y, who, "ybar_dot", 2);
+    if (rc) return rc;
+    if (Xbar_final_dot) rc = check_finite(c, Xbar_final_dot, 2 * n_X, who, "Xbar_final_dot", 2);
+    if (rc) return rc;
+    // the direction's buffers are the device forms' too, and those do not block: nothing of them is in flight from here on
+    rc = drain(c, c);
+    if (rc) return rc;
+    if (ybar || ybar_dot) {
+        rc = grow(c, &c->d_vjp_O, &c->vjp_O_bytes, sizeof(double2) * n_O, who, "the probes");
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpy(c->d_vjp_O, O, sizeof(double2) * n_O, hipMemcpyHostToDevice));
+    }
+    if (ybar) {
+        rc = grow(c, &c->d_vjp_ybar, &c->vjp_ybar_bytes, sizeof(double2) * n_y, who, "the cotangents of the expectation values");
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpy(c->d_vjp_ybar, ybar, sizeof(double2) * n_y, hipMemcpyHostToDevice));
+    }
+    if (ybar_dot) {
+        rc = grow(c, &c->d_hvp_ybd, &c->hvp_ybd_bytes, sizeof(double2) * n_y, who, "the tangents of the expectation values' cotangents");
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpy(c->d_hvp_ybd, ybar_dot, sizeof(double2) * n_y, hipMemcpyHostToDevice));
+    }
+    if (Xbar_final) {
+        rc = grow(c, &c->d_vjp_xbar, &c->vjp_xbar_bytes, sizeof(double2) * n_X, who, "the cotangents of the final states");
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpy(c->d_vjp_xbar, Xbar_final, sizeof(double2) * n_X, hipMemcpyHostToDevice));
+    }
+    if (Xbar_final_dot) {
+        rc = grow(c, &c->d_hvp_xbd, &c->hvp_xbd_bytes, sizeof(double2) * n_X, who, "the tangents of the final states' cotangents");
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpy(c->d_hvp_xbd, Xbar_final_dot, sizeof(double2) * n_X, hipMemcpyHostToDevice));
+    }
+    rc = grow(c, &c->d_jvp_xdot, &c->jvp_xdot_bytes, sizeof(double) * kp, who, "the direction");
+    if (rc) return rc;
+    if (pulse_map(c)) {
+        rc = grow(c, &c->d_jvp_xphys, &c->jvp_xphys_bytes, sizeof(double) * kn, who, "the direction of the physical pulse");
+        if (rc) return rc;
+    }
+    HIP_TRY(c, hipMemcpy(c->d_jvp_xdot, xdot, sizeof(double) * kp, hipMemcpyHostToDevice));
+    rc = grow(c, &c->d_vjp_part, &c->vjp_part_bytes, sizeof(double) * kn * ((E + grape::kVjpGroup - 1) / grape::kVjpGroup), who, "the groups' rows");
+    if (rc) return rc;
+    rc = grow(c, &c->d_vjp_g, &c->vjp_g_bytes, sizeof(double) * (kn + 1), who, "the summed row");
+    if (rc) return rc;
+    rc = grow(c, &c->d_vjp_out, &c->vjp_out_bytes, sizeof(double) * (kp + 1), who, "the projected row");
+    if (rc) return rc;
+    const double zero = 0.0;                                 // (where the tail expects F)
+    HIP_TRY(c, hipMemcpy(c->d_vjp_g + kn, &zero, sizeof(double), hipMemcpyHostToDevice));
+    c->vjp_n = n_obs;
+    c->vjp_per_member = per_member;
+    c->vjp_has_y = ybar != nullptr;
+    c->vjp_has_x = Xbar_final != nullptr;
+    c->hvp_has_yd = ybar_dot != nullptr;
+    c->hvp_has_xd = Xbar_final_dot != nullptr;
+    c->vjp_O_call = c->d_vjp_O;
+    c->vjp_ybar_call = c->d_vjp_ybar;
+    c->vjp_xbar_call = c->d_vjp_xbar;
+    c->hvp_ybd_call = c->d_hvp_ybd;
+    c->hvp_xbd_call = c->d_hvp_xbd;
+    c->jvp_xdot_call = c->d_jvp_xdot;
+    c->vjp_G_call = c->d_vjp_g;
+    c->vjp_staged = 0;
+    c->hvp_on = true;                                        // enqueue_eval's member blocks end in the two kernels of hvp.hip
+    rc = eval_host(c, 1, x, nullptr, nullptr, who);          // (its [G, F] are not wanted)
+    c->hvp_on = false;
+    if (rc) return rc;
+    // the summed physical row -> the coordinates of x: the projection of the evaluation that has just run, as for the VJP
+    // (bounds are refused: the slope is one)
+    const double *d_res = c->d_vjp_g;
+    if (pulse_map(c)) {
+        KernelLogScope log_scope(&c->kernel_log, true);
+        const grape::BasisOp op = basis_op(c, true, 1);
+        grape::DoneSignal d;
+        d.basis = &op;
+        HIP_TRY(c, grape::launch_copy(c->d_vjp_g, c->d_vjp_out, (int)(kp + 1), c->stream, d));
+        d_res = c->d_vjp_out;
+    }
+    // (the evaluation is published by its own last kernel, or by the sweep itself: the launches above may sit behind that)
+    rc = wait_stream(c, c->stream);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpy(Gdot, d_res, sizeof(double) * kp, hipMemcpyDeviceToHost));
+    return GRAPE_OK;
+}
+
+extern "C" int grape_eval_hvp_device(grape_ctx *c, const double *d_x, const double *d_xdot, int32_t n_obs, int32_t per_member,
+                                     const double *d_O, const double *d_ybar, const double *d_Xbar_final, const double *d_ybar_dot,
+                                     const double *d_Xbar_final_dot, double *d_Gdot, void *stream)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_hvp_device: null context");
+    const char *who = "grape_eval_hvp_device";
+    const bool reuse = d_x == nullptr, was_valid = c->traj_valid;
+    c->traj_valid = false;
+    int rc = hvp_check(c, who, d_x, false, d_xdot, n_obs, per_member, d_O, d_ybar, d_Xbar_final, d_ybar_dot, d_Gdot);
+    if (rc) return rc;
+    if (reuse && chunked(c))
+        return fail(c, GRAPE_ERR_NOT_READY, std::string(who) + ": d_x is null (reuse), but the workspace of a context under member_chunk "
+                                            "holds one block of members only");
+    if (reuse && !was_valid)
+        return fail(c, GRAPE_ERR_NOT_READY, std::string(who) + ": d_x is null (reuse), but the workspace does not hold the trajectory of a "
+                                            "device form: another call has evaluated, changed a setting or failed since");
+    hipStream_t st = (hipStream_t)stream;
+    rc = traj_device_prologue(c);
+    if (rc) return rc;
+    const size_t E = (size_t)c->cfg.n_ensemble, kn = KN(c), kp = KP(c);
+    rc = grow(c, &c->d_vjp_part, &c->vjp_part_bytes, sizeof(double) * kn * ((E + grape::kVjpGroup - 1) / grape::kVjpGroup), who, "the groups' rows");
+    if (rc) return rc;
+    if (pulse_map(c)) {
+        rc = grow(c, &c->d_vjp_g, &c->vjp_g_bytes, sizeof(double) * (kn + 1), who, "the summed row");
+        if (rc) return rc;
+        rc = grow(c, &c->d_vjp_out, &c->vjp_out_bytes, sizeof(double) * (kp + 1), who, "the projected row");
+        if (rc) return rc;
+        rc = grow(c, &c->d_jvp_xphys, &c->jvp_xphys_bytes, sizeof(double) * kn, who, "the direction of the physical pulse");
+        if (rc) return rc;
+    }
+    c->vjp_n = n_obs;
+    c->vjp_per_member = per_member;
+    c->vjp_has_y = d_ybar != nullptr;
+    c->vjp_has_x = d_Xbar_final != nullptr;
+    c->hvp_has_yd = d_ybar_dot != nullptr;
+    c->hvp_has_xd = d_Xbar_final_dot != nullptr;
+    c->vjp_O_call = (const double2 *)d_O;
+    c->vjp_ybar_call = (const double2 *)d_ybar;
+    c->vjp_xbar_call = (const double2 *)d_Xbar_final;
+    c->hvp_ybd_call = (const double2 *)d_ybar_dot;
+    c->hvp_xbd_call = (const double2 *)d_Xbar_final_dot;
+    c->jvp_xdot_call = d_xdot;
+    c->vjp_G_call = pulse_map(c) ? c->d_vjp_g : d_Gdot;      // (no pulse map: the groups' sums ARE Gdot)
+    c->vjp_staged = 0;
+    if (!reuse) {
+        c->hvp_on = true;                                    // enqueue_eval's member blocks end in the two kernels of hvp.hip
+        rc = traj_device_eval(c, d_x, pulse_map(c) ? c->d_vjp_out : c->d_fg, st);          // (its [G, F] are not wanted)
+        c->hvp_on = false;
+        if (rc) return rc;
+    } else {
+        // the propagators (and the slope array) of the last device form are in place: the tangent map and the two kernels alone
+        rc = rc_ensure(c);                                   // (the rows)
+        if (rc) return rc;
+        rc = hvp_ensure(c, who);
+        if (rc) return rc;
+        KernelLogScope log_scope(&c->kernel_log);
+        if (pulse_map(c)) {
+            rc = jvp_tangent_map(c, st);
+            if (rc) return rc;
+        }
+        SweepParams q = sweep_params(c, nullptr, 1);
+        q.props = c->d_props;
+        rc = hvp_launch(c, q, 0, true, c->unitary ? 2 : (c->d_costates ? 1 : 0), st);
+        if (rc) return rc;
+    }
+    if (pulse_map(c)) {
+        // the summed physical row -> the coordinates of x, straight into the caller's Gdot (no F slot: BasisOp::no_f)
+        KernelLogScope log_scope(&c->kernel_log, true);
+        grape::BasisOp op = basis_op(c, true, 1);
+        op.no_f = 1;
+        grape::DoneSignal d;
+        d.basis = &op;
+        HIP_TRY(c, grape::launch_copy(c->d_vjp_g, d_Gdot, (int)kp, st, d));
+    }
+    HIP_TRY(c, hipEventRecord(c->ev_dev, st));
+    c->dev_pending = true;
+    c->traj_valid = !chunked(c);
+    return GRAPE_OK;
 }
 
 // ---- ABI v8: the figure of merit without the gradient ----------------------------------------------------------------------

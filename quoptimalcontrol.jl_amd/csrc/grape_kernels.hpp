@@ -254,6 +254,17 @@ struct SweepParams {
     // fields it reads) -- wherever those are uploaded.  (Appended.)
     double2 *pair_img;
     int32_t img_only;
+    // grape_eval_hvp (hvp.hip): launch_sweep_small / launch_sweep_pair hand a launch with hvp_only set to
+    // trajectory_hvp_kernel + vjp_sum_kernel INSTEAD of the sweep: behind the sweep of the same members (one control array)
+    // they read the propagators that sweep stored and differentiate the pull-back along the direction hvp_xdot.  The
+    // pull-back is described by the vjp_* fields (probes, cotangents, decomposition, rows, groups' sums; vjp_only stays 0
+    // and vjp_staged / traj_exact are not read); the groups' sums go into vjp_G by a vjp_only = 2 launch, as for the VJP.
+    // (Appended.)
+    int32_t hvp_only;
+    const double *hvp_xdot;         // (K, N) column-major: the direction in the coordinates of the PHYSICAL pulse
+    const double2 *hvp_ybar_dot;    // (N + 1, vjp_n, vjp_Etot), nullable (zero): the tangent of vjp_ybar
+    const double2 *hvp_xbar_dot;    // (n, m, vjp_Etot), nullable (zero): the tangent of vjp_xbar
+    double2 *hvp_xs;                // general flow: [X_{t+1} | Xdot_{t+1}] per slice, chunk-major like props, 2 n m elements per slice
 };
 // A member's image record: what the lane-pair sweep's prologue puts into LDS, laid out as the LDS holds it.
 //   [0, 2 PS)        both parity images of A', B'_c, B'_c^T, Xi, Xt, Xi Xt' (every mode but the anti-Hermitian sweep), pads zero
@@ -315,6 +326,15 @@ hipError_t run_observe(int n, int sandwich, const SweepParams &p, hipStream_t st
 hipError_t run_trajectory_vjp(int n, const SweepParams &p, hipStream_t stream);
 // jvp.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::jvp_only) only
 hipError_t run_trajectory_jvp(int n, const SweepParams &p, hipStream_t stream);
+// vjp.hip: vjp_sum_kernel over the rows of the launch's members, onto their groups' sums in vjp_part (run_trajectory_vjp and
+// run_trajectory_hvp end in it)
+hipError_t launch_vjp_rows_sum(const SweepParams &p, hipStream_t stream);
+// grape_eval_hvp: whether trajectory_hvp_kernel at (n, m) walks X and Xdot back with P' under the unitary flow (three blocks of
+// scratch per chunk) or stores them per slice as the general flow does (2 S blocks per chunk).  n = m = 3 stores: its walk-back
+// instance does not fit 256 registers.  The host layer sizes SweepParams::hvp_xs by it.
+constexpr bool hvp_walks_back(int n, int m) { return !(n == 3 && m == 3); }
+// hvp.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::hvp_only) only
+hipError_t run_trajectory_hvp(int n, const SweepParams &p, hipStream_t stream);
 // traj_frechet.hip; reached through run_trajectory_vjp (dir = false) / run_trajectory_jvp (dir = true) only
 hipError_t run_traj_frechet(int n, bool dir, const SweepParams &p, hipStream_t stream);
 constexpr int kVjpGroup = 32;                 // members per group of vjp_sum_kernel's tree: vjp_part has ceil(E / 32) rows

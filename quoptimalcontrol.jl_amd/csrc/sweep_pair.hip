@@ -1565,6 +1565,8 @@ hipError_t launch_sweep_pair(int n, int sandwich, int mode, const SweepParams &p
         return run_trajectory_vjp(n, p, stream);
     if (p.jvp_only)                                  // grape_eval_jvp: the kernel behind the sweep (jvp.hip)
         return run_trajectory_jvp(n, p, stream);
+    if (p.hvp_only)                                  // grape_eval_hvp: the kernels behind the sweep (hvp.hip)
+        return run_trajectory_hvp(n, p, stream);
     switch (n * 2 + (sandwich ? 1 : 0)) {
     case 4: return plaunch_ns<2, 0>(mode, p, stream);
     case 5: return plaunch_ns<2, 1>(mode, p, stream);

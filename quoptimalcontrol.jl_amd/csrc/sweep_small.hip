@@ -625,6 +625,8 @@ hipError_t launch_sweep_small(int n, int sandwich, int mode, const SweepParams &
         return run_trajectory_vjp(n, p, stream);
     if (p.jvp_only)                                  // grape_eval_jvp: the kernel behind the sweep (jvp.hip)
         return run_trajectory_jvp(n, p, stream);
+    if (p.hvp_only)                                  // grape_eval_hvp: the kernels behind the sweep (hvp.hip)
+        return run_trajectory_hvp(n, p, stream);
     switch (n * 2 + (sandwich ? 1 : 0)) {
     case 4: return launch_ns<2, 0>(mode, p, stream);
     case 5: return launch_ns<2, 1>(mode, p, stream);

@@ -1,5 +1,5 @@
 // traj_chunk.hpp -- the chunk-scan skeleton of the kernels that run behind the small-n sweeps on the propagators those left
-// in the workspace: running_cost_kernel, observe_kernel, trajectory_vjp_kernel, trajectory_jvp_kernel.
+// in the workspace: running_cost_kernel, observe_kernel, trajectory_vjp_kernel, trajectory_jvp_kernel, trajectory_hvp_kernel.
 //
 // The workspace is chunk-major: element e of slice t = c S + jj of row k at ((k S + jj) n^2 + e) CH + c.  Every kernel of the
 // family runs one workgroup per row and one lane per time chunk of S consecutive slices, so every workspace access is

@@ -276,6 +276,13 @@ static hipError_t vjp_launch_nm(const SweepParams &p, hipStream_t stream)
     e = hipGetLastError();
     if (e != hipSuccess)
         return e;
+    return launch_vjp_rows_sum(p, stream);
+}
+
+// the rows of this launch's members onto the sums of their groups (behind trajectory_vjp_kernel, and behind
+// trajectory_hvp_kernel of hvp.hip, which writes the same rows)
+hipError_t launch_vjp_rows_sum(const SweepParams &p, hipStream_t stream)
+{
     const int Q = p.K * p.N;
     const int groups = (p.vjp_E0 + p.E - 1) / kVjpGroup - p.vjp_E0 / kVjpGroup + 1;
     GRAPE_LAUNCH(vjp_sum_kernel, dim3((Q + 255) / 256, groups), dim3(256), 0, stream, p.vjp_rows, p.vjp_part, p.vjp_E0, p.E, Q,

@@ -44,7 +44,7 @@ EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_oper
            "grape_comm_unique_id", "grape_comm_attach", "grape_ipc_export", "grape_ipc_attach",
            "grape_eval", "grape_eval_device", "grape_eval_batch", "grape_eval_batch_device", "grape_eval_fom", "grape_eval_observables",
            "grape_eval_vjp", "grape_eval_observables_device", "grape_eval_vjp_device", "grape_eval_jvp", "grape_eval_jvp_device",
-           "grape_eval_jvp_multi", "grape_eval_jvp_multi_device",
+           "grape_eval_jvp_multi", "grape_eval_jvp_multi_device", "grape_eval_hvp", "grape_eval_hvp_device",
            "grape_set_trajectory_derivative", "grape_set_running_cost_derivative",
            "grape_lbfgs", "grape_lbfgs_get_trace",
            "grape_get_member_results", "grape_get_trajectory",
@@ -153,6 +153,8 @@ def load_library():
     L.grape_eval_jvp_device.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
     L.grape_eval_jvp_multi.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp]
     L.grape_eval_jvp_multi_device.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
+    L.grape_eval_hvp.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.grape_eval_hvp_device.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.grape_set_trajectory_derivative.argtypes = [vp, i32]
     L.grape_set_running_cost_derivative.argtypes = [vp, i32]
     L.grape_lbfgs.argtypes = [vp, vp, C.POINTER(GrapeLbfgsOptions), vp, C.POINTER(GrapeLbfgsResult)]
@@ -734,6 +736,55 @@ class GrapeEngine:
             return yd, np.ascontiguousarray(np.swapaxes(Xf, -1, -2))
         return yd
 
+    def observe_hvp(self, x, xdot, ops, ybar=None, xbar_final=None, ybar_dot=None, xbar_final_dot=None, per_member=False):
+        """grape_eval_hvp: the directional derivative of observe_vjp -- how G = observe_vjp(x, ops, ybar, xbar_final) moves to
+        first order when x moves along xdot (x's shape and coordinates) and the cotangents move along ybar_dot (E, n_obs, N+1)
+        / xbar_final_dot (E, n, m); either tangent may be None (zero).  With ybar = dl/dy of a loss l on observe's returns and
+        ybar_dot = l'' applied to observe_jvp(x, xdot, ...) this is the Hessian-vector product of l.  Returns Gdot (K, cols),
+        first order in dt under the rule of observe_vjp / observe_jvp, without ensemble weights, penalties, running cost or
+        risk.  The contexts observe_vjp serves, without bounds and in the first-order trajectory derivative mode
+        (include/grape_hip.h)."""
+        x = np.asarray(x, dtype=np.float64)
+        xd = np.asarray(xdot, dtype=np.float64)
+        if x.shape != (self.K, self._cols):
+            raise ValueError(f"x must be ({self.K},{self._cols})")
+        if xd.shape != x.shape:
+            raise ValueError(f"observe_hvp: xdot must be ({self.K},{self._cols}), the shape of x")
+        n, m, E, N = self.n, self.m, self.E, self.N
+        if ybar is None and xbar_final is None:
+            raise ValueError("observe_hvp: nothing to pull back (ybar and xbar_final are both None)")
+        if ops is None:
+            if ybar is not None or ybar_dot is not None:
+                raise ValueError("observe_hvp: ybar / ybar_dot need the probes they belong to")
+        n_obs, O = self._jvp_probes("observe_hvp", ops, per_member)
+        Of = None if O is None else _cm(np.swapaxes(O, 0, 1) if per_member else O)
+        if ybar is None and ybar_dot is None:
+            n_obs, Of = 0, None                                   # (probes without cotangents: nothing of theirs to pull back)
+
+        def rows(a, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.complex128)
+            if a.shape != (E, n_obs, N + 1):
+                raise ValueError(f"observe_hvp: {name} must be ({E},{n_obs},{N + 1})")
+            return a
+
+        def finals(a, name):
+            if a is None:
+                return None
+            a = np.asarray(a, dtype=np.complex128)
+            if a.shape != (E, n, m):
+                raise ValueError(f"observe_hvp: {name} must be ({E},{n},{m})")
+            return _cm(a)
+
+        yb, ybd = rows(ybar, "ybar"), rows(ybar_dot, "ybar_dot")
+        xb, xbd = finals(xbar_final, "xbar_final"), finals(xbar_final_dot, "xbar_final_dot")
+        Gd = np.empty((self._cols, self.K))
+        xf, xdf = np.ascontiguousarray(x.T), np.ascontiguousarray(xd.T)
+        self._check(self._lib.grape_eval_hvp(self._h, _p(xf), _p(xdf), n_obs, 1 if per_member else 0, _p(Of), _p(yb), _p(xb),
+                                             _p(ybd), _p(xbd), _p(Gd)))
+        return np.ascontiguousarray(Gd.T)
+
     def observe_device(self, d_x, n_obs, per_member, d_O, d_y, d_X_final, d_fg=0, stream=0):
         """grape_eval_observables_device with raw device pointers (e.g. torch tensor .data_ptr()), in the library's layouts:
         d_x f64 (K, cols) column-major, d_O c128 (n, m, [E,] n_obs), d_y c128 (N+1, n_obs, E), d_X_final c128 (n, m, E), d_fg
@@ -765,6 +816,23 @@ class GrapeEngine:
             raise ValueError("observe_jvp_device: d_xdot is null")
         self._check(self._lib.grape_eval_jvp_device(self._h, C.c_void_p(d_x), C.c_void_p(d_xdot), n_obs, 1 if per_member else 0,
                                                     C.c_void_p(d_O), C.c_void_p(d_ydot), C.c_void_p(d_Xdot_final),
+                                                    C.c_void_p(stream)))
+
+    def observe_hvp_device(self, d_x, d_xdot, n_obs, per_member, d_O, d_ybar, d_Xbar_final, d_ybar_dot, d_Xbar_final_dot, d_Gdot,
+                           stream=0):
+        """grape_eval_hvp_device with raw device pointers, layouts as observe_vjp_device / observe_jvp_device; d_ybar_dot and
+        d_Xbar_final_dot in the layouts of d_ybar / d_Xbar_final, 0 for zero; d_Gdot f64 (K, cols) column-major.  d_x=0: reuse
+        -- along the trajectory the last device form left in the workspace, without a sweep (GrapeError NOT_READY when
+        anything else has touched the context since, or under a member chunk); the other reuse forms may follow."""
+        n_obs = self._traj_device_args("observe_hvp_device", 1, n_obs, d_O, d_ybar, d_Xbar_final, "d_ybar and d_Xbar_final")
+        if not d_xdot:
+            raise ValueError("observe_hvp_device: d_xdot is null")
+        if not d_Gdot:
+            raise ValueError("observe_hvp_device: d_Gdot is null")
+        self.calls += 1
+        self._check(self._lib.grape_eval_hvp_device(self._h, C.c_void_p(d_x), C.c_void_p(d_xdot), n_obs, 1 if per_member else 0,
+                                                    C.c_void_p(d_O), C.c_void_p(d_ybar), C.c_void_p(d_Xbar_final),
+                                                    C.c_void_p(d_ybar_dot), C.c_void_p(d_Xbar_final_dot), C.c_void_p(d_Gdot),
                                                     C.c_void_p(stream)))
 
     def _jvp_probes(self, who, ops, per_member):
