@@ -602,6 +602,39 @@ int grape_eval_observables_device(grape_ctx *ctx, const double *d_x, int32_t n_o
 int grape_eval_vjp_device(grape_ctx *ctx, const double *d_x, int32_t n_obs, int32_t per_member, const double *d_O,
                           const double *d_ybar, const double *d_Xbar_final, double *d_G, void *stream);
 
+/* ABI v8 (additive).  grape_eval_vjp for several cotangent sets behind ONE evaluation of x: one gradient per loss or constraint
+ * of a multi-objective / constrained optimiser, Jacobian ROWS of the read-out in reverse mode (the twin of the columns
+ * grape_eval_jvp_multi gives), per-probe sensitivities.  The set index is slowest everywhere:
+ *   ybar        c128 (N+1, n_obs, E, n_set)   nullable for the whole block (zero)
+ *   Xbar_final  c128 (n, m, E, n_set)         nullable for the whole block (zero); not both
+ *   G           f64  (K, cols, n_set)         cols = N, or M in parameter mode
+ * The probes O are shared by the sets.  1 <= n_set <= GRAPE_MAX_VJP_COTANGENTS, anything else GRAPE_ERR_INVALID_ARG with the
+ * value in the message.  Every other argument check, refusal (checked first) and GRAPE_ERR_NOT_READY is grape_eval_vjp's; the
+ * not-finite check of the host arrays runs over all sets.
+ * DEFINING PROPERTY: block r of G is bit for bit what grape_eval_vjp returns for set r alone on the same context -- in both
+ * modes of grape_set_trajectory_derivative, under a basis and / or bounds, on member-chunked contexts (the unchunked bits),
+ * with forced slices_per_lane / waves_per_member and under a standing running cost, penalties or risk (none of which enter).
+ * Exact linearity in the cotangents and the transpose identity with grape_eval_jvp_multi follow from it.
+ * trajectory_vjp_multi_kernel carries a block of sets (2 to 8, by operator dimension and state columns) next to one chunk
+ * product, one prefix scan, one walk of the states and one load of every propagator per pass; vjp_sum_kernel adds every
+ * set's rows in grape_eval_vjp's fixed tree.  A decomposition with more than 256 time chunks per member, the exact mode
+ * (trajectory_vjp_exact_kernel + traj_frechet_rows_kernel once per set behind the ONE sweep) and GRAPE_VJP_MULTI=0 run the
+ * single call's kernels per set: the same bits; grape_get_kernel_names tells which ran.  The scratch of the block (the
+ * members' rows, the groups' sums, the summed and projected rows of every set) is counted in grape_info.workspace_bytes.
+ * An eval -> vjp_multi -> eval sequence returns the first evaluation's bits. */
+#define GRAPE_MAX_VJP_COTANGENTS 8
+int grape_eval_vjp_multi(grape_ctx *ctx, const double *x, int32_t n_set, int32_t n_obs, int32_t per_member,
+                         const double *O, const double *ybar, const double *Xbar_final, double *G);
+
+/* ABI v8 (additive).  The device form of grape_eval_vjp_multi under the rules of grape_eval_vjp_device: device arrays in the
+ * layouts above, asynchronous on `stream`, not checked for non-finite values, no staging copy; the "trajectory valid" flag is
+ * set under the same conditions.  d_x = NULL pulls back along the stored trajectory with no sweep, keeps the flag set and
+ * returns the bits of the call with d_x; with the flag clear, or on a member-chunked context, GRAPE_ERR_NOT_READY with
+ * grape_eval_vjp_device's messages.  The multi instance reads ybar directly (no staged instance). */
+int grape_eval_vjp_multi_device(grape_ctx *ctx, const double *d_x, int32_t n_set, int32_t n_obs, int32_t per_member,
+                                const double *d_O, const double *d_ybar, const double *d_Xbar_final, double *d_G,
+                                void *stream);
+
 /* ABI v8 (additive).  The Jacobian-vector product of the trajectory read-out: the forward-mode twin of grape_eval_vjp.  Given
  * a direction xdot in control space it returns how every expectation value along the trajectory, and the final state of every
  * member, move to first order -- what a Gauss-Newton / Levenberg-Marquardt step on a loss on y needs next to the pull-back,

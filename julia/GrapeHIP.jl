@@ -324,6 +324,48 @@ function eval_jvp_multi_device!(ctx::GrapeContext, d_x::Ptr{Cvoid}, n_dir::Integ
     ctx
 end
 
+# grape_eval_vjp_multi: the pull-back of `observables` for a block of cotangent sets behind ONE evaluation of x.  ybar is
+# (N+1, n_obs, E, n_set) and Xbar (n, m, E, n_set) (the set index slowest, 1 <= n_set <= 8; either may be `nothing` = zero, not
+# both); G (K, N, n_set) is written in place and returned.  Slice [:, :, r] is bit for bit what grape_eval_vjp returns for
+# set r alone.  (Written, NOT executed, like `eval_jvp_multi!`; the Python binding makes the same call and is tested on the GPU.)
+function eval_vjp_multi!(G::Array{Float64,3}, ctx::GrapeContext, x::Matrix{Float64}, O::Union{Nothing,Array{ComplexF64}},
+                         ybar::Union{Nothing,Array{ComplexF64,4}}, Xbar::Union{Nothing,Array{ComplexF64,4}})
+    size(x) == (ctx.K, ctx.N) || throw(DimensionMismatch("x must be (n_controls, n_slices)"))
+    (ybar === nothing && Xbar === nothing) && throw(ArgumentError("eval_vjp_multi!: ybar and Xbar are both nothing"))
+    n_set = ybar === nothing ? size(Xbar, 4) : size(ybar, 4)
+    1 <= n_set <= 8 || throw(ArgumentError("eval_vjp_multi!: 1 to 8 cotangent sets (GRAPE_MAX_VJP_COTANGENTS)"))
+    n_obs = 0
+    if ybar !== nothing
+        O === nothing && throw(ArgumentError("eval_vjp_multi!: ybar needs the probes it belongs to"))
+        n_obs = size(O, ndims(O))
+        (ndims(O) == 3 && size(O) == (ctx.n, ctx.m, n_obs)) || (ndims(O) == 4 && size(O) == (ctx.n, ctx.m, ctx.E, n_obs)) ||
+            throw(DimensionMismatch("O must be (n, m, n_obs) or (n, m, E, n_obs) with the context's n, m and E"))
+        1 <= n_obs <= 16 || throw(ArgumentError("eval_vjp_multi!: 1 to 16 probes"))
+        size(ybar) == (ctx.N + 1, n_obs, ctx.E, n_set) || throw(DimensionMismatch("ybar must be (N+1, n_obs, E, n_set)"))
+    end
+    Xbar === nothing || size(Xbar) == (ctx.n, ctx.m, ctx.E, n_set) || throw(DimensionMismatch("Xbar must be (n, m, E, n_set)"))
+    size(G) == (ctx.K, ctx.N, n_set) || throw(DimensionMismatch("G must be (n_controls, n_slices, n_set)"))
+    per_member = (n_obs > 0 && ndims(O) == 4) ? 1 : 0
+    p_O = n_obs > 0 ? pointer(O) : Ptr{ComplexF64}(C_NULL)
+    p_y = ybar === nothing ? Ptr{ComplexF64}(C_NULL) : pointer(ybar)
+    p_X = Xbar === nothing ? Ptr{ComplexF64}(C_NULL) : pointer(Xbar)
+    GC.@preserve x O ybar Xbar G check(ctx, ccall((:grape_eval_vjp_multi, libgrape), Cint,
+                                                  (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Int32, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{Float64}),
+                                                  ctx.handle, x, Int32(n_set), Int32(n_obs), Int32(per_member), p_O, p_y, p_X, G))
+    G
+end
+
+# grape_eval_vjp_multi_device: the same on device memory (raw device pointers in the layouts above), asynchronous on `stream`;
+# d_x = C_NULL pulls back along the stored trajectory without a sweep.
+function eval_vjp_multi_device!(ctx::GrapeContext, d_x::Ptr{Cvoid}, n_set::Integer, n_obs::Integer, per_member::Bool,
+                                d_O::Ptr{Cvoid}, d_ybar::Ptr{Cvoid}, d_Xbar_final::Ptr{Cvoid}, d_G::Ptr{Cvoid};
+                                stream::Ptr{Cvoid} = C_NULL)
+    check(ctx, ccall((:grape_eval_vjp_multi_device, libgrape), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                     ctx.handle, d_x, Int32(n_set), Int32(n_obs), Int32(per_member ? 1 : 0), d_O, d_ybar, d_Xbar_final, d_G, stream))
+    ctx
+end
+
 # grape_set_trajectory_derivative: :first_order (default) or :exact -- observables_vjp / observables_jvp, their device forms and
 # the reuse forms then use the Frechet derivative of the sweep's own expm evaluation per slice instead of (-i dt B) P
 function set_trajectory_derivative!(ctx::GrapeContext, mode::Symbol)

@@ -232,6 +232,11 @@ struct grape_ctx {
     double2 *obs_y_call = nullptr, *obs_xf_call = nullptr;
     double *vjp_G_call = nullptr;              // K N: the summed physical row (d_vjp_g, or the caller's G without a pulse map)
     int obs_staged = 0, vjp_staged = 0;
+    // grape_eval_vjp_multi: cotangent sets of the call in flight (0: the single call), each with the single call's arrays one
+    // behind the other -- the cotangents, the members' rows, the groups' sums, the summed rows (vjp_G_step doubles apart);
+    // vjp_multi: trajectory_vjp_multi_kernel where it serves the shape (GRAPE_VJP_MULTI, else the table)
+    int vjp_nset = 0, vjp_multi = 0;
+    size_t vjp_G_step = 0;
     // grape_eval_jvp (jvp.hip): behind the sweep (the running-cost kernels) of every member block of ONE evaluation,
     // trajectory_jvp_kernel pushes the caller's direction forward along the stored propagators.  jvp_on is set by the entry
     // point around that evaluation only.  Under a pulse map the direction goes through the map's tangent first (BasisOp::tangent,
@@ -2677,6 +2682,9 @@ static void traj_exact_params(const grape_ctx *c, SweepParams &v)
     v.traj_x = c->d_traj_x;
 }
 
+// grape_eval_vjp_multi: doubles between the members' rows of consecutive cotangent sets (the single call's rows, rc_ensure)
+static size_t vjp_set_rows(const grape_ctx *c) { return (size_t)c->Ec * ws_batch(c) * (KN(c) + 1); }
+
 // grape_eval_vjp: the launch of trajectory_vjp_kernel + vjp_sum_kernel for the members from `lo` on that `q` sweeps (or swept:
 // grape_eval_vjp_device's reuse)
 static SweepParams vjp_params(const grape_ctx *c, const SweepParams &q, int lo)
@@ -2699,7 +2707,27 @@ static SweepParams vjp_params(const grape_ctx *c, const SweepParams &q, int lo)
     v.vjp_G = c->vjp_G_call;
     v.vjp_staged = c->vjp_has_y && !traj_exact(c) ? c->vjp_staged : 0;      // (exact mode: the direct instance only)
     traj_exact_params(c, v);
+    if (c->vjp_nset > 0) {                                   // grape_eval_vjp_multi: the single call's arrays, set-slowest
+        const size_t E = (size_t)c->cfg.n_ensemble;
+        v.vjp_nset = c->vjp_nset;
+        v.vjp_multi = c->vjp_multi;
+        v.vjp_set_ybar = (int64_t)(((size_t)c->cfg.n_slices + 1) * c->vjp_n * E);
+        v.vjp_set_xbar = (int64_t)((size_t)c->cfg.n * c->m * E);
+        v.vjp_set_rows = (int64_t)vjp_set_rows(c);
+        v.vjp_set_part = (int64_t)(KN(c) * ((E + grape::kVjpGroup - 1) / grape::kVjpGroup));
+        v.vjp_set_G = (int64_t)c->vjp_G_step;
+    }
     return v;
+}
+
+// the members' rows and the stored states of a pull-back (rc_ensure), and for grape_eval_vjp_multi the rows of every set, one
+// image of the single call's behind the other
+static int vjp_rows_ensure(grape_ctx *c)
+{
+    if (int rc = rc_ensure(c)) return rc;
+    if (c->vjp_nset < 2) return GRAPE_OK;
+    return grow(c, &c->d_rc_rows, &c->rc_rows_bytes, sizeof(double) * vjp_set_rows(c) * (size_t)c->vjp_nset, "grape_eval_vjp_multi",
+                "the members' rows of every cotangent set");
 }
 
 // grape_eval_jvp: the launch of trajectory_jvp_kernel for the members from `lo` on that `q` sweeps (or swept:
@@ -2838,7 +2866,7 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
         if (rc) return rc;
     }
     if (c->vjp_on || c->hvp_on) {                            // (the rows, and the states of the general flow)
-        const int rc = rc_ensure(c);
+        const int rc = vjp_rows_ensure(c);
         if (rc) return rc;
     }
     if (c->hvp_on) {
@@ -3747,11 +3775,15 @@ static int jvp_check(grape_ctx *c, const std::string &who, const void *x, bool x
     return GRAPE_OK;
 }
 
+// (n_set: grape_eval_vjp_multi's set count; the single calls pass 1)
 static int vjp_check(grape_ctx *c, const std::string &who, const void *x, bool x_needed, int32_t n_obs, int32_t per_member,
-                     const void *O, const void *ybar, const void *Xbar_final, const void *G)
+                     const void *O, const void *ybar, const void *Xbar_final, const void *G, int32_t n_set = 1)
 {
     const char *why = why_linearisation_not_served(c);
     if (why) return fail(c, GRAPE_ERR_UNSUPPORTED, who + ": " + why);
+    if (n_set < 1 || n_set > GRAPE_MAX_VJP_COTANGENTS)
+        return fail(c, GRAPE_ERR_INVALID_ARG, who + ": n_set = " + std::to_string(n_set) + " (must be in 1.." +
+                                              std::to_string(GRAPE_MAX_VJP_COTANGENTS) + ")");
     if (!x && x_needed) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": x is null");
     if (!G) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": G is null");
     if (!ybar && !Xbar_final) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": ybar and Xbar_final are both null");
@@ -3812,16 +3844,47 @@ extern "C" int grape_eval_observables(grape_ctx *c, const double *x, int32_t n_o
 }
 
 // ---- grape_eval_vjp: one evaluation + the pull-back of the caller's cotangents along its trajectory ---------------------------
-extern "C" int grape_eval_vjp(grape_ctx *c, const double *x, int32_t n_obs, int32_t per_member, const double *O,
-                              const double *ybar, const double *Xbar_final, double *G)
+// GRAPE_VJP_MULTI=0 / 1 forces the single call's kernels per set / trajectory_vjp_multi_kernel (where an instance serves the
+// launch); otherwise the shapes at which the multi kernel measured faster per set (grape_kernels.hpp)
+static int vjp_multi_choice(const grape_ctx *c)
 {
-    DeviceGuard guard;
-    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp: null context");
-    const char *who = "grape_eval_vjp";
+    if (env_off("GRAPE_VJP_MULTI")) return 0;
+    if (env_on("GRAPE_VJP_MULTI")) return 2;                 // (forced: blocks of one set too)
+    return grape::vjp_multi_default(c->cfg.n, c->m) ? 1 : 0;
+}
+
+// the set count of a grape_eval_vjp_multi call in flight, back to 0 (the single call) on every way out
+struct VjpMultiScope {
+    grape_ctx *c;
+    VjpMultiScope(grape_ctx *c_, int nset) : c(c_)
+    {
+        c->vjp_nset = nset;
+        c->vjp_multi = nset > 0 ? vjp_multi_choice(c) : 0;
+    }
+    ~VjpMultiScope() { c->vjp_nset = 0; c->vjp_multi = 0; c->vjp_G_step = 0; }
+};
+
+// the groups' sums of every set of the call, and (`rows`: the host forms always, the device forms under a pulse map) the
+// summed physical rows [K N | 0] and the projected rows [K M | 0], one per set
+static int vjp_grow_sums(grape_ctx *c, const char *who, size_t nset, bool rows)
+{
+    const size_t E = (size_t)c->cfg.n_ensemble, kn = KN(c), kp = KP(c);
+    int rc = grow(c, &c->d_vjp_part, &c->vjp_part_bytes, sizeof(double) * kn * ((E + grape::kVjpGroup - 1) / grape::kVjpGroup) * nset, who, "the groups' rows");
+    if (rc || !rows) return rc;
+    rc = grow(c, &c->d_vjp_g, &c->vjp_g_bytes, sizeof(double) * (kn + 1) * nset, who, "the summed row");
+    if (rc) return rc;
+    return grow(c, &c->d_vjp_out, &c->vjp_out_bytes, sizeof(double) * (kp + 1) * nset, who, "the projected row");
+}
+
+// grape_eval_vjp (multi = false) and grape_eval_vjp_multi (n_set cotangent sets, every array set-slowest)
+static int eval_vjp_host(grape_ctx *c, const char *who, bool multi, const double *x, int32_t n_set, int32_t n_obs, int32_t per_member,
+                         const double *O, const double *ybar, const double *Xbar_final, double *G)
+{
     c->traj_valid = false;
-    if (int rc0 = vjp_check(c, who, x, true, n_obs, per_member, O, ybar, Xbar_final, G)) return rc0;
+    if (int rc0 = vjp_check(c, who, x, true, n_obs, per_member, O, ybar, Xbar_final, G, multi ? n_set : 1)) return rc0;
+    const size_t ns = multi ? (size_t)n_set : 1;
     const size_t n = (size_t)c->cfg.n, m = (size_t)c->m, E = (size_t)c->cfg.n_ensemble, N = (size_t)c->cfg.n_slices;
-    const size_t n_O = n * m * (per_member ? E : 1) * (size_t)n_obs, n_y = (N + 1) * (size_t)n_obs * E, n_X = n * m * E;
+    const size_t n_O = n * m * (per_member ? E : 1) * (size_t)n_obs, n_y = (N + 1) * (size_t)n_obs * E * ns, n_X = n * m * E * ns;
     int rc = check_finite(c, O, 2 * n_O, who, "O", 2);
     if (rc) return rc;
     if (ybar) rc = check_finite(c, ybar, 2 * n_y, who, "ybar", 2);
@@ -3829,6 +3892,11 @@ extern "C" int grape_eval_vjp(grape_ctx *c, const double *x, int32_t n_obs, int3
     if (Xbar_final) rc = check_finite(c, Xbar_final, 2 * n_X, who, "Xbar_final", 2);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
+    VjpMultiScope scope(c, multi ? n_set : 0);
+    if (multi) {                                             // (the sums and the rows are the device form's too, which does not block)
+        rc = drain(c, c);
+        if (rc) return rc;
+    }
     const size_t kn = KN(c), kp = KP(c);
     // (the buffers belong to this entry point alone, which is blocking: no launch in flight reads them)
     if (ybar) {
@@ -3844,14 +3912,11 @@ extern "C" int grape_eval_vjp(grape_ctx *c, const double *x, int32_t n_obs, int3
         if (rc) return rc;
         HIP_TRY(c, hipMemcpy(c->d_vjp_xbar, Xbar_final, sizeof(double2) * n_X, hipMemcpyHostToDevice));
     }
-    rc = grow(c, &c->d_vjp_part, &c->vjp_part_bytes, sizeof(double) * kn * ((E + grape::kVjpGroup - 1) / grape::kVjpGroup), who, "the groups' rows");
-    if (rc) return rc;
-    rc = grow(c, &c->d_vjp_g, &c->vjp_g_bytes, sizeof(double) * (kn + 1), who, "the summed row");
-    if (rc) return rc;
-    rc = grow(c, &c->d_vjp_out, &c->vjp_out_bytes, sizeof(double) * (kp + 1), who, "the projected row");
+    rc = vjp_grow_sums(c, who, ns, true);
     if (rc) return rc;
     const double zero = 0.0;                                 // (where the tail expects F)
-    HIP_TRY(c, hipMemcpy(c->d_vjp_g + kn, &zero, sizeof(double), hipMemcpyHostToDevice));
+    for (size_t r = 0; r < ns; ++r)
+        HIP_TRY(c, hipMemcpy(c->d_vjp_g + r * (kn + 1) + kn, &zero, sizeof(double), hipMemcpyHostToDevice));
     c->vjp_n = n_obs;
     c->vjp_per_member = per_member;
     c->vjp_has_y = ybar != nullptr;
@@ -3860,27 +3925,48 @@ extern "C" int grape_eval_vjp(grape_ctx *c, const double *x, int32_t n_obs, int3
     c->vjp_ybar_call = c->d_vjp_ybar;
     c->vjp_xbar_call = c->d_vjp_xbar;
     c->vjp_G_call = c->d_vjp_g;
+    c->vjp_G_step = kn + 1;
     c->vjp_staged = 0;
     c->vjp_on = true;                                        // enqueue_eval's member blocks end in the two kernels of vjp.hip
     rc = eval_host(c, 1, x, nullptr, nullptr, who);          // (its [G, F] are not wanted)
     c->vjp_on = false;
     if (rc) return rc;
-    // the summed physical row -> the coordinates of x: the slope / projection of the evaluation that has just run (its slope
+    // the summed physical rows -> the coordinates of x: the slope / projection of the evaluation that has just run (its slope
     // array is in place), without the penalty and F that the evaluation's own tail carries
     const double *d_res = c->d_vjp_g;
+    size_t res_step = kn + 1;
     if (pulse_map(c)) {
         KernelLogScope log_scope(&c->kernel_log, true);
         const grape::BasisOp op = basis_op(c, true, 1);
         grape::DoneSignal d;
         d.basis = &op;
-        HIP_TRY(c, grape::launch_copy(c->d_vjp_g, c->d_vjp_out, (int)(kp + 1), c->stream, d));
+        for (size_t r = 0; r < ns; ++r)
+            HIP_TRY(c, grape::launch_copy(c->d_vjp_g + r * (kn + 1), c->d_vjp_out + r * (kp + 1), (int)(kp + 1), c->stream, d));
         d_res = c->d_vjp_out;
+        res_step = kp + 1;
     }
     // (the evaluation is published by its own last kernel, or by the sweep itself: the launches above may sit behind that)
     rc = wait_stream(c, c->stream);
     if (rc) return rc;
-    HIP_TRY(c, hipMemcpy(G, d_res, sizeof(double) * kp, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < ns; ++r)
+        HIP_TRY(c, hipMemcpy(G + r * kp, d_res + r * res_step, sizeof(double) * kp, hipMemcpyDeviceToHost));
     return GRAPE_OK;
+}
+
+extern "C" int grape_eval_vjp(grape_ctx *c, const double *x, int32_t n_obs, int32_t per_member, const double *O,
+                              const double *ybar, const double *Xbar_final, double *G)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp: null context");
+    return eval_vjp_host(c, "grape_eval_vjp", false, x, 0, n_obs, per_member, O, ybar, Xbar_final, G);
+}
+
+extern "C" int grape_eval_vjp_multi(grape_ctx *c, const double *x, int32_t n_set, int32_t n_obs, int32_t per_member,
+                                    const double *O, const double *ybar, const double *Xbar_final, double *G)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp_multi: null context");
+    return eval_vjp_host(c, "grape_eval_vjp_multi", true, x, n_set, n_obs, per_member, O, ybar, Xbar_final, G);
 }
 
 // ---- the device forms: the caller's arrays live on this device, nothing is copied, nothing is synchronised ---------------------
@@ -3962,15 +4048,13 @@ extern "C" int grape_eval_observables_device(grape_ctx *c, const double *d_x, in
     return GRAPE_OK;
 }
 
-extern "C" int grape_eval_vjp_device(grape_ctx *c, const double *d_x, int32_t n_obs, int32_t per_member, const double *d_O,
-                                     const double *d_ybar, const double *d_Xbar_final, double *d_G, void *stream)
+// grape_eval_vjp_device (multi = false) and grape_eval_vjp_multi_device
+static int eval_vjp_device(grape_ctx *c, const char *who, bool multi, const double *d_x, int32_t n_set, int32_t n_obs, int32_t per_member,
+                           const double *d_O, const double *d_ybar, const double *d_Xbar_final, double *d_G, void *stream)
 {
-    DeviceGuard guard;
-    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp_device: null context");
-    const char *who = "grape_eval_vjp_device";
     const bool reuse = d_x == nullptr, was_valid = c->traj_valid;
     c->traj_valid = false;
-    int rc = vjp_check(c, who, d_x, false, n_obs, per_member, d_O, d_ybar, d_Xbar_final, d_G);
+    int rc = vjp_check(c, who, d_x, false, n_obs, per_member, d_O, d_ybar, d_Xbar_final, d_G, multi ? n_set : 1);
     if (rc) return rc;
     if (reuse && chunked(c))
         return fail(c, GRAPE_ERR_NOT_READY, std::string(who) + ": d_x is null (reuse), but the workspace of a context under member_chunk "
@@ -3981,15 +4065,10 @@ extern "C" int grape_eval_vjp_device(grape_ctx *c, const double *d_x, int32_t n_
     hipStream_t st = (hipStream_t)stream;
     rc = traj_device_prologue(c);
     if (rc) return rc;
-    const size_t E = (size_t)c->cfg.n_ensemble, kn = KN(c), kp = KP(c);
-    rc = grow(c, &c->d_vjp_part, &c->vjp_part_bytes, sizeof(double) * kn * ((E + grape::kVjpGroup - 1) / grape::kVjpGroup), who, "the groups' rows");
+    VjpMultiScope scope(c, multi ? n_set : 0);
+    const size_t ns = multi ? (size_t)n_set : 1, kn = KN(c), kp = KP(c);
+    rc = vjp_grow_sums(c, who, ns, pulse_map(c));
     if (rc) return rc;
-    if (pulse_map(c)) {
-        rc = grow(c, &c->d_vjp_g, &c->vjp_g_bytes, sizeof(double) * (kn + 1), who, "the summed row");
-        if (rc) return rc;
-        rc = grow(c, &c->d_vjp_out, &c->vjp_out_bytes, sizeof(double) * (kp + 1), who, "the projected row");
-        if (rc) return rc;
-    }
     c->vjp_n = n_obs;
     c->vjp_per_member = per_member;
     c->vjp_has_y = d_ybar != nullptr;
@@ -3998,6 +4077,7 @@ extern "C" int grape_eval_vjp_device(grape_ctx *c, const double *d_x, int32_t n_
     c->vjp_ybar_call = (const double2 *)d_ybar;
     c->vjp_xbar_call = (const double2 *)d_Xbar_final;
     c->vjp_G_call = pulse_map(c) ? c->d_vjp_g : d_G;          // (no pulse map: the groups' sums ARE G)
+    c->vjp_G_step = pulse_map(c) ? kn + 1 : kn;
     c->vjp_staged = d_ybar ? traj_staged_bytes(c, n_obs, true) : 0;
     if (!reuse) {
         c->vjp_on = true;                                    // enqueue_eval's member blocks end in the two kernels of vjp.hip
@@ -4006,7 +4086,7 @@ extern "C" int grape_eval_vjp_device(grape_ctx *c, const double *d_x, int32_t n_
         if (rc) return rc;
     } else {
         // the propagators (and the slope array) of the last device form are in place: the pull-back alone
-        rc = rc_ensure(c);                                   // (the rows, and the states of the general flow)
+        rc = vjp_rows_ensure(c);                             // (the rows, and the states of the general flow)
         if (rc) return rc;
         if (traj_exact(c)) {                                 // (the pulse is in place; the blocks, after a read-out alone)
             rc = traj_exact_ensure(c, who);
@@ -4022,18 +4102,37 @@ extern "C" int grape_eval_vjp_device(grape_ctx *c, const double *d_x, int32_t n_
         HIP_TRY(c, launch_small_family(c, 0, mode, v, st));
     }
     if (pulse_map(c)) {
-        // the summed physical row -> the coordinates of x, straight into the caller's G (no F slot: BasisOp::no_f)
+        // the summed physical rows -> the coordinates of x, straight into the caller's G (no F slot: BasisOp::no_f)
         KernelLogScope log_scope(&c->kernel_log, true);
         grape::BasisOp op = basis_op(c, true, 1);
         op.no_f = 1;
         grape::DoneSignal d;
         d.basis = &op;
-        HIP_TRY(c, grape::launch_copy(c->d_vjp_g, d_G, (int)kp, st, d));
+        for (size_t r = 0; r < ns; ++r)
+            HIP_TRY(c, grape::launch_copy(c->d_vjp_g + r * (kn + 1), d_G + r * kp, (int)kp, st, d));
     }
     HIP_TRY(c, hipEventRecord(c->ev_dev, st));
     c->dev_pending = true;
     c->traj_valid = !chunked(c);
     return GRAPE_OK;
+}
+
+extern "C" int grape_eval_vjp_device(grape_ctx *c, const double *d_x, int32_t n_obs, int32_t per_member, const double *d_O,
+                                     const double *d_ybar, const double *d_Xbar_final, double *d_G, void *stream)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp_device: null context");
+    return eval_vjp_device(c, "grape_eval_vjp_device", false, d_x, 0, n_obs, per_member, d_O, d_ybar, d_Xbar_final, d_G, stream);
+}
+
+extern "C" int grape_eval_vjp_multi_device(grape_ctx *c, const double *d_x, int32_t n_set, int32_t n_obs, int32_t per_member,
+                                           const double *d_O, const double *d_ybar, const double *d_Xbar_final, double *d_G,
+                                           void *stream)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp_multi_device: null context");
+    return eval_vjp_device(c, "grape_eval_vjp_multi_device", true, d_x, n_set, n_obs, per_member, d_O, d_ybar, d_Xbar_final, d_G,
+                           stream);
 }
 
 // ---- grape_eval_jvp: one evaluation + the push-forward of the caller's direction along its trajectory ------------------------

@@ -265,6 +265,17 @@ struct SweepParams {
     const double2 *hvp_ybar_dot;    // (N + 1, vjp_n, vjp_Etot), nullable (zero): the tangent of vjp_ybar
     const double2 *hvp_xbar_dot;    // (n, m, vjp_Etot), nullable (zero): the tangent of vjp_xbar
     double2 *hvp_xs;                // general flow: [X_{t+1} | Xdot_{t+1}] per slice, chunk-major like props, 2 n m elements per slice
+    // grape_eval_vjp_multi (vjp.hip): a vjp_only launch with vjp_nset > 0 pulls vjp_nset cotangent sets back.  Set r reads
+    // vjp_ybar + r vjp_set_ybar / vjp_xbar + r vjp_set_xbar, writes its members' rows at vjp_rows + r vjp_set_rows, its groups'
+    // sums at vjp_part + r vjp_set_part and (vjp_only = 2) its summed row at vjp_G + r vjp_set_G (elements of the arrays' own
+    // types); the probes are shared.  vjp_multi != 0: trajectory_vjp_multi_kernel in blocks of vjp_multi_block(n, m) sets
+    // where an instance serves the launch (at most 256 time chunks per member, first-order mode), else (and with 0) the
+    // single call's kernels once per set -- the same bits either way; 1 leaves a block of ONE set to the single kernel,
+    // 2 (GRAPE_VJP_MULTI=1) forces the multi kernel for every block.  vjp_nset = 0: the single call (and grape_eval_hvp),
+    // which reads none of these.  (Appended.)
+    int32_t vjp_nset;
+    int32_t vjp_multi;
+    int64_t vjp_set_ybar, vjp_set_xbar, vjp_set_rows, vjp_set_part, vjp_set_G;
 };
 // A member's image record: what the lane-pair sweep's prologue puts into LDS, laid out as the LDS holds it.
 //   [0, 2 PS)        both parity images of A', B'_c, B'_c^T, Xi, Xt, Xi Xt' (every mode but the anti-Hermitian sweep), pads zero
@@ -286,6 +297,27 @@ constexpr int jvp_multi_block(int n, int m)
 constexpr bool jvp_multi_default(int n, int m)
 {
     return jvp_multi_block(n, m) > 0;
+}
+// grape_eval_vjp_multi: the cotangent sets trajectory_vjp_multi_kernel (trajectory_vjp_kernel<n, m, ..., RB> at RB > 1) carries
+// per launch (RB: the largest block per shape, up to GRAPE_MAX_VJP_COTANGENTS, that compiles without scratch and without
+// spills to memory at 256 threads in both flows; 0: no instance, the single kernel per set), its workgroup size
+// limit, and whether the shape dispatches to it by default (where it measured faster per set than
+// the single kernel by more than the spread, profiles/r21_vjp_multi_time.txt; GRAPE_VJP_MULTI=0/1 forces)
+constexpr int kVjpMultiMaxThreads = 256;
+constexpr int vjp_multi_block(int n, int m)
+{
+    return n == 2 ? 8 : n == 3 ? (m == 1 ? 8 : m == 2 ? 6 : 3) : n == 4 ? (m == 1 ? 8 : m == 2 ? 3 : m <= 4 ? 2 : 0) : 0;
+}
+// whether the unitary-flow multi instance at (n, m) parks X at the chunk end in dynamic LDS across the suffix scan (vjp.hip)
+constexpr bool vjp_multi_stash(int n, int m) { return n == 4 && m == 4; }
+// Measured at 4 probes and 4 sets per call, per set, multi against single (us; unitary | general flow): <4,4> 134.0 / 116.3 |
+// 158.9 / 160.7, <2,2> 51.3 / 35.2 | 54.5 / 46.1, <3,3> 72.3 / 61.0 | 81.9 / 84.2, <4,1> 100.9 / 86.1 | 107.2 / 114.5, spread
+// <= 0.9: no shape is faster in both flows (the device form's single call stages ybar through LDS up to 8 probes, the multi
+// instance reads it strided), so no shape dispatches to the multi kernel by default.  GRAPE_VJP_MULTI=1 reaches it: it wins at
+// the headline shape with 1 and with 16 probes (0.84 and 0.90 of the single kernels' time per set) and in the general flow.
+constexpr bool vjp_multi_default(int n, int m)
+{
+    return false && vjp_multi_block(n, m) > 0;
 }
 // workgroup size limit of the kernels that run behind the small-n sweeps (running_cost.hip, observe.hip, vjp.hip, jvp.hip;
 // RcTraits<n>::MAXT): the chunk count of the largest decomposition the sweeps of this n run with

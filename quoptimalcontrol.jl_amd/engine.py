@@ -29,6 +29,7 @@ FLAG_TIME_SAMPLED = 64
 FLAG_GROUP_PEER_SUM = 128
 MAX_DEVICES = 8
 MAX_JVP_DIRECTIONS = 8                                     # GRAPE_MAX_JVP_DIRECTIONS
+MAX_VJP_COTANGENTS = 8                                     # GRAPE_MAX_VJP_COTANGENTS
 ABI_VERSION = 8
 
 STATUS = {0: "GRAPE_OK", -1: "GRAPE_ERR_INVALID_ARG", -2: "GRAPE_ERR_UNSUPPORTED",
@@ -45,6 +46,7 @@ EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_oper
            "grape_eval", "grape_eval_device", "grape_eval_batch", "grape_eval_batch_device", "grape_eval_fom", "grape_eval_observables",
            "grape_eval_vjp", "grape_eval_observables_device", "grape_eval_vjp_device", "grape_eval_jvp", "grape_eval_jvp_device",
            "grape_eval_jvp_multi", "grape_eval_jvp_multi_device", "grape_eval_hvp", "grape_eval_hvp_device",
+           "grape_eval_vjp_multi", "grape_eval_vjp_multi_device",
            "grape_set_trajectory_derivative", "grape_set_running_cost_derivative",
            "grape_lbfgs", "grape_lbfgs_get_trace",
            "grape_get_member_results", "grape_get_trajectory",
@@ -151,6 +153,8 @@ def load_library():
     L.grape_eval_vjp_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.grape_eval_jvp.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp]
     L.grape_eval_jvp_device.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    L.grape_eval_vjp_multi.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
+    L.grape_eval_vjp_multi_device.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
     L.grape_eval_jvp_multi.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp]
     L.grape_eval_jvp_multi_device.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
     L.grape_eval_hvp.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
@@ -929,6 +933,144 @@ class GrapeEngine:
         if final:
             return yd, Xf.transpose(-1, -2).contiguous()
         return yd
+
+    def observe_vjp_multi(self, x, ops, ybars=None, xbars_final=None, per_member=False):
+        """grape_eval_vjp_multi: observe_vjp for several cotangent sets behind ONE evaluation of x.  ybars (n_set, E, n_obs, N+1)
+        and xbars_final (n_set, E, n, m), either None (zero) for all sets, not both; the probes are shared by the sets.
+        Returns G (n_set, K, cols); block r is bit for bit observe_vjp(x, ops, ybars[r], xbars_final[r]).  More than
+        MAX_VJP_COTANGENTS = 8 sets are walked in blocks of 8 (one evaluation each)."""
+        x = np.asarray(x, dtype=np.float64)
+        if x.shape != (self.K, self._cols):
+            raise ValueError(f"x must be ({self.K},{self._cols})")
+        n, m, E, N = self.n, self.m, self.E, self.N
+        if ybars is None and xbars_final is None:
+            raise ValueError("observe_vjp_multi: nothing to pull back (ybars and xbars_final are both None)")
+        if ops is None and ybars is not None:
+            raise ValueError("observe_vjp_multi: ybars needs the probes it belongs to")
+        n_obs, O = self._jvp_probes("observe_vjp_multi", ops if ybars is not None else None, per_member)
+        Of = None if O is None else _cm(np.swapaxes(O, 0, 1) if per_member else O)
+        yb = xb = None
+        if ybars is not None:
+            yb = np.ascontiguousarray(ybars, dtype=np.complex128)
+            if yb.ndim != 4 or yb.shape[1:] != (E, n_obs, N + 1) or yb.shape[0] < 1:
+                raise ValueError(f"observe_vjp_multi: ybars must be (n_set, {E},{n_obs},{N + 1}) with n_set >= 1")
+        if xbars_final is not None:
+            xb = np.asarray(xbars_final, dtype=np.complex128)
+            if xb.ndim != 4 or xb.shape[1:] != (E, n, m) or xb.shape[0] < 1:
+                raise ValueError(f"observe_vjp_multi: xbars_final must be (n_set, {E},{n},{m}) with n_set >= 1")
+            xb = _cm(xb)
+        if yb is not None and xb is not None and yb.shape[0] != xb.shape[0]:
+            raise ValueError("observe_vjp_multi: ybars and xbars_final differ in n_set")
+        n_set = (yb if yb is not None else xb).shape[0]
+        G = np.empty((n_set, self._cols, self.K))
+        xf = np.ascontiguousarray(x.T)
+        for r0 in range(0, n_set, MAX_VJP_COTANGENTS):
+            r1 = min(n_set, r0 + MAX_VJP_COTANGENTS)
+            part = lambda a: None if a is None else a[r0:r1]
+            self._check(self._lib.grape_eval_vjp_multi(self._h, _p(xf), r1 - r0, n_obs, 1 if per_member else 0, _p(Of),
+                                                       _p(part(yb)), _p(part(xb)), _p(G[r0:r1])))
+        return np.ascontiguousarray(np.swapaxes(G, 1, 2))
+
+    def observe_vjp_multi_device(self, x, ops, ybars=None, xbars_final=None, per_member=False, stream=0):
+        """grape_eval_vjp_multi_device on CUDA tensors of the context's GPU: x float64 (K, cols), or None for reuse -- along the
+        trajectory the last device form left in the workspace, without a sweep (GrapeError NOT_READY when anything else has
+        touched the context since, or under a member chunk); ops complex128 as in observe_vjp (None with xbars_final alone);
+        ybars complex128 (n_set, E, n_obs, N+1) and xbars_final complex128 (n_set, E, n, m), either None, not both.  Returns
+        the CUDA tensor G (n_set, K, cols), written asynchronously on `stream` (0: the default stream; the layout copies of
+        the inputs run on torch's current stream, which must be the same or ordered in front of it).  More than 8 sets are
+        walked in blocks of 8, the blocks behind the first one by reuse.  Non-finite device entries are not checked."""
+        import torch
+
+        K, cols, n, m, E, N = self.K, self._cols, self.n, self.m, self.E, self.N
+        who = "observe_vjp_multi_device"
+        if x is not None and (not x.is_cuda or x.dtype != torch.float64 or tuple(x.shape) != (K, cols)):
+            raise ValueError(f"{who}: x must be a CUDA float64 tensor ({K},{cols}) or None")
+        if ybars is None and xbars_final is None:
+            raise ValueError(f"{who}: nothing to pull back (ybars and xbars_final are both None)")
+        n_obs, d_O = 0, None
+        if ybars is not None:
+            if ops is None:
+                raise ValueError(f"{who}: ybars needs the probes it belongs to")
+            if not ops.is_cuda or ops.dtype != torch.complex128:
+                raise ValueError(f"{who}: ops must be a CUDA complex128 tensor")
+            O = ops[None] if (not per_member and ops.dim() == 2) else ops
+            want = (E, O.shape[1] if O.dim() == 4 else 0, n, m) if per_member else (O.shape[0] if O.dim() == 3 else 0, n, m)
+            if tuple(O.shape) != want or not 1 <= O.shape[-3] <= 16:
+                raise ValueError(f"{who}: ops must be {'(E, n_obs, n, m)' if per_member else '(n_obs, n, m)'} "
+                                 f"with E = {E}, n = {n}, m = {m} and 1 <= n_obs <= 16")
+            n_obs = O.shape[-3]
+            # column-major (n, m, [E,] n_obs): the probe index slowest, then the member
+            d_O = (O.transpose(0, 1) if per_member else O).transpose(-1, -2).contiguous()
+            if not ybars.is_cuda or ybars.dtype != torch.complex128 or ybars.dim() != 4 \
+                    or tuple(ybars.shape[1:]) != (E, n_obs, N + 1) or ybars.shape[0] < 1:
+                raise ValueError(f"{who}: ybars must be a CUDA complex128 tensor (n_set, {E},{n_obs},{N + 1}) with n_set >= 1")
+        if xbars_final is not None and (not xbars_final.is_cuda or xbars_final.dtype != torch.complex128 or xbars_final.dim() != 4
+                                        or tuple(xbars_final.shape[1:]) != (E, n, m) or xbars_final.shape[0] < 1):
+            raise ValueError(f"{who}: xbars_final must be a CUDA complex128 tensor (n_set, {E},{n},{m}) with n_set >= 1")
+        if ybars is not None and xbars_final is not None and ybars.shape[0] != xbars_final.shape[0]:
+            raise ValueError(f"{who}: ybars and xbars_final differ in n_set")
+        n_set = (ybars if ybars is not None else xbars_final).shape[0]
+        d_x = None if x is None else x.t().contiguous()
+        d_yb = None if ybars is None else ybars.contiguous()
+        d_xb = None if xbars_final is None else xbars_final.transpose(-1, -2).contiguous()
+        G = torch.empty((n_set, cols, K), dtype=torch.float64, device=(ybars if ybars is not None else xbars_final).device)
+        reuse_ok = n_set <= MAX_VJP_COTANGENTS or self._jacobian_reuse()     # (a member chunk: every block carries x)
+        for r0 in range(0, n_set, MAX_VJP_COTANGENTS):
+            r1 = min(n_set, r0 + MAX_VJP_COTANGENTS)
+            ptr = lambda t: C.c_void_p(0 if t is None else t[r0:r1].data_ptr())
+            first = d_x is not None and (r0 == 0 or not reuse_ok)
+            self._check(self._lib.grape_eval_vjp_multi_device(self._h, C.c_void_p(d_x.data_ptr() if first else 0), r1 - r0, n_obs,
+                                                              1 if per_member else 0,
+                                                              C.c_void_p(0 if d_O is None else d_O.data_ptr()), ptr(d_yb), ptr(d_xb),
+                                                              ptr(G), C.c_void_p(stream)))
+        self._vjp_multi_keep = (d_x, d_O, d_yb, d_xb)        # (alive until the stream has passed the call)
+        return G.transpose(1, 2).contiguous()
+
+    def trajectory_jacobian_rows(self, x, ops, rows, per_member=False):
+        """Rows of the Jacobian of observe(x, ops) in reverse mode, the twin of trajectory_jacobian: `rows` is a list of
+        (member, probe, slice) triples, the result J (n_rows, K, cols) is complex with J[r] = d y[member, probe, slice] / d x.
+        Each row is two unit cotangents (1: the real part's gradient, i: the imaginary part's), so a block of 8 cotangent
+        sets serves 4 rows; the first block carries x, the rest reuse its trajectory (member-chunked contexts: every block
+        carries x).  It pays off where there are fewer residuals than controls.  In the derivative mode of
+        set_trajectory_derivative."""
+        x = np.asarray(x, dtype=np.float64)
+        if x.shape != (self.K, self._cols):
+            raise ValueError(f"x must be ({self.K},{self._cols})")
+        O = np.asarray(ops)
+        n_obs = 1 if (not per_member and O.ndim == 2) else O.shape[-3]
+        rows = [tuple(int(v) for v in r) for r in rows]
+        if not rows:
+            raise ValueError("trajectory_jacobian_rows: no rows")
+        for r in rows:
+            if len(r) != 3 or not (0 <= r[0] < self.E and 0 <= r[1] < n_obs and 0 <= r[2] <= self.N):
+                raise ValueError(f"trajectory_jacobian_rows: row {r} is not a (member < {self.E}, probe < {n_obs}, "
+                                 f"slice <= {self.N}) triple")
+        reuse_ok = self._jacobian_reuse()
+        per_block = MAX_VJP_COTANGENTS // 2
+        out = []
+        for b in range(0, len(rows), per_block):
+            block = rows[b:b + per_block]
+            ybars = np.zeros((2 * len(block), self.E, n_obs, self.N + 1), np.complex128)
+            for i, (k, j, s) in enumerate(block):
+                ybars[2 * i, k, j, s] = 1.0
+                ybars[2 * i + 1, k, j, s] = 1.0j
+            G = self._jacobian_rows_block(x, b == 0 or not reuse_ok, ybars, ops, per_member)
+            out.append(G[0::2] + 1j * G[1::2])
+        return np.concatenate(out, axis=0)
+
+    def _jacobian_rows_block(self, x, carry_x, ybars, ops, per_member):
+        """one block of trajectory_jacobian_rows through the device form: G (len(ybars), K, cols) as a NumPy array"""
+        import torch
+
+        dev = torch.device("cuda", self.info["device"])
+        state = getattr(self, "_jacobian_rows_dev", None)
+        if carry_x or state is None:                         # (x and the probes go up once per walk)
+            state = self._jacobian_rows_dev = (torch.as_tensor(x, device=dev),
+                                               torch.as_tensor(np.asarray(ops, np.complex128), device=dev))
+        G = self.observe_vjp_multi_device(state[0] if carry_x else None, state[1], torch.as_tensor(ybars, device=dev),
+                                          per_member=per_member)
+        torch.cuda.synchronize(dev)
+        return G.cpu().numpy()
 
     def trajectory_jacobian(self, x, ops, columns=None, per_member=False):
         """dy/dx of observe(x, ops) for the listed flat indices of x (row-major over (K, cols); all by default): an array
