@@ -781,6 +781,47 @@ int grape_eval_hvp_device(grape_ctx *ctx, const double *d_x, const double *d_xdo
                           const double *d_O, const double *d_ybar, const double *d_Xbar_final, const double *d_ybar_dot,
                           const double *d_Xbar_final_dot, double *d_Gdot, void *stream);
 
+/* ABI v8 (additive).  The ensemble-averaged host forms of the trajectory read-out, its pull-back and its push-forward: the
+ * member axis of y / ybar / ydot never crosses the bus.  What an experiment on an inhomogeneously broadened ensemble measures
+ * is sum_k v_k y[k]; a loss on it has the cotangent ybar[k] = v_k ybar_mean, ONE block broadcast over the members.
+ *   x, xdot, n_obs, per_member, O, F, G   exactly as in grape_eval_observables / grape_eval_vjp / grape_eval_jvp (x is theta / u
+ *                   under grape_set_basis / grape_set_bounds and G is in x's coordinates; both trajectory-derivative modes)
+ *   v               host f64 [E], the weights of the sum; NULL: the ensemble weights w_k as grape_set_operators received them
+ *                   (their device copy is read).  grape_set_risk does not enter: a caller who wants the risk weights passes
+ *                   grape_get_risk_weights' output.  Zero and negative entries are accepted
+ *   y_mean, ybar_mean, ydot_mean   host c128 (N+1, n_obs) column-major; ybar_mean in grape_eval_vjp's cotangent convention
+ *                   (dl/dRe + i dl/dIm of the AVERAGED value)
+ *   X_mean, Xbar_mean, Xdot_mean   host c128 (n, m) column-major
+ * Nullability follows the call each form sits on: at least one of the pair; n_obs = 0 with a non-NULL y-type array is invalid.
+ *   y_mean[s + (N+1) j] = sum_k v_k y[s + (N+1)(j + n_obs k)],   X_mean = sum_k v_k X_{k,N}
+ * and the same sums of grape_eval_jvp's ydot / Xdot_final.  F of the read-out is grape_eval's F bit for bit.
+ * grape_eval_vjp_mean returns, BIT FOR BIT, the G grape_eval_vjp returns for the explicit cotangents
+ *   ybar[s,j,k] = (v_k Re ybar_mean[s,j], v_k Im ybar_mean[s,j]),   Xbar_k = (v_k Re Xbar_mean, v_k Im Xbar_mean)
+ * -- each component one rounded product: traj_mean_broadcast_kernel writes exactly those arrays into the buffers the
+ * pull-back kernels read, in front of the evaluation, and everything behind it is grape_eval_vjp.
+ * The sums: traj_mean_reduce_kernel cuts the member axis into segments of 16 consecutive members and sums each in member
+ * order (the first term a product, every further one an FMA), one lane per complex entry; with more than one segment
+ * traj_mean_combine_kernel adds the segments' sums in segment order.  No atomics.  The tree depends on E alone -- not on N,
+ * n_obs, the probe index, the member chunk or the sweep's workgroup layout -- so results are bitwise reproducible, a
+ * member-chunked context returns the unchunked context's bits, and column j of a 16-probe call is the 1-probe call with
+ * probe j.  E = 1 with v = {1.0} returns y[0].  Each component differs from the exact sum by at most
+ * E 2^-53 sum_k |v_k| |component_k| to first order.  The reduction runs once, behind the read-out (push-forward) of the last
+ * member block; afterwards grape_get_kernel_names includes the kernels named here.
+ * Host forms ONLY: there is no _device form, no multi form and no HVP form.  A caller with device tensors already holds y on
+ * the GPU and averages it there.
+ * Served and refused exactly where the underlying call is, with its words behind this call's name: the context's refusals
+ * first (GRAPE_ERR_UNSUPPORTED), then the arguments.  GRAPE_ERR_INVALID_ARG: what the underlying call refuses, a non-finite
+ * entry of v, ybar_mean or Xbar_mean ("not finite"), and for grape_eval_vjp_mean a product v_k ybar_mean / v_k Xbar_mean that
+ * overflows ("not finite").  Before grape_set_operators: GRAPE_ERR_NOT_READY.  After any refusal the context evaluates exactly
+ * as before; a context that never calls these launches the kernels it always did; eval -> *_mean -> eval returns the first
+ * evaluation's bits.  Blocking, ordered behind an in-flight grape_eval_device. */
+int grape_eval_observables_mean(grape_ctx *ctx, const double *x, int32_t n_obs, int32_t per_member, const double *O,
+                                const double *v, double *y_mean, double *X_mean, double *F);
+int grape_eval_vjp_mean(grape_ctx *ctx, const double *x, int32_t n_obs, int32_t per_member, const double *O,
+                        const double *v, const double *ybar_mean, const double *Xbar_mean, double *G);
+int grape_eval_jvp_mean(grape_ctx *ctx, const double *x, const double *xdot, int32_t n_obs, int32_t per_member,
+                        const double *O, const double *v, double *ydot_mean, double *Xdot_mean);
+
 /* ABI v8 (additive).  The derivative rule of the pull-back and the push-forward along the trajectory: all six entry points --
  * grape_eval_vjp, grape_eval_vjp_device, grape_eval_jvp, grape_eval_jvp_device and the d_x = NULL reuse forms of both device
  * calls.  GRAPE_TRAJ_FIRST_ORDER (the default) takes dP_t/dx[c,t] as (-i dt B_c) P_t, as documented above.  GRAPE_TRAJ_EXACT

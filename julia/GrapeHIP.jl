@@ -280,6 +280,67 @@ function observables_jvp(ctx::GrapeContext, x::Matrix{Float64}, xdot::Matrix{Flo
     ydot, Xdf
 end
 
+# The ensemble-averaged host forms (grape_eval_observables_mean / _vjp_mean / _jvp_mean): the member axis is summed (or, for the
+# cotangent, broadcast) on the device, y_mean[s+1, j] = sum_k v[k] y[s+1, j, k], X_mean = sum_k v[k] X_final[:, :, k].
+# v (E): the weights; `nothing`: the ensemble weights the context was given.  O as in `observables`.  The summation order depends
+# on E alone (bitwise reproducible; column j of a 16-probe call is the 1-probe call with probe j).  (Written, NOT executed, like
+# `observables`; the Python binding makes the same calls and is tested on the GPU.)
+function _mean_probes(ctx::GrapeContext, who::String, O::Array{ComplexF64}, v::Union{Nothing,Vector{Float64}})
+    n_obs = size(O, ndims(O))
+    (ndims(O) == 3 && size(O) == (ctx.n, ctx.m, n_obs)) || (ndims(O) == 4 && size(O) == (ctx.n, ctx.m, ctx.E, n_obs)) ||
+        throw(DimensionMismatch("O must be (n, m, n_obs) or (n, m, E, n_obs) with the context's n, m and E"))
+    1 <= n_obs <= 16 || throw(ArgumentError("$who: 1 to 16 probes"))
+    v === nothing || length(v) == ctx.E || throw(DimensionMismatch("v must have one entry per member"))
+    n_obs, Int32(ndims(O) == 4 ? 1 : 0), (v === nothing ? Ptr{Float64}(C_NULL) : pointer(v))
+end
+
+"Returns (y_mean (N+1, n_obs), X_mean (n, m), F) with F bit for bit fom_and_gradient!'s."
+function observables_mean(ctx::GrapeContext, x::Matrix{Float64}, O::Array{ComplexF64}; v::Union{Nothing,Vector{Float64}} = nothing)
+    size(x) == (ctx.K, ctx.N) || throw(DimensionMismatch("x must be (n_controls, n_slices)"))
+    n_obs, pm, p_v = _mean_probes(ctx, "observables_mean", O, v)
+    y = Array{ComplexF64}(undef, ctx.N + 1, n_obs)
+    Xm = Array{ComplexF64}(undef, ctx.n, ctx.m)
+    F = Ref{Float64}(NaN)
+    GC.@preserve x O v y Xm check(ctx, ccall((:grape_eval_observables_mean, libgrape), Cint,
+                                             (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{ComplexF64}, Ptr{Float64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Ref{Float64}),
+                                             ctx.handle, x, Int32(n_obs), pm, O, p_v, y, Xm, F))
+    y, Xm, F[]
+end
+
+"The gradient (K, N) of a loss on `observables_mean`'s returns from its cotangents ybar_mean (N+1, n_obs) and Xbar_mean (n, m)
+(either may be `nothing`, not both): bit for bit grape_eval_vjp with ybar[:, :, k] = v[k] ybar_mean, component by component."
+function observables_vjp_mean(ctx::GrapeContext, x::Matrix{Float64}, O::Array{ComplexF64},
+                              ybar_mean::Union{Nothing,Matrix{ComplexF64}}, Xbar_mean::Union{Nothing,Matrix{ComplexF64}};
+                              v::Union{Nothing,Vector{Float64}} = nothing)
+    size(x) == (ctx.K, ctx.N) || throw(DimensionMismatch("x must be (n_controls, n_slices)"))
+    (ybar_mean === nothing && Xbar_mean === nothing) && throw(ArgumentError("observables_vjp_mean: both cotangents are nothing"))
+    n_obs, pm, p_v = _mean_probes(ctx, "observables_vjp_mean", O, v)
+    ybar_mean === nothing || size(ybar_mean) == (ctx.N + 1, n_obs) || throw(DimensionMismatch("ybar_mean must be (N+1, n_obs)"))
+    Xbar_mean === nothing || size(Xbar_mean) == (ctx.n, ctx.m) || throw(DimensionMismatch("Xbar_mean must be (n, m)"))
+    p_y = ybar_mean === nothing ? Ptr{ComplexF64}(C_NULL) : pointer(ybar_mean)
+    p_X = Xbar_mean === nothing ? Ptr{ComplexF64}(C_NULL) : pointer(Xbar_mean)
+    G = Matrix{Float64}(undef, ctx.K, ctx.N)
+    GC.@preserve x O v ybar_mean Xbar_mean G check(ctx, ccall((:grape_eval_vjp_mean, libgrape), Cint,
+                                                              (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{ComplexF64}, Ptr{Float64}, Ptr{ComplexF64}, Ptr{ComplexF64}, Ptr{Float64}),
+                                                              ctx.handle, x, Int32(ybar_mean === nothing ? 0 : n_obs), pm,
+                                                              ybar_mean === nothing ? Ptr{ComplexF64}(C_NULL) : pointer(O), p_v, p_y, p_X, G))
+    G
+end
+
+"Returns (ydot_mean (N+1, n_obs), Xdot_mean (n, m)): `observables_jvp`'s tangents summed over the members with v."
+function observables_jvp_mean(ctx::GrapeContext, x::Matrix{Float64}, xdot::Matrix{Float64}, O::Array{ComplexF64};
+                              v::Union{Nothing,Vector{Float64}} = nothing)
+    size(x) == (ctx.K, ctx.N) || throw(DimensionMismatch("x must be (n_controls, n_slices)"))
+    size(xdot) == size(x) || throw(DimensionMismatch("xdot must have the shape of x"))
+    n_obs, pm, p_v = _mean_probes(ctx, "observables_jvp_mean", O, v)
+    ydot = Array{ComplexF64}(undef, ctx.N + 1, n_obs)
+    Xdm = Array{ComplexF64}(undef, ctx.n, ctx.m)
+    GC.@preserve x xdot O v ydot Xdm check(ctx, ccall((:grape_eval_jvp_mean, libgrape), Cint,
+                                                      (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{ComplexF64}, Ptr{Float64}, Ptr{ComplexF64}, Ptr{ComplexF64}),
+                                                      ctx.handle, x, xdot, Int32(n_obs), pm, O, p_v, ydot, Xdm))
+    ydot, Xdm
+end
+
 # grape_eval_jvp_device: the same on device memory of the context's GPU (raw device pointers, e.g. of AMDGPU.jl arrays in the
 # layouts above; C_NULL for an output that is not wanted, not both), asynchronous on `stream`.  d_x = C_NULL pushes d_xdot forward
 # along the trajectory the last device form left in the workspace, without a sweep.

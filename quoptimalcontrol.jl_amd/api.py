@@ -480,13 +480,15 @@ def test_pulse(prob, pulse_or_solres, engine=None):
 test_pulse.__test__ = False                    # (a library function, not a test: keep pytest from collecting it)
 
 
-def expectation_values(prob, pulse, ops, engine=None):
+def expectation_values(prob, pulse, ops, engine=None, mean=False):
     """What src/visualisation.jl:13-51 computes (commented out there): the expectation values of `ops` along the pulse.
     ops: (n_obs, n, m) matrices (or one (n, m) matrix), at most 16.  Returns (times (N+1,), y (E, n_obs, N+1)) with
-    y[k, j, s] = tr(ops[j]' X_ks) from the device; y.real is what visualise_expt_vals plots against the times."""
+    y[k, j, s] = tr(ops[j]' X_ks) from the device; y.real is what visualise_expt_vals plots against the times.
+    mean=True: (times, y_mean (n_obs, N+1)) with y_mean = sum_k wts_k y[k], the curve of an EnsembleProblem under its own
+    weights, summed on the device (GrapeEngine.observe_mean): the member axis is never copied to the host."""
     eng, own, pulse, _ = _observe_setup(prob, pulse, engine)
     try:
-        y = eng.observe(pulse, ops)
+        y = eng.observe_mean(pulse, ops) if mean else eng.observe(pulse, ops)
         times = np.linspace(0.0, eng.T, eng.N + 1)
     finally:
         if own:

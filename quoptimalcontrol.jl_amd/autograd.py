@@ -27,6 +27,10 @@ so torch.autograd.grad(..., create_graph=True) and torch.autograd.functional.hvp
 (y, X_final) -- first order in dt, engines without bounds in the first-order derivative mode.  twice=False (the default) is the
 once-differentiable function it always was.
 
+trajectory_mean is trajectory for a loss on the ENSEMBLE-AVERAGED read-out, sum_k v_k y[k] (what an experiment on an
+inhomogeneously broadened ensemble measures): the sum, the broadcast of its cotangent and the sum of the tangents run on the
+device (GrapeEngine.observe_mean / observe_vjp_mean / observe_jvp_mean), so the member axis never crosses the bus.
+
 trajectory_device is the same for a workflow that lives on the GPU (once differentiable): x, y, X_final, the loss and x.grad are CUDA tensors on the
 engine's device, the read-out and the pull-back run on torch's current stream (GrapeEngine.observe_device /
 observe_vjp_device) and nothing crosses to the host.
@@ -175,6 +179,58 @@ def trajectory(engine, x, ops, per_member=False, final=True, twice=False):
     if twice:
         return _TrajectoryTwice.apply(x, engine, ops, bool(per_member), bool(final))
     return _Trajectory.apply(x, engine, ops, bool(per_member), bool(final))
+
+
+class _TrajectoryMean(torch.autograd.Function):
+    """(y_mean, X_mean) = observe_mean(x); backward = observe_vjp_mean, jvp = observe_jvp_mean: the member axis stays on the
+    device in all three directions (include/grape_hip.h: grape_eval_observables_mean / _vjp_mean / _jvp_mean)."""
+
+    @staticmethod
+    def forward(ctx, x, engine, ops, v, per_member, final):
+        xn = x.detach().numpy()
+        out = engine.observe_mean(xn, ops, v=v, per_member=per_member, final=final)
+        y, Xm = out if final else (out, None)
+        ctx.engine, ctx.ops, ctx.v, ctx.per_member, ctx.final = engine, ops, v, per_member, final
+        ctx.xn = np.array(xn, copy=True)
+        ctx.set_materialize_grads(False)
+        y_t = torch.from_numpy(y)
+        if final:
+            return y_t, torch.from_numpy(Xm)
+        return y_t
+
+    @staticmethod
+    def backward(ctx, ybar, xbar=None):
+        if ybar is None and xbar is None:
+            return None, None, None, None, None, None
+        yb = None if ybar is None else ybar.detach().resolve_conj().numpy()
+        xb = None if xbar is None else xbar.detach().resolve_conj().numpy()
+        G = ctx.engine.observe_vjp_mean(ctx.xn, ctx.ops, ybar_mean=yb, xbar_mean=xb, v=ctx.v, per_member=ctx.per_member)
+        return torch.from_numpy(G), None, None, None, None, None
+
+    @staticmethod
+    def jvp(ctx, xdot, *_):
+        """forward mode: the tangents of (y_mean, X_mean) -- of y_mean alone with final=False -- along the tangent of x"""
+        xd = xdot.detach().numpy()
+        out = ctx.engine.observe_jvp_mean(ctx.xn, xd, ctx.ops, v=ctx.v, per_member=ctx.per_member, final=ctx.final)
+        if ctx.final:
+            return torch.from_numpy(out[0]), torch.from_numpy(out[1])
+        return torch.from_numpy(out)
+
+
+def trajectory_mean(engine, x, ops, v=None, per_member=False, final=True):
+    """trajectory with the member axis summed on the device: y_mean (n_obs, N+1) = sum_k v_k y[k] and -- final=True -- X_mean
+    (n, m) = sum_k v_k X_final[k] of the pulse x, a CPU float64 tensor of the shape engine.eval takes, differentiable with respect
+    to x (backward and forward_ad).  v (E,): the weights, not differentiated; None: the engine's ensemble weights.  What a loss
+    on the averaged populations needs, at about the cost of its kernels: (N+1) n_obs numbers cross the bus in each direction
+    instead of (N+1) n_obs E.  Once differentiable; the engine's trajectory-derivative setting carries through as in trajectory."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.device.type != "cpu":
+        raise TypeError("trajectory_mean: x must be a CPU float64 tensor")
+    if ops is None:
+        raise ValueError("trajectory_mean: at least one probe is needed (GrapeEngine.observe_mean(final=True) gives X_mean alone)")
+    ops = np.array(ops.detach().numpy() if isinstance(ops, torch.Tensor) else ops, dtype=np.complex128, copy=True)
+    if v is not None:
+        v = np.array(v.detach().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64, copy=True)
+    return _TrajectoryMean.apply(x, engine, ops, v, bool(per_member), bool(final))
 
 
 def _dev_probes(ops, per_member):

@@ -162,6 +162,8 @@ __global__ __launch_bounds__(256) void bounds_slope_kernel(const BasisOp op, con
 
 hipError_t launch_basis(const BasisOp &op, const double *src, double *dst, hipStream_t stream, DoneSignal done)
 {
+    if (op.mean)                                             // the *_mean trajectory calls: traj_mean.hip stands in
+        return run_traj_mean(*op.mean, stream);
     if (op.K < 1 || op.K > 65535 || op.N < 1 || op.M < 0 || op.M > op.N || op.n_x < 1 || op.n_x > 65535 || !src || !dst)
         return hipErrorInvalidValue;
     if (op.M > 0 ? !op.phi : !op.bounded)                    // (M = 0, the identity expansion, exists for the bounds alone)

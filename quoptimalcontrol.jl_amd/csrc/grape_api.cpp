@@ -270,7 +270,18 @@ struct grape_ctx {
     double2 *d_hvp_xs = nullptr;
     size_t hvp_ybd_bytes = 0, hvp_xbd_bytes = 0, hvp_xs_bytes = 0;
     const double2 *hvp_ybd_call = nullptr, *hvp_xbd_call = nullptr;
-    int lds_cap = 0;                         // LDS bytes a workgroup of this device may hold (queried by the first device form)
+    // grape_eval_observables_mean / _vjp_mean / _jvp_mean (traj_mean.hip): mean_on is set by the entry point around ONE
+    // evaluation with obs_on / jvp_on / vjp_on.  Behind the read-out (push-forward) of the last member block the member
+    // reduction sums the host form's full-size arrays over the members into d_mean_io; in front of a pull-back the
+    // broadcast fills d_vjp_ybar / d_vjp_xbar from the caller's one block in d_mean_io.  The buffers are allocated by the
+    // first call that needs them and only ever grow; they belong to these blocking entry points alone.
+    bool mean_on = false;
+    const double *mean_v_call = nullptr;       // the weights of the call: d_mean_v, or d_wts (v = NULL)
+    double *d_mean_v = nullptr;                // [E]
+    double2 *d_mean_io = nullptr;              // [(N + 1) n_obs | n m]: the reduction's result / the broadcast's source
+    double2 *d_mean_part = nullptr;            // the segments' sums, ceil(E / kMeanSeg) rows of d_mean_io's length
+    size_t mean_v_bytes = 0, mean_io_bytes = 0, mean_part_bytes = 0;
+    int lds_cap = 0;                        // LDS bytes a workgroup of this device may hold (queried by the first device form)
     // The workspace holds the complete trajectory (every member's propagators, and the slope array of a pulse map) of the last
     // device form: grape_eval_vjp_device may pull back along it without a sweep (d_x == NULL).  Set by a successful device form
     // that ran an evaluation on a context that is not member-chunked; cleared by everything else that evaluates or changes a
@@ -685,6 +696,7 @@ static void free_all(grape_ctx *c)
     (void)hipFree(c->d_traj_w); (void)hipFree(c->d_traj_x);
     (void)hipFree(c->d_jvp_O); (void)hipFree(c->d_jvp_xdot); (void)hipFree(c->d_jvp_xphys); (void)hipFree(c->d_jvp_ydot); (void)hipFree(c->d_jvp_xf);
     (void)hipFree(c->d_hvp_ybd); (void)hipFree(c->d_hvp_xbd); (void)hipFree(c->d_hvp_xs);
+    (void)hipFree(c->d_mean_v); (void)hipFree(c->d_mean_io); (void)hipFree(c->d_mean_part);
     (void)hipFree(c->d_basis_phi); (void)hipFree(c->d_basis_x0);
     (void)hipFree(c->d_bounds); (void)hipFree(c->d_slope);
     (void)hipFree(c->d_fom_member); (void)hipFree(c->d_fom_rows);
@@ -2828,6 +2840,35 @@ static int jvp_tangent_map(grape_ctx *c, hipStream_t stream)
     return GRAPE_OK;
 }
 
+// The *_mean trajectory calls (traj_mean.hip, reached through launch_copy: BasisOp::mean): the member reduction of the
+// (N + 1, n_obs, E) array `y` and the (n, m, E) array `xf` (null: absent) into d_mean_io = [y part | xf part] with the weights
+// of the call, or the broadcast of d_mean_io into them.  Logged into the open kernel log.
+static int mean_launch(grape_ctx *c, bool broadcast, double2 *y, int n_obs, double2 *xf, hipStream_t stream)
+{
+    grape::MeanOp mo;
+    mo.broadcast = broadcast ? 1 : 0;
+    mo.E = c->cfg.n_ensemble;
+    mo.v = c->mean_v_call;
+    mo.L[0] = y ? ((long long)c->cfg.n_slices + 1) * n_obs : 0;
+    mo.L[1] = xf ? (long long)c->cfg.n * c->m : 0;
+    if (broadcast) {
+        mo.in = c->d_mean_io;
+        mo.dst[0] = y;
+        mo.dst[1] = xf;
+    } else {
+        mo.src[0] = y;
+        mo.src[1] = xf;
+        mo.out = c->d_mean_io;
+        mo.part = c->d_mean_part;
+    }
+    grape::BasisOp op;
+    op.mean = &mo;
+    grape::DoneSignal d;
+    d.basis = &op;
+    HIP_TRY(c, grape::launch_copy((const double *)c->d_mean_io, (double *)c->d_mean_io, 0, stream, d));
+    return GRAPE_OK;
+}
+
 // one shard: sweep kernel(s) + the on-device ensemble reduction into d_fg; nothing is synchronised
 static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream_t stream, int n_x = 1,
                         grape::DoneSignal done = grape::DoneSignal())
@@ -2882,6 +2923,10 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
     }
     KernelLogScope log_scope(&c->kernel_log);
     if (keep_x) HIP_TRY(c, grape::launch_copy(d_x, c->d_traj_x, (int)KN(c), stream));
+    if (c->mean_on && c->vjp_on) {                           // grape_eval_vjp_mean: the members' cotangents from the caller's one block
+        const int rc = mean_launch(c, true, c->vjp_has_y ? c->d_vjp_ybar : nullptr, c->vjp_n, c->vjp_has_x ? c->d_vjp_xbar : nullptr, stream);
+        if (rc) return rc;
+    }
     if ((c->jvp_on || c->hvp_on) && pulse_map(c)) {          // (the expansion in front has written this evaluation's slope array)
         const int rc = jvp_tangent_map(c, stream);
         if (rc) return rc;
@@ -2986,8 +3031,13 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
                 o.obs_xf = c->obs_want_xf ? c->obs_xf_call : nullptr;
                 o.obs_staged = c->obs_want_y ? c->obs_staged : 0;
                 HIP_TRY(c, launch_small_family(c, sand, mode, o, stream));
+                if (c->mean_on && lo + cnt == c->cfg.n_ensemble) {       // grape_eval_observables_mean: once, behind the last block
+                    const int rc = mean_launch(c, false, c->obs_want_y ? c->d_obs_y : nullptr, c->obs_n,
+                                               c->obs_want_xf ? c->d_obs_xf : nullptr, stream);
+                    if (rc) return rc;
+                }
             }
-            if (c->vjp_on) {                                 // grape_eval_vjp: the cotangents of these members, pulled back
+            if (c->vjp_on) {                                // grape_eval_vjp: the cotangents of these members, pulled back
                 SweepParams v = vjp_params(c, q, lo);
                 HIP_TRY(c, launch_small_family(c, 0, mode, v, stream));
                 if (lo + cnt == c->cfg.n_ensemble) {         // behind the last block: the groups' sums into the row
@@ -2998,6 +3048,11 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
             if (c->jvp_on) {                                 // grape_eval_jvp: the direction of these members, pushed forward
                 SweepParams v = jvp_params(c, q, lo);
                 HIP_TRY(c, launch_small_family(c, 0, mode, v, stream));
+                if (c->mean_on && lo + cnt == c->cfg.n_ensemble) {       // grape_eval_jvp_mean: once, behind the last block
+                    const int rc = mean_launch(c, false, c->jvp_has_y ? c->d_jvp_ydot : nullptr, c->jvp_n,
+                                               c->jvp_has_x ? c->d_jvp_xf : nullptr, stream);
+                    if (rc) return rc;
+                }
             }
             if (c->hvp_on) {                                 // grape_eval_hvp: the pull-back of these members, differentiated
                 const int rc = hvp_launch(c, q, lo, lo + cnt == c->cfg.n_ensemble, mode, stream);
@@ -3797,20 +3852,45 @@ static int vjp_check(grape_ctx *c, const std::string &who, const void *x, bool x
     return GRAPE_OK;
 }
 
-extern "C" int grape_eval_observables(grape_ctx *c, const double *x, int32_t n_obs, int32_t per_member, const double *O,
-                                      double *y, double *X_final, double *F)
+// What the three *_mean entry points do in front of their evaluation: the weights of the call on the device (v, or the
+// ensemble weights as grape_set_operators received them: their device copy) and the buffers of the member reduction / the
+// broadcast for n_io complex entries per member.  The device of `c` is current.
+static int mean_prepare(grape_ctx *c, const char *who, const double *v, size_t n_io)
 {
-    DeviceGuard guard;
-    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_observables: null context");
-    const char *who = "grape_eval_observables";
+    const size_t E = (size_t)c->cfg.n_ensemble, nseg = (E + grape::kMeanSeg - 1) / grape::kMeanSeg;
+    if (v) {
+        int rc = grow(c, &c->d_mean_v, &c->mean_v_bytes, sizeof(double) * E, who, "the weights");
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpy(c->d_mean_v, v, sizeof(double) * E, hipMemcpyHostToDevice));
+    }
+    c->mean_v_call = v ? c->d_mean_v : c->d_wts;
+    int rc = grow(c, &c->d_mean_io, &c->mean_io_bytes, sizeof(double2) * n_io, who, "the averaged arrays");
+    if (rc || nseg < 2) return rc;
+    return grow(c, &c->d_mean_part, &c->mean_part_bytes, sizeof(double2) * n_io * nseg, who, "the segments' sums");
+}
+
+// mean_on around one evaluation, off again on every way out
+struct MeanScope {
+    grape_ctx *c;
+    MeanScope(grape_ctx *c_, bool on) : c(c_) { c->mean_on = on; }
+    ~MeanScope() { c->mean_on = false; }
+};
+
+// grape_eval_observables (mean = false) and grape_eval_observables_mean (y, X_final: the averaged arrays)
+static int eval_observables_host(grape_ctx *c, const char *who, bool mean, const double *x, int32_t n_obs, int32_t per_member,
+                                 const double *O, const double *v, double *y, double *X_final, double *F)
+{
     c->traj_valid = false;
     if (int rc0 = obs_check(c, who, x, n_obs, per_member, O, y, X_final)) return rc0;
     const size_t n = (size_t)c->cfg.n, m = (size_t)c->m, E = (size_t)c->cfg.n_ensemble, N = (size_t)c->cfg.n_slices;
     const size_t n_O = n * m * (per_member ? E : 1) * (size_t)n_obs;
     int rc = check_finite(c, O, 2 * n_O, who, "O", 2);
     if (rc) return rc;
+    if (mean && v) rc = check_finite(c, v, E, who, "v");
+    if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const bool want_y = y != nullptr && n_obs > 0;
+    const size_t L_y = want_y ? (N + 1) * (size_t)n_obs : 0, L_x = X_final ? n * m : 0;
     if (want_y) {
         rc = grow(c, &c->d_obs_O, &c->obs_O_bytes, sizeof(double2) * n_O, who, "the probes");
         if (rc) return rc;
@@ -3823,6 +3903,10 @@ extern "C" int grape_eval_observables(grape_ctx *c, const double *x, int32_t n_o
         rc = grow(c, &c->d_obs_xf, &c->obs_xf_bytes, sizeof(double2) * n * m * E, who, "the final states");
         if (rc) return rc;
     }
+    if (mean) {
+        rc = mean_prepare(c, who, v, L_y + L_x);
+        if (rc) return rc;
+    }
     c->obs_n = n_obs;
     c->obs_per_member = per_member;
     c->obs_want_y = want_y;
@@ -3831,16 +3915,40 @@ extern "C" int grape_eval_observables(grape_ctx *c, const double *x, int32_t n_o
     c->obs_y_call = c->d_obs_y;
     c->obs_xf_call = c->d_obs_xf;
     c->obs_staged = 0;
-    c->obs_on = true;                                        // enqueue_eval's member blocks end in observe_kernel
-    rc = eval_host(c, 1, x, F, nullptr, "grape_eval_observables");
-    c->obs_on = false;
+    {
+        MeanScope mean_scope(c, mean);                       // (the read-out of the last member block ends in the member reduction)
+        c->obs_on = true;                                    // enqueue_eval's member blocks end in observe_kernel
+        rc = eval_host(c, 1, x, F, nullptr, who);
+        c->obs_on = false;
+    }
     if (rc) return rc;
     // F is published by the evaluation's own last kernel (or by the sweep itself); the read-out's last launch may sit behind it
     rc = wait_stream(c, c->stream);
     if (rc) return rc;
+    if (mean) {
+        if (want_y) HIP_TRY(c, hipMemcpy(y, c->d_mean_io, sizeof(double2) * L_y, hipMemcpyDeviceToHost));
+        if (X_final) HIP_TRY(c, hipMemcpy(X_final, c->d_mean_io + L_y, sizeof(double2) * L_x, hipMemcpyDeviceToHost));
+        return GRAPE_OK;
+    }
     if (want_y) HIP_TRY(c, hipMemcpy(y, c->d_obs_y, sizeof(double2) * (N + 1) * (size_t)n_obs * E, hipMemcpyDeviceToHost));
     if (X_final) HIP_TRY(c, hipMemcpy(X_final, c->d_obs_xf, sizeof(double2) * n * m * E, hipMemcpyDeviceToHost));
     return GRAPE_OK;
+}
+
+extern "C" int grape_eval_observables(grape_ctx *c, const double *x, int32_t n_obs, int32_t per_member, const double *O,
+                                      double *y, double *X_final, double *F)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_observables: null context");
+    return eval_observables_host(c, "grape_eval_observables", false, x, n_obs, per_member, O, nullptr, y, X_final, F);
+}
+
+extern "C" int grape_eval_observables_mean(grape_ctx *c, const double *x, int32_t n_obs, int32_t per_member, const double *O,
+                                           const double *v, double *y_mean, double *X_mean, double *F)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_observables_mean: null context");
+    return eval_observables_host(c, "grape_eval_observables_mean", true, x, n_obs, per_member, O, v, y_mean, X_mean, F);
 }
 
 // ---- grape_eval_vjp: one evaluation + the pull-back of the caller's cotangents along its trajectory ---------------------------
@@ -3876,21 +3984,40 @@ static int vjp_grow_sums(grape_ctx *c, const char *who, size_t nset, bool rows)
     return grow(c, &c->d_vjp_out, &c->vjp_out_bytes, sizeof(double) * (kp + 1) * nset, who, "the projected row");
 }
 
-// grape_eval_vjp (multi = false) and grape_eval_vjp_multi (n_set cotangent sets, every array set-slowest)
+// the largest magnitude among v[0 .. count)
+static double max_abs(const double *v, size_t count)
+{
+    double a = 0.0;
+    for (size_t i = 0; i < count; ++i) a = std::max(a, std::fabs(v[i]));
+    return a;
+}
+
+// grape_eval_vjp (multi = false), grape_eval_vjp_multi (n_set cotangent sets, every array set-slowest) and grape_eval_vjp_mean
+// (mean: ybar, Xbar_final are ONE member's block; the broadcast kernel writes every member's, scaled by its weight)
 static int eval_vjp_host(grape_ctx *c, const char *who, bool multi, const double *x, int32_t n_set, int32_t n_obs, int32_t per_member,
-                         const double *O, const double *ybar, const double *Xbar_final, double *G)
+                         const double *O, const double *ybar, const double *Xbar_final, double *G, bool mean = false,
+                         const double *v = nullptr)
 {
     c->traj_valid = false;
     if (int rc0 = vjp_check(c, who, x, true, n_obs, per_member, O, ybar, Xbar_final, G, multi ? n_set : 1)) return rc0;
     const size_t ns = multi ? (size_t)n_set : 1;
     const size_t n = (size_t)c->cfg.n, m = (size_t)c->m, E = (size_t)c->cfg.n_ensemble, N = (size_t)c->cfg.n_slices;
     const size_t n_O = n * m * (per_member ? E : 1) * (size_t)n_obs, n_y = (N + 1) * (size_t)n_obs * E * ns, n_X = n * m * E * ns;
+    const size_t L_y = ybar ? n_y / E : 0, L_x = Xbar_final ? n_X / E : 0;       // (mean: the entries of the caller's one block)
     int rc = check_finite(c, O, 2 * n_O, who, "O", 2);
     if (rc) return rc;
-    if (ybar) rc = check_finite(c, ybar, 2 * n_y, who, "ybar", 2);
+    if (mean && v) rc = check_finite(c, v, E, who, "v");
     if (rc) return rc;
-    if (Xbar_final) rc = check_finite(c, Xbar_final, 2 * n_X, who, "Xbar_final", 2);
+    if (ybar) rc = check_finite(c, ybar, 2 * (mean ? L_y : n_y), who, mean ? "ybar_mean" : "ybar", 2);
     if (rc) return rc;
+    if (Xbar_final) rc = check_finite(c, Xbar_final, 2 * (mean ? L_x : n_X), who, mean ? "Xbar_mean" : "Xbar_final", 2);
+    if (rc) return rc;
+    if (mean) {
+        // every member's cotangent v_k ybar_mean has to be finite, as grape_eval_vjp asks of its ybar: the largest product decides
+        const double vmax = max_abs(v ? v : c->h_wts.data(), E);
+        if (!std::isfinite(vmax * std::max(ybar ? max_abs(ybar, 2 * L_y) : 0.0, Xbar_final ? max_abs(Xbar_final, 2 * L_x) : 0.0)))
+            return fail(c, GRAPE_ERR_INVALID_ARG, std::string(who) + ": a member's cotangent v[k] * ybar_mean / v[k] * Xbar_mean is not finite");
+    }
     HIP_TRY(c, hipSetDevice(c->device));
     VjpMultiScope scope(c, multi ? n_set : 0);
     if (multi) {                                             // (the sums and the rows are the device form's too, which does not block)
@@ -3905,12 +4032,18 @@ static int eval_vjp_host(grape_ctx *c, const char *who, bool multi, const double
         rc = grow(c, &c->d_vjp_ybar, &c->vjp_ybar_bytes, sizeof(double2) * n_y, who, "the cotangents of the expectation values");
         if (rc) return rc;
         HIP_TRY(c, hipMemcpy(c->d_vjp_O, O, sizeof(double2) * n_O, hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(c->d_vjp_ybar, ybar, sizeof(double2) * n_y, hipMemcpyHostToDevice));
+        if (!mean) HIP_TRY(c, hipMemcpy(c->d_vjp_ybar, ybar, sizeof(double2) * n_y, hipMemcpyHostToDevice));
     }
     if (Xbar_final) {
         rc = grow(c, &c->d_vjp_xbar, &c->vjp_xbar_bytes, sizeof(double2) * n_X, who, "the cotangents of the final states");
         if (rc) return rc;
-        HIP_TRY(c, hipMemcpy(c->d_vjp_xbar, Xbar_final, sizeof(double2) * n_X, hipMemcpyHostToDevice));
+        if (!mean) HIP_TRY(c, hipMemcpy(c->d_vjp_xbar, Xbar_final, sizeof(double2) * n_X, hipMemcpyHostToDevice));
+    }
+    if (mean) {                                              // the caller's one block: what the broadcast kernel reads
+        rc = mean_prepare(c, who, v, L_y + L_x);
+        if (rc) return rc;
+        if (ybar) HIP_TRY(c, hipMemcpy(c->d_mean_io, ybar, sizeof(double2) * L_y, hipMemcpyHostToDevice));
+        if (Xbar_final) HIP_TRY(c, hipMemcpy(c->d_mean_io + L_y, Xbar_final, sizeof(double2) * L_x, hipMemcpyHostToDevice));
     }
     rc = vjp_grow_sums(c, who, ns, true);
     if (rc) return rc;
@@ -3927,9 +4060,12 @@ static int eval_vjp_host(grape_ctx *c, const char *who, bool multi, const double
     c->vjp_G_call = c->d_vjp_g;
     c->vjp_G_step = kn + 1;
     c->vjp_staged = 0;
-    c->vjp_on = true;                                        // enqueue_eval's member blocks end in the two kernels of vjp.hip
-    rc = eval_host(c, 1, x, nullptr, nullptr, who);          // (its [G, F] are not wanted)
-    c->vjp_on = false;
+    {
+        MeanScope mean_scope(c, mean);                       // (the evaluation starts with the broadcast of the cotangents)
+        c->vjp_on = true;                                    // enqueue_eval's member blocks end in the two kernels of vjp.hip
+        rc = eval_host(c, 1, x, nullptr, nullptr, who);      // (its [G, F] are not wanted)
+        c->vjp_on = false;
+    }
     if (rc) return rc;
     // the summed physical rows -> the coordinates of x: the slope / projection of the evaluation that has just run (its slope
     // array is in place), without the penalty and F that the evaluation's own tail carries
@@ -3959,6 +4095,14 @@ extern "C" int grape_eval_vjp(grape_ctx *c, const double *x, int32_t n_obs, int3
     DeviceGuard guard;
     if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp: null context");
     return eval_vjp_host(c, "grape_eval_vjp", false, x, 0, n_obs, per_member, O, ybar, Xbar_final, G);
+}
+
+extern "C" int grape_eval_vjp_mean(grape_ctx *c, const double *x, int32_t n_obs, int32_t per_member, const double *O,
+                                   const double *v, const double *ybar_mean, const double *Xbar_mean, double *G)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_vjp_mean: null context");
+    return eval_vjp_host(c, "grape_eval_vjp_mean", false, x, 0, n_obs, per_member, O, ybar_mean, Xbar_mean, G, true, v);
 }
 
 extern "C" int grape_eval_vjp_multi(grape_ctx *c, const double *x, int32_t n_set, int32_t n_obs, int32_t per_member,
@@ -4147,9 +4291,11 @@ struct JvpMultiScope {
     ~JvpMultiScope() { c->jvp_ndir = 0; c->jvp_multi = 0; }
 };
 
-// grape_eval_jvp (multi = false) and grape_eval_jvp_multi (n_dir directions, every array direction-slowest)
+// grape_eval_jvp (multi = false), grape_eval_jvp_multi (n_dir directions, every array direction-slowest) and grape_eval_jvp_mean
+// (mean: ydot, Xdot_final are the averaged arrays)
 static int eval_jvp_host(grape_ctx *c, const char *who, bool multi, const double *x, int32_t n_dir, const double *xdot, int32_t n_obs,
-                         int32_t per_member, const double *O, double *ydot, double *Xdot_final)
+                         int32_t per_member, const double *O, double *ydot, double *Xdot_final, bool mean = false,
+                         const double *v = nullptr)
 {
     c->traj_valid = false;
     if (int rc0 = jvp_check(c, who, x, true, xdot, n_obs, per_member, O, ydot, Xdot_final, multi ? n_dir : 1)) return rc0;
@@ -4160,6 +4306,8 @@ static int eval_jvp_host(grape_ctx *c, const char *who, bool multi, const double
     int rc = check_finite(c, O, 2 * n_O, who, "O", 2);
     if (rc) return rc;
     rc = check_finite(c, xdot, kp, who, "xdot");
+    if (rc) return rc;
+    if (mean && v) rc = check_finite(c, v, E, who, "v");
     if (rc) return rc;
     JvpMultiScope scope(c, multi ? n_dir : 0);
     // the direction's buffers are the device form's too, and that one does not block: nothing of it is in flight from here on
@@ -4188,6 +4336,11 @@ static int eval_jvp_host(grape_ctx *c, const char *who, bool multi, const double
         if (rc) return rc;
     }
     HIP_TRY(c, hipMemcpy(c->d_jvp_xdot, xdot, sizeof(double) * kp, hipMemcpyHostToDevice));
+    const size_t L_y = want_y ? (N + 1) * (size_t)n_obs : 0, L_x = Xdot_final ? n * m : 0;
+    if (mean) {
+        rc = mean_prepare(c, who, v, L_y + L_x);
+        if (rc) return rc;
+    }
     c->jvp_n = n_obs;
     c->jvp_per_member = per_member;
     c->jvp_has_y = want_y;
@@ -4196,13 +4349,21 @@ static int eval_jvp_host(grape_ctx *c, const char *who, bool multi, const double
     c->jvp_xdot_call = c->d_jvp_xdot;
     c->jvp_ydot_call = c->d_jvp_ydot;
     c->jvp_xf_call = c->d_jvp_xf;
-    c->jvp_on = true;                                        // enqueue_eval's member blocks end in trajectory_jvp_kernel
-    rc = eval_host(c, 1, x, nullptr, nullptr, who);          // (its [G, F] are not wanted)
-    c->jvp_on = false;
+    {
+        MeanScope mean_scope(c, mean);                       // (the push-forward of the last member block ends in the member reduction)
+        c->jvp_on = true;                                    // enqueue_eval's member blocks end in trajectory_jvp_kernel
+        rc = eval_host(c, 1, x, nullptr, nullptr, who);      // (its [G, F] are not wanted)
+        c->jvp_on = false;
+    }
     if (rc) return rc;
     // (the evaluation is published by its own last kernel, or by the sweep itself: the push-forward may sit behind that)
     rc = wait_stream(c, c->stream);
     if (rc) return rc;
+    if (mean) {
+        if (want_y) HIP_TRY(c, hipMemcpy(ydot, c->d_mean_io, sizeof(double2) * L_y, hipMemcpyDeviceToHost));
+        if (Xdot_final) HIP_TRY(c, hipMemcpy(Xdot_final, c->d_mean_io + L_y, sizeof(double2) * L_x, hipMemcpyDeviceToHost));
+        return GRAPE_OK;
+    }
     if (want_y) HIP_TRY(c, hipMemcpy(ydot, c->d_jvp_ydot, sizeof(double2) * n_y, hipMemcpyDeviceToHost));
     if (Xdot_final) HIP_TRY(c, hipMemcpy(Xdot_final, c->d_jvp_xf, sizeof(double2) * n_X, hipMemcpyDeviceToHost));
     return GRAPE_OK;
@@ -4214,6 +4375,14 @@ extern "C" int grape_eval_jvp(grape_ctx *c, const double *x, const double *xdot,
     DeviceGuard guard;
     if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_jvp: null context");
     return eval_jvp_host(c, "grape_eval_jvp", false, x, 0, xdot, n_obs, per_member, O, ydot, Xdot_final);
+}
+
+extern "C" int grape_eval_jvp_mean(grape_ctx *c, const double *x, const double *xdot, int32_t n_obs, int32_t per_member,
+                                   const double *O, const double *v, double *ydot_mean, double *Xdot_mean)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_jvp_mean: null context");
+    return eval_jvp_host(c, "grape_eval_jvp_mean", false, x, 0, xdot, n_obs, per_member, O, ydot_mean, Xdot_mean, true, v);
 }
 
 extern "C" int grape_eval_jvp_multi(grape_ctx *c, const double *x, int32_t n_dir, const double *xdot, int32_t n_obs,

@@ -44,6 +44,24 @@ constexpr double kTheta8 = 0.08;
 //   a control with lo = -inf, hi = +inf keeps x = acc, slope = 1)
 // and the projection multiplies every gradient entry by its slope in front of the sum.  M = 0 is the identity expansion
 // (no basis in force: acc = src, bounds_saturate_kernel; dst rows = src rows x slope, bounds_slope_kernel).
+// The ensemble-averaged trajectory calls (traj_mean.hip) ride on the same seam: a BasisOp whose `mean` points at one of these
+// makes launch_copy run the member reduction / the cotangent broadcast INSTEAD (src, dst and n of the call are not read).
+// Read by the launcher on the host and handed to the kernels by value.  Two arrays per call, either may be absent (L = 0):
+// [0] the y type, L = (N + 1) n_obs entries per member; [1] the final-state type, L = n m.
+//   reduction (broadcast = 0): out[i] = sum_k v[k] src[a][i + L[a] k], out = [array 0 | array 1]; the member axis in segments of
+//                              kMeanSeg, their sums through `part` (ceil(E / kMeanSeg) rows of L[0] + L[1]; unused for one segment)
+//   broadcast (1):             dst[a][i + L[a] k] = (v[k] Re in[i], v[k] Im in[i]), in = [array 0 | array 1]
+constexpr int kMeanSeg = 16;                   // members per segment of the reduction's tree (a function of E alone)
+struct MeanOp {
+    int32_t broadcast = 0;
+    int32_t E = 0;
+    const double *v = nullptr;                 // device [E]
+    long long L[2] = {0, 0};
+    const double2 *src[2] = {nullptr, nullptr};
+    double2 *out = nullptr, *part = nullptr;
+    const double2 *in = nullptr;
+    double2 *dst[2] = {nullptr, nullptr};
+};
 struct BasisOp {
     int32_t project = 0;                       // 0: expand, 1: project
     const double *phi = nullptr;               // device (N, M, n_bases) column-major
@@ -57,6 +75,9 @@ struct BasisOp {
     //   dst (K, N) = slope * sum_m src[c, m] phi_b[t, m]   (no x0, no saturation; the slope is READ, 1 without bounds;
     //   M = 0: dst = src * slope, bounds_tangent_kernel) -- the transpose of what the projection does to a gradient
     int32_t tangent = 0;
+    // the *_mean trajectory calls: HOST pointer, read by launch_basis alone (which runs traj_mean.hip's kernels and nothing
+    // else); nullptr: everything above.  Never dereferenced on the device.
+    const MeanOp *mean = nullptr;
 };
 // optional host-visible completion signal of an evaluation's FINAL kernel (reduce.hip: signal_done);
 // flag == nullptr: none (device-pointer entry points, intermediate kernels)
@@ -367,6 +388,8 @@ hipError_t launch_vjp_rows_sum(const SweepParams &p, hipStream_t stream);
 constexpr bool hvp_walks_back(int n, int m) { return !(n == 3 && m == 3); }
 // hvp.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::hvp_only) only
 hipError_t run_trajectory_hvp(int n, const SweepParams &p, hipStream_t stream);
+// traj_mean.hip; reached through launch_copy (DoneSignal::basis, BasisOp::mean) only
+hipError_t run_traj_mean(const MeanOp &op, hipStream_t stream);
 // traj_frechet.hip; reached through run_trajectory_vjp (dir = false) / run_trajectory_jvp (dir = true) only
 hipError_t run_traj_frechet(int n, bool dir, const SweepParams &p, hipStream_t stream);
 constexpr int kVjpGroup = 32;                 // members per group of vjp_sum_kernel's tree: vjp_part has ceil(E / 32) rows

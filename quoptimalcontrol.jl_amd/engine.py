@@ -47,6 +47,7 @@ EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_oper
            "grape_eval_vjp", "grape_eval_observables_device", "grape_eval_vjp_device", "grape_eval_jvp", "grape_eval_jvp_device",
            "grape_eval_jvp_multi", "grape_eval_jvp_multi_device", "grape_eval_hvp", "grape_eval_hvp_device",
            "grape_eval_vjp_multi", "grape_eval_vjp_multi_device",
+           "grape_eval_observables_mean", "grape_eval_vjp_mean", "grape_eval_jvp_mean",
            "grape_set_trajectory_derivative", "grape_set_running_cost_derivative",
            "grape_lbfgs", "grape_lbfgs_get_trace",
            "grape_get_member_results", "grape_get_trajectory",
@@ -159,6 +160,9 @@ def load_library():
     L.grape_eval_jvp_multi_device.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
     L.grape_eval_hvp.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.grape_eval_hvp_device.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.grape_eval_observables_mean.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, dp]
+    L.grape_eval_vjp_mean.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.grape_eval_jvp_mean.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
     L.grape_set_trajectory_derivative.argtypes = [vp, i32]
     L.grape_set_running_cost_derivative.argtypes = [vp, i32]
     L.grape_lbfgs.argtypes = [vp, vp, C.POINTER(GrapeLbfgsOptions), vp, C.POINTER(GrapeLbfgsResult)]
@@ -738,6 +742,88 @@ class GrapeEngine:
         self._check(self._lib.grape_eval_jvp(self._h, _p(xf), _p(xdf), n_obs, 1 if per_member else 0, _p(Of), _p(yd), _p(Xf)))
         if final:
             return yd, np.ascontiguousarray(np.swapaxes(Xf, -1, -2))
+        return yd
+
+    def _mean_args(self, who, x, ops, per_member, v):
+        """(xf, n_obs, Of, vf) of the *_mean forms: x column-major, the probes as the library reads them, the weights"""
+        x = np.asarray(x, dtype=np.float64)
+        if x.shape != (self.K, self._cols):
+            raise ValueError(f"x must be ({self.K},{self._cols})")
+        n_obs, O = self._jvp_probes(who, ops, per_member)
+        Of = None if O is None else _cm(np.swapaxes(O, 0, 1) if per_member else O)
+        vf = None
+        if v is not None:
+            vf = np.ascontiguousarray(v, dtype=np.float64)
+            if vf.shape != (self.E,):
+                raise ValueError(f"{who}: v must be ({self.E},)")
+        return np.ascontiguousarray(x.T), n_obs, Of, vf
+
+    def observe_mean(self, x, ops, v=None, per_member=False, final=False, want_F=False):
+        """grape_eval_observables_mean: observe() with the member axis summed on the device, y_mean[j, s] = sum_k v_k y[k, j, s]
+        and X_mean = sum_k v_k X_final[k].  v (E,): the weights of the sum; None: the ensemble weights wts (not the risk
+        weights: pass risk_weights() for those).  x, ops, per_member, final, want_F as in observe.  Returns y_mean (n_obs, N+1)
+        complex128 -- then X_mean (n, m) with final=True -- then F with want_F=True.  The summation order depends on E alone:
+        equal bits call to call, chunked or not, and column j of a 16-probe call is the 1-probe call with probe j."""
+        xf, n_obs, Of, vf = self._mean_args("observe_mean", x, ops, per_member, v)
+        if Of is None and not final:
+            raise ValueError("observe_mean: nothing asked for (ops=None needs final=True)")
+        y = None if Of is None else np.empty((n_obs, self.N + 1), np.complex128)
+        Xm = np.empty((self.m, self.n), np.complex128) if final else None
+        F = C.c_double()
+        self._check(self._lib.grape_eval_observables_mean(self._h, _p(xf), n_obs, 1 if per_member else 0, _p(Of), _p(vf), _p(y),
+                                                          _p(Xm), C.byref(F) if want_F else None))
+        out = [y]
+        if final:
+            out.append(np.ascontiguousarray(Xm.T))
+        if want_F:
+            out.append(F.value)
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def observe_vjp_mean(self, x, ops, ybar_mean=None, xbar_mean=None, v=None, per_member=False):
+        """grape_eval_vjp_mean: the vector-Jacobian product of observe_mean() -- the gradient with respect to x of any real loss
+        written on its returns, from the cotangents ybar_mean (n_obs, N+1) and xbar_mean (n, m) (either may be None, not both).
+        Bit for bit observe_vjp with ybar[k] = v_k * ybar_mean, xbar_final[k] = v_k * xbar_mean (component-wise products),
+        which a kernel forms on the device.  Returns G (K, cols) in the coordinates of x."""
+        xf, n_obs, Of, vf = self._mean_args("observe_vjp_mean", x, ops, per_member, v)
+        if ybar_mean is None and xbar_mean is None:
+            raise ValueError("observe_vjp_mean: nothing to pull back (ybar_mean and xbar_mean are both None)")
+        yb = None
+        if ybar_mean is not None:
+            if Of is None:
+                raise ValueError("observe_vjp_mean: ybar_mean needs the probes it belongs to")
+            yb = np.ascontiguousarray(ybar_mean, dtype=np.complex128)
+            if yb.shape != (n_obs, self.N + 1):
+                raise ValueError(f"observe_vjp_mean: ybar_mean must be ({n_obs},{self.N + 1})")
+        else:
+            n_obs, Of = 0, None                                   # (probes without cotangents: nothing of theirs to pull back)
+        xb = None
+        if xbar_mean is not None:
+            xb = np.asarray(xbar_mean, dtype=np.complex128)
+            if xb.shape != (self.n, self.m):
+                raise ValueError(f"observe_vjp_mean: xbar_mean must be ({self.n},{self.m})")
+            xb = _cm(xb)
+        G = np.empty((self._cols, self.K))
+        self._check(self._lib.grape_eval_vjp_mean(self._h, _p(xf), n_obs, 1 if per_member else 0, _p(Of), _p(vf), _p(yb), _p(xb),
+                                                  _p(G)))
+        return np.ascontiguousarray(G.T)
+
+    def observe_jvp_mean(self, x, xdot, ops, v=None, per_member=False, final=False):
+        """grape_eval_jvp_mean: the Jacobian-vector product of observe_mean() along xdot (x's shape and coordinates): the sums
+        sum_k v_k ydot[k] and sum_k v_k Xdot_final[k] of observe_jvp's returns, formed on the device in observe_mean's order.
+        Returns ydot_mean (n_obs, N+1) -- then Xdot_mean (n, m) with final=True.  The transpose of observe_vjp_mean."""
+        xf, n_obs, Of, vf = self._mean_args("observe_jvp_mean", x, ops, per_member, v)
+        xd = np.asarray(xdot, dtype=np.float64)
+        if xd.shape != (self.K, self._cols):
+            raise ValueError(f"observe_jvp_mean: xdot must be ({self.K},{self._cols}), the shape of x")
+        if Of is None and not final:
+            raise ValueError("observe_jvp_mean: nothing asked for (ops=None needs final=True)")
+        yd = None if Of is None else np.empty((n_obs, self.N + 1), np.complex128)
+        Xm = np.empty((self.m, self.n), np.complex128) if final else None
+        xdf = np.ascontiguousarray(xd.T)
+        self._check(self._lib.grape_eval_jvp_mean(self._h, _p(xf), _p(xdf), n_obs, 1 if per_member else 0, _p(Of), _p(vf), _p(yd),
+                                                  _p(Xm)))
+        if final:
+            return yd, np.ascontiguousarray(Xm.T)
         return yd
 
     def observe_hvp(self, x, xdot, ops, ybar=None, xbar_final=None, ybar_dot=None, xbar_final_dot=None, per_member=False):
