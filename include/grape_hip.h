@@ -781,6 +781,62 @@ int grape_eval_hvp_device(grape_ctx *ctx, const double *d_x, const double *d_xdo
                           const double *d_O, const double *d_ybar, const double *d_Xbar_final, const double *d_ybar_dot,
                           const double *d_Xbar_final_dot, double *d_Gdot, void *stream);
 
+/* ABI v8 (additive).  Gauss-Newton products along the trajectory in ONE pass: the push-forward of grape_eval_jvp, weighted entry
+ * by entry, into the pull-back of grape_eval_vjp -- Gn = J' W J xdot, the operator a Gauss-Newton or Levenberg-Marquardt step on
+ * a least-squares trajectory loss (tracking a population curve, fitting a measured transient, holding a state on a path) applies
+ * once per CG iteration.  Neither ydot nor a ybar array exists anywhere.
+ *   x, xdot, n_obs, per_member, O   exactly as in grape_eval_jvp (x is theta / u under grape_set_basis / grape_set_bounds)
+ *   w_per_member    0: wy is shared by the members; 1: one block per member
+ *   wy              host f64 (N+1, n_obs, 3) (w_per_member = 0) or (N+1, n_obs, E, 3) (w_per_member = 1), column-major, the
+ *                   PLANES rr, ri, ii slowest: a real symmetric 2x2 block per entry of y, acting on (Re ydot, Im ydot).  Scalar
+ *                   weights are rr = ii = w, ri = 0.  Row s = 0 is read by nobody (ydot[0] = 0).  NULL: zero
+ *   wf              host f64 [E], the weights of the final states; NULL: zero (each alone or both)
+ *   Gn              host f64 (K, N), or (K, M) in parameter mode: the shape and coordinates of grape_eval_vjp's G
+ * With B'_kc = -i dt B_kc, V_ks = sum_c xdot_phys[c,s] B'_kc and the propagators P and states X of the physical pulse:
+ *   D_0    = 0 ,    D_{s+1} = P_s D_s + V_s X_{s+1}                                                  (grape_eval_jvp's tangent)
+ *   ydot[s,j,k] = tr( O_kj' D_{k,s} )
+ *   c[s,j,k]    = ( w_rr Re ydot + w_ri Im ydot ) + i ( w_ri Re ydot + w_ii Im ydot )
+ *   Lam_N  = wf_k D_N + sum_j c[N,j,k] O_kj ,    Lam_s = P_s' Lam_{s+1} + sum_j c[s,j,k] O_kj         s = N-1 .. 1
+ *   Gn[c,t] = sum_k Re tr( Lam_{k,t+1}' B'_kc X_{k,t+1} )                                             t = 0 .. N-1
+ * that is grape_eval_vjp(ybar = W ydot, Xbar_final = wf Xdot_final) of (ydot, Xdot_final) = grape_eval_jvp(xdot), FIRST ORDER in
+ * dt under the rule of that pair.  With these weights it is the generalised Gauss-Newton matrix of any loss that is separable
+ * over the entries of y (the block is l'' of the entry's loss in (Re y, Im y): (|y|^2 - p)^2 and log-barriers on populations
+ * have an off-diagonal part) plus 1/2 wf_k |X_N - T|^2.  The operator is symmetric to rounding, and positive semi-definite for
+ * PSD blocks and wf >= 0; the library does NOT check definiteness -- indefinite weights are the caller's business.
+ * Gn carries no ensemble weight, penalty, running cost or risk.  Under grape_set_basis and / or grape_set_bounds xdot_phys is
+ * the tangent map grape_eval_jvp uses and Gn goes through the slope and projection grape_eval_vjp uses: Phi' s J' W J s Phi.
+ * Bounds ARE served (no second derivative of the pulse map enters), unlike grape_eval_hvp.
+ * The call runs ONE evaluation of x exactly as the context is configured and discards its [G, F]; behind the sweep of every
+ * member block trajectory_gnvp_kernel reads the stored propagators -- one workgroup per member, one lane per time chunk -- and
+ * vjp_sum_kernel adds the members' rows in grape_eval_vjp's fixed tree.  The kernel's scratch (one n x m block per slice and
+ * member of a workspace block: the costate's source) is allocated on first use, grows only behind a pending device call and is
+ * counted in grape_info.workspace_bytes.  Blocking, ordered behind an in-flight grape_eval_device; afterwards
+ * grape_get_kernel_names includes trajectory_gnvp_kernel.  An eval -> gnvp -> eval sequence returns the first evaluation's
+ * bits; results are bitwise reproducible call to call; a member-chunked context returns the unchunked context's bits; a
+ * standing running cost, penalties or risk do not change a bit.  Every operation is linear in xdot, and in (wy, wf): twice the
+ * direction returns twice the bits, the negated direction the negated bits, xdot = 0 exact zeros; shared weights return the
+ * bits of the same block repeated per member.
+ * Served: the contexts grape_eval_vjp serves, refused with its reasons first.  One refusal of this call alone follows them,
+ * GRAPE_ERR_UNSUPPORTED: grape_set_trajectory_derivative(GRAPE_TRAJ_EXACT) in force ("trajectory_derivative": the fused kernel
+ * carries the first-order pair only).
+ * GRAPE_ERR_INVALID_ARG: null x, xdot or Gn; wy and wf both NULL; n_obs outside 0..16; n_obs = 0 with a non-NULL wy; n_obs > 0
+ * with a NULL O; per_member or w_per_member other than 0 or 1; a non-finite entry of a host array ("not finite").
+ * Before grape_set_operators: GRAPE_ERR_NOT_READY.  After any refusal the context evaluates exactly as before. */
+int grape_eval_gnvp(grape_ctx *ctx, const double *x, const double *xdot, int32_t n_obs, int32_t per_member, const double *O,
+                    int32_t w_per_member, const double *wy, const double *wf, double *Gn);
+
+/* ABI v8 (additive).  The device form of grape_eval_gnvp under the rules of grape_eval_vjp_device / grape_eval_jvp_device: every
+ * array lives in device memory of the context's GPU, the call is asynchronous on `stream`, nothing is synchronised; device
+ * arrays are NOT checked for non-finite entries, everything else is validated as in the host form.  Results are bit for bit
+ * the host form's.  With a non-NULL d_x on a context that is not member-chunked the call sets the "trajectory valid" flag;
+ * d_x = NULL runs along the stored trajectory of the last device form with no sweep and the same bits, and keeps the flag set,
+ * so the other reuse calls may follow (a Gauss-Newton-CG inner loop: ONE grape_eval_gnvp_device(NULL) per iteration at one
+ * linearisation point).  With the flag clear, or on a member-chunked context, GRAPE_ERR_NOT_READY with
+ * grape_eval_vjp_device's messages. */
+int grape_eval_gnvp_device(grape_ctx *ctx, const double *d_x, const double *d_xdot, int32_t n_obs, int32_t per_member,
+                           const double *d_O, int32_t w_per_member, const double *d_wy, const double *d_wf, double *d_Gn,
+                           void *stream);
+
 /* ABI v8 (additive).  The ensemble-averaged host forms of the trajectory read-out, its pull-back and its push-forward: the
  * member axis of y / ybar / ydot never crosses the bus.  What an experiment on an inhomogeneously broadened ensemble measures
  * is sum_k v_k y[k]; a loss on it has the cotangent ybar[k] = v_k ybar_mean, ONE block broadcast over the members.

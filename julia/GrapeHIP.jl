@@ -352,6 +352,52 @@ function observables_jvp_device(ctx::GrapeContext, d_x::Ptr{Cvoid}, d_xdot::Ptr{
     ctx
 end
 
+# grape_eval_gnvp: the weighted Gauss-Newton product J' W J xdot of `observables` in one trajectory pass -- what
+# `observables_vjp` returns for ybar = W ydot, Xbar_final = wf Xdot_final of `observables_jvp`, without either array.
+# wy: (N+1, n_obs, 3) shared by the members or (N+1, n_obs, E, 3), the last axis the planes rr, ri, ii of a real symmetric 2x2
+# block per entry of y (scalar weights: rr = ii = w, ri = 0); wf (E): the weights of the final states; either may be `nothing`,
+# not both.  Returns Gn (K, N).  Bounds and a basis are served.  (Written, NOT executed, like `observables_jvp`; the Python
+# binding makes the same call and is tested on the GPU.)
+function observables_gnvp(ctx::GrapeContext, x::Matrix{Float64}, xdot::Matrix{Float64}, O::Union{Nothing,Array{ComplexF64}},
+                          wy::Union{Nothing,Array{Float64}}, wf::Union{Nothing,Vector{Float64}})
+    size(x) == (ctx.K, ctx.N) || throw(DimensionMismatch("x must be (n_controls, n_slices)"))
+    size(xdot) == size(x) || throw(DimensionMismatch("xdot must have the shape of x"))
+    (wy === nothing && wf === nothing) && throw(ArgumentError("observables_gnvp: both weights are nothing"))
+    n_obs, pm, wpm = 0, Int32(0), Int32(0)
+    if wy !== nothing
+        O === nothing && throw(ArgumentError("observables_gnvp: wy needs the probes it belongs to"))
+        n_obs = size(O, ndims(O))
+        (ndims(O) == 3 && size(O) == (ctx.n, ctx.m, n_obs)) || (ndims(O) == 4 && size(O) == (ctx.n, ctx.m, ctx.E, n_obs)) ||
+            throw(DimensionMismatch("O must be (n, m, n_obs) or (n, m, E, n_obs) with the context's n, m and E"))
+        1 <= n_obs <= 16 || throw(ArgumentError("observables_gnvp: 1 to 16 probes"))
+        size(wy) == (ctx.N + 1, n_obs, 3) || size(wy) == (ctx.N + 1, n_obs, ctx.E, 3) ||
+            throw(DimensionMismatch("wy must be (N+1, n_obs, 3) or (N+1, n_obs, E, 3)"))
+        pm, wpm = Int32(ndims(O) == 4 ? 1 : 0), Int32(ndims(wy) == 4 ? 1 : 0)
+    end
+    wf === nothing || length(wf) == ctx.E || throw(DimensionMismatch("wf must have one entry per member"))
+    p_O = wy === nothing ? Ptr{ComplexF64}(C_NULL) : pointer(O)
+    p_wy = wy === nothing ? Ptr{Float64}(C_NULL) : pointer(wy)
+    p_wf = wf === nothing ? Ptr{Float64}(C_NULL) : pointer(wf)
+    Gn = Matrix{Float64}(undef, ctx.K, ctx.N)
+    GC.@preserve x xdot O wy wf Gn check(ctx, ccall((:grape_eval_gnvp, libgrape), Cint,
+                                                    (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{ComplexF64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                                                    ctx.handle, x, xdot, Int32(n_obs), pm, p_O, wpm, p_wy, p_wf, Gn))
+    Gn
+end
+
+# grape_eval_gnvp_device: the same on device memory of the context's GPU (raw device pointers in the layouts above; C_NULL for
+# a weight array that is zero, not both), asynchronous on `stream`.  d_x = C_NULL runs along the trajectory the last device form
+# left in the workspace, without a sweep: one call per CG iteration of a Gauss-Newton step.
+function observables_gnvp_device(ctx::GrapeContext, d_x::Ptr{Cvoid}, d_xdot::Ptr{Cvoid}, n_obs::Integer, per_member::Bool,
+                                 d_O::Ptr{Cvoid}, w_per_member::Bool, d_wy::Ptr{Cvoid}, d_wf::Ptr{Cvoid}, d_Gn::Ptr{Cvoid};
+                                 stream::Ptr{Cvoid} = C_NULL)
+    check(ctx, ccall((:grape_eval_gnvp_device, libgrape), Cint,
+                     (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                     ctx.handle, d_x, d_xdot, Int32(n_obs), Int32(per_member ? 1 : 0), d_O, Int32(w_per_member ? 1 : 0), d_wy, d_wf,
+                     d_Gn, stream))
+    ctx
+end
+
 # grape_eval_jvp_multi: `observables_jvp` for a block of directions behind ONE evaluation of x.  xdot is (K, N, n_dir) (the
 # direction index slowest, 1 <= n_dir <= 8); ydot (N+1, n_obs, E, n_dir) and Xdf (n, m, E, n_dir) are written in place and
 # returned.  Slice [:, :, :, d] of either is bit for bit what `observables_jvp` returns for xdot[:, :, d].  (Written, NOT

@@ -270,6 +270,19 @@ struct grape_ctx {
     double2 *d_hvp_xs = nullptr;
     size_t hvp_ybd_bytes = 0, hvp_xbd_bytes = 0, hvp_xs_bytes = 0;
     const double2 *hvp_ybd_call = nullptr, *hvp_xbd_call = nullptr;
+    // grape_eval_gnvp (gnvp.hip): behind the sweep of every member block of ONE evaluation, trajectory_gnvp_kernel pushes the
+    // caller's direction forward, weights the tangents of the read-out and pulls the result back; vjp_sum_kernel adds the
+    // members' rows as it does for grape_eval_vjp.  The call is described by the pull-back's fields (vjp_n, vjp_per_member,
+    // vjp_O_call, d_vjp_part / _g / _out; no cotangents: vjp_has_y = vjp_has_x = false) and the push-forward's direction
+    // (jvp_xdot_call, d_jvp_xdot, d_jvp_xphys and the tangent map); its own are the weights and the kernel's scratch, the
+    // costate's source per slice.
+    bool gnvp_on = false;
+    int gnvp_w_per_member = 0;
+    double *d_gnvp_wy = nullptr;               // (N + 1, n_obs, [E,] 3)
+    double *d_gnvp_wf = nullptr;               // (E)
+    double2 *d_gnvp_src = nullptr;
+    size_t gnvp_wy_bytes = 0, gnvp_wf_bytes = 0, gnvp_src_bytes = 0;
+    const double *gnvp_wy_call = nullptr, *gnvp_wf_call = nullptr;
     // grape_eval_observables_mean / _vjp_mean / _jvp_mean (traj_mean.hip): mean_on is set by the entry point around ONE
     // evaluation with obs_on / jvp_on / vjp_on.  Behind the read-out (push-forward) of the last member block the member
     // reduction sums the host form's full-size arrays over the members into d_mean_io; in front of a pull-back the
@@ -696,6 +709,7 @@ static void free_all(grape_ctx *c)
     (void)hipFree(c->d_traj_w); (void)hipFree(c->d_traj_x);
     (void)hipFree(c->d_jvp_O); (void)hipFree(c->d_jvp_xdot); (void)hipFree(c->d_jvp_xphys); (void)hipFree(c->d_jvp_ydot); (void)hipFree(c->d_jvp_xf);
     (void)hipFree(c->d_hvp_ybd); (void)hipFree(c->d_hvp_xbd); (void)hipFree(c->d_hvp_xs);
+    (void)hipFree(c->d_gnvp_wy); (void)hipFree(c->d_gnvp_wf); (void)hipFree(c->d_gnvp_src);
     (void)hipFree(c->d_mean_v); (void)hipFree(c->d_mean_io); (void)hipFree(c->d_mean_part);
     (void)hipFree(c->d_basis_phi); (void)hipFree(c->d_basis_x0);
     (void)hipFree(c->d_bounds); (void)hipFree(c->d_slope);
@@ -2809,6 +2823,45 @@ static int hvp_launch(grape_ctx *c, const SweepParams &q, int lo, bool last, int
     return GRAPE_OK;
 }
 
+// grape_eval_gnvp: the scratch of trajectory_gnvp_kernel behind the CURRENT workspace plan -- the costate's source, one n x m
+// block per slice and member of a workspace block
+static int gnvp_ensure(grape_ctx *c, const char *who)
+{
+    return grow(c, &c->d_gnvp_src, &c->gnvp_src_bytes, sizeof(double2) * (size_t)c->Ec * c->S * c->CH * c->cfg.n * c->m, who,
+                "the costate's sources");
+}
+
+// grape_eval_gnvp: the launch of trajectory_gnvp_kernel + vjp_sum_kernel for the members from `lo` on that `q` sweeps (or swept:
+// grape_eval_gnvp_device's reuse) -- the pull-back's launch, first order, without cotangents, with the direction and the weights
+static SweepParams gnvp_params(const grape_ctx *c, const SweepParams &q, int lo)
+{
+    SweepParams v = vjp_params(c, q, lo);
+    v.vjp_only = 0;
+    v.vjp_staged = 0;
+    v.traj_exact = 0;
+    v.gnvp_only = 1;
+    v.vjp_n = c->gnvp_wy_call ? c->vjp_n : 0;
+    v.hvp_xdot = pulse_map(c) ? c->d_jvp_xphys : c->jvp_xdot_call;
+    v.gnvp_w_per_member = c->gnvp_w_per_member;
+    v.gnvp_wy = c->gnvp_wy_call;
+    v.gnvp_wf = c->gnvp_wf_call;
+    v.gnvp_src = c->d_gnvp_src;
+    return v;
+}
+
+// the two launches of a member block: the rows and their groups' sums, and behind the last block the groups' sums into the row
+static int gnvp_launch(grape_ctx *c, const SweepParams &q, int lo, bool last, int mode, hipStream_t stream)
+{
+    SweepParams v = gnvp_params(c, q, lo);
+    HIP_TRY(c, launch_small_family(c, 0, mode, v, stream));
+    if (last) {
+        v.gnvp_only = 0;
+        v.vjp_only = 2;
+        HIP_TRY(c, launch_small_family(c, 0, mode, v, stream));
+    }
+    return GRAPE_OK;
+}
+
 // grape_eval_jvp_multi: the E_t images the exact mode keeps side by side (one per direction of a block of the multi kernel)
 static int jvp_exact_images(const grape_ctx *c)
 {
@@ -2906,12 +2959,16 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
         const int rc = rc_ensure(c);
         if (rc) return rc;
     }
-    if (c->vjp_on || c->hvp_on) {                            // (the rows, and the states of the general flow)
+    if (c->vjp_on || c->hvp_on || c->gnvp_on) {              // (the rows, and the states of the general flow)
         const int rc = vjp_rows_ensure(c);
         if (rc) return rc;
     }
     if (c->hvp_on) {
         const int rc = hvp_ensure(c, "grape_eval_hvp");
+        if (rc) return rc;
+    }
+    if (c->gnvp_on) {
+        const int rc = gnvp_ensure(c, "grape_eval_gnvp");
         if (rc) return rc;
     }
     // GRAPE_TRAJ_EXACT: every evaluation that may leave a trajectory for the pull-back / push-forward (the read-out's device
@@ -2927,7 +2984,7 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
         const int rc = mean_launch(c, true, c->vjp_has_y ? c->d_vjp_ybar : nullptr, c->vjp_n, c->vjp_has_x ? c->d_vjp_xbar : nullptr, stream);
         if (rc) return rc;
     }
-    if ((c->jvp_on || c->hvp_on) && pulse_map(c)) {          // (the expansion in front has written this evaluation's slope array)
+    if ((c->jvp_on || c->hvp_on || c->gnvp_on) && pulse_map(c)) {       // (the expansion in front has written this evaluation's slope array)
         const int rc = jvp_tangent_map(c, stream);
         if (rc) return rc;
     }
@@ -3056,6 +3113,10 @@ static int enqueue_eval(grape_ctx *c, const double *d_x, double *d_fg, hipStream
             }
             if (c->hvp_on) {                                 // grape_eval_hvp: the pull-back of these members, differentiated
                 const int rc = hvp_launch(c, q, lo, lo + cnt == c->cfg.n_ensemble, mode, stream);
+                if (rc) return rc;
+            }
+            if (c->gnvp_on) {                                // grape_eval_gnvp: the direction of these members, pushed, weighted, pulled
+                const int rc = gnvp_launch(c, q, lo, lo + cnt == c->cfg.n_ensemble, mode, stream);
                 if (rc) return rc;
             }
             if (exact) {                                     // exact gradient + objective from the stored trajectory
@@ -4682,6 +4743,184 @@ extern "C" int grape_eval_hvp_device(grape_ctx *c, const double *d_x, const doub
         grape::DoneSignal d;
         d.basis = &op;
         HIP_TRY(c, grape::launch_copy(c->d_vjp_g, d_Gdot, (int)kp, st, d));
+    }
+    HIP_TRY(c, hipEventRecord(c->ev_dev, st));
+    c->dev_pending = true;
+    c->traj_valid = !chunked(c);
+    return GRAPE_OK;
+}
+
+// ---- grape_eval_gnvp: one evaluation + the weighted Gauss-Newton product J' W J xdot along its trajectory ---------------------
+// vjp_check's order with the refusal of this entry point behind the context's own and the direction behind x.  Bounds are
+// served: no second derivative of the pulse map enters.
+static int gnvp_check(grape_ctx *c, const std::string &who, const void *x, bool x_needed, const void *xdot, int32_t n_obs,
+                      int32_t per_member, const void *O, int32_t w_per_member, const void *wy, const void *wf, const void *Gn)
+{
+    if (const char *why = why_linearisation_not_served(c)) return fail(c, GRAPE_ERR_UNSUPPORTED, who + ": " + why);
+    if (traj_exact(c))
+        return fail(c, GRAPE_ERR_UNSUPPORTED, who + ": trajectory_derivative = exact is in force (grape_set_trajectory_derivative): "
+                                              "the fused kernel carries the first-order pair only");
+    if (!x && x_needed) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": x is null");
+    if (!xdot) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": xdot is null");
+    if (!Gn) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": Gn is null");
+    if (!wy && !wf) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": wy and wf are both null");
+    if (n_obs < 0 || n_obs > 16)
+        return fail(c, GRAPE_ERR_INVALID_ARG, who + ": n_obs = " + std::to_string(n_obs) + " (must be in 0..16)");
+    if (n_obs == 0 && wy) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": n_obs = 0 with a non-null wy");
+    if (n_obs > 0 && !O) return fail(c, GRAPE_ERR_INVALID_ARG, who + ": n_obs > 0 with a null O");
+    if (per_member != 0 && per_member != 1)
+        return fail(c, GRAPE_ERR_INVALID_ARG, who + ": per_member = " + std::to_string(per_member) + " (must be 0 or 1)");
+    if (w_per_member != 0 && w_per_member != 1)
+        return fail(c, GRAPE_ERR_INVALID_ARG, who + ": w_per_member = " + std::to_string(w_per_member) + " (must be 0 or 1)");
+    if (!c->ops_set) return fail(c, GRAPE_ERR_NOT_READY, who + ": operators not set");
+    return GRAPE_OK;
+}
+
+extern "C" int grape_eval_gnvp(grape_ctx *c, const double *x, const double *xdot, int32_t n_obs, int32_t per_member, const double *O,
+                               int32_t w_per_member, const double *wy, const double *wf, double *Gn)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_gnvp: null context");
+    const char *who = "grape_eval_gnvp";
+    c->traj_valid = false;
+    if (int rc0 = gnvp_check(c, who, x, true, xdot, n_obs, per_member, O, w_per_member, wy, wf, Gn)) return rc0;
+    const size_t n = (size_t)c->cfg.n, m = (size_t)c->m, E = (size_t)c->cfg.n_ensemble, N = (size_t)c->cfg.n_slices;
+    const size_t n_O = n * m * (per_member ? E : 1) * (size_t)n_obs, n_w = (N + 1) * (size_t)n_obs * (w_per_member ? E : 1) * 3;
+    const size_t kn = KN(c), kp = KP(c);
+    int rc = check_finite(c, O, 2 * n_O, who, "O", 2);
+    if (rc) return rc;
+    rc = check_finite(c, xdot, kp, who, "xdot");
+    if (rc) return rc;
+    if (wy) rc = check_finite(c, wy, n_w, who, "wy");
+    if (rc) return rc;
+    if (wf) rc = check_finite(c, wf, E, who, "wf");
+    if (rc) return rc;
+    // the direction's buffers are the device forms' too, and those do not block: nothing of them is in flight from here on
+    rc = drain(c, c);
+    if (rc) return rc;
+    if (wy) {
+        rc = grow(c, &c->d_vjp_O, &c->vjp_O_bytes, sizeof(double2) * n_O, who, "the probes");
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpy(c->d_vjp_O, O, sizeof(double2) * n_O, hipMemcpyHostToDevice));
+        rc = grow(c, &c->d_gnvp_wy, &c->gnvp_wy_bytes, sizeof(double) * n_w, who, "the weights of the expectation values");
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpy(c->d_gnvp_wy, wy, sizeof(double) * n_w, hipMemcpyHostToDevice));
+    }
+    if (wf) {
+        rc = grow(c, &c->d_gnvp_wf, &c->gnvp_wf_bytes, sizeof(double) * E, who, "the weights of the final states");
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpy(c->d_gnvp_wf, wf, sizeof(double) * E, hipMemcpyHostToDevice));
+    }
+    rc = grow(c, &c->d_jvp_xdot, &c->jvp_xdot_bytes, sizeof(double) * kp, who, "the direction");
+    if (rc) return rc;
+    if (pulse_map(c)) {
+        rc = grow(c, &c->d_jvp_xphys, &c->jvp_xphys_bytes, sizeof(double) * kn, who, "the direction of the physical pulse");
+        if (rc) return rc;
+    }
+    HIP_TRY(c, hipMemcpy(c->d_jvp_xdot, xdot, sizeof(double) * kp, hipMemcpyHostToDevice));
+    rc = vjp_grow_sums(c, who, 1, true);
+    if (rc) return rc;
+    const double zero = 0.0;                                 // (where the tail expects F)
+    HIP_TRY(c, hipMemcpy(c->d_vjp_g + kn, &zero, sizeof(double), hipMemcpyHostToDevice));
+    c->vjp_n = n_obs;
+    c->vjp_per_member = per_member;
+    c->vjp_has_y = false;
+    c->vjp_has_x = false;
+    c->vjp_O_call = c->d_vjp_O;
+    c->gnvp_w_per_member = w_per_member;
+    c->gnvp_wy_call = wy ? c->d_gnvp_wy : nullptr;
+    c->gnvp_wf_call = wf ? c->d_gnvp_wf : nullptr;
+    c->jvp_xdot_call = c->d_jvp_xdot;
+    c->vjp_G_call = c->d_vjp_g;
+    c->vjp_staged = 0;
+    c->gnvp_on = true;                                       // enqueue_eval's member blocks end in the two kernels of gnvp.hip
+    rc = eval_host(c, 1, x, nullptr, nullptr, who);          // (its [G, F] are not wanted)
+    c->gnvp_on = false;
+    if (rc) return rc;
+    // the summed physical row -> the coordinates of x: the slope / projection of the evaluation that has just run, as for the VJP
+    const double *d_res = c->d_vjp_g;
+    if (pulse_map(c)) {
+        KernelLogScope log_scope(&c->kernel_log, true);
+        const grape::BasisOp op = basis_op(c, true, 1);
+        grape::DoneSignal d;
+        d.basis = &op;
+        HIP_TRY(c, grape::launch_copy(c->d_vjp_g, c->d_vjp_out, (int)(kp + 1), c->stream, d));
+        d_res = c->d_vjp_out;
+    }
+    // (the evaluation is published by its own last kernel, or by the sweep itself: the launches above may sit behind that)
+    rc = wait_stream(c, c->stream);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpy(Gn, d_res, sizeof(double) * kp, hipMemcpyDeviceToHost));
+    return GRAPE_OK;
+}
+
+extern "C" int grape_eval_gnvp_device(grape_ctx *c, const double *d_x, const double *d_xdot, int32_t n_obs, int32_t per_member,
+                                      const double *d_O, int32_t w_per_member, const double *d_wy, const double *d_wf, double *d_Gn,
+                                      void *stream)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_eval_gnvp_device: null context");
+    const char *who = "grape_eval_gnvp_device";
+    const bool reuse = d_x == nullptr, was_valid = c->traj_valid;
+    c->traj_valid = false;
+    int rc = gnvp_check(c, who, d_x, false, d_xdot, n_obs, per_member, d_O, w_per_member, d_wy, d_wf, d_Gn);
+    if (rc) return rc;
+    if (reuse && chunked(c))
+        return fail(c, GRAPE_ERR_NOT_READY, std::string(who) + ": d_x is null (reuse), but the workspace of a context under member_chunk "
+                                            "holds one block of members only");
+    if (reuse && !was_valid)
+        return fail(c, GRAPE_ERR_NOT_READY, std::string(who) + ": d_x is null (reuse), but the workspace does not hold the trajectory of a "
+                                            "device form: another call has evaluated, changed a setting or failed since");
+    hipStream_t st = (hipStream_t)stream;
+    rc = traj_device_prologue(c);
+    if (rc) return rc;
+    const size_t kn = KN(c), kp = KP(c);
+    rc = vjp_grow_sums(c, who, 1, pulse_map(c));
+    if (rc) return rc;
+    if (pulse_map(c)) {
+        rc = grow(c, &c->d_jvp_xphys, &c->jvp_xphys_bytes, sizeof(double) * kn, who, "the direction of the physical pulse");
+        if (rc) return rc;
+    }
+    c->vjp_n = n_obs;
+    c->vjp_per_member = per_member;
+    c->vjp_has_y = false;
+    c->vjp_has_x = false;
+    c->vjp_O_call = (const double2 *)d_O;
+    c->gnvp_w_per_member = w_per_member;
+    c->gnvp_wy_call = d_wy;
+    c->gnvp_wf_call = d_wf;
+    c->jvp_xdot_call = d_xdot;
+    c->vjp_G_call = pulse_map(c) ? c->d_vjp_g : d_Gn;        // (no pulse map: the groups' sums ARE Gn)
+    c->vjp_staged = 0;
+    if (!reuse) {
+        c->gnvp_on = true;                                   // enqueue_eval's member blocks end in the two kernels of gnvp.hip
+        rc = traj_device_eval(c, d_x, pulse_map(c) ? c->d_vjp_out : c->d_fg, st);          // (its [G, F] are not wanted)
+        c->gnvp_on = false;
+        if (rc) return rc;
+    } else {
+        // the propagators (and the slope array) of the last device form are in place: the tangent map and the two kernels alone
+        rc = rc_ensure(c);                                   // (the rows, and the states of the general flow)
+        if (rc) return rc;
+        rc = gnvp_ensure(c, who);
+        if (rc) return rc;
+        KernelLogScope log_scope(&c->kernel_log);
+        if (pulse_map(c)) {
+            rc = jvp_tangent_map(c, st);
+            if (rc) return rc;
+        }
+        SweepParams q = sweep_params(c, nullptr, 1);
+        q.props = c->d_props;
+        rc = gnvp_launch(c, q, 0, true, c->unitary ? 2 : (c->d_costates ? 1 : 0), st);
+        if (rc) return rc;
+    }
+    if (pulse_map(c)) {
+        // the summed physical row -> the coordinates of x, straight into the caller's Gn (no F slot: BasisOp::no_f)
+        KernelLogScope log_scope(&c->kernel_log, true);
+        grape::BasisOp op = basis_op(c, true, 1);
+        op.no_f = 1;
+        grape::DoneSignal d;
+        d.basis = &op;
+        HIP_TRY(c, grape::launch_copy(c->d_vjp_g, d_Gn, (int)kp, st, d));
     }
     HIP_TRY(c, hipEventRecord(c->ev_dev, st));
     c->dev_pending = true;

@@ -297,6 +297,17 @@ struct SweepParams {
     int32_t vjp_nset;
     int32_t vjp_multi;
     int64_t vjp_set_ybar, vjp_set_xbar, vjp_set_rows, vjp_set_part, vjp_set_G;
+    // grape_eval_gnvp (gnvp.hip): launch_sweep_small / launch_sweep_pair hand a launch with gnvp_only set to
+    // trajectory_gnvp_kernel + vjp_sum_kernel INSTEAD of the sweep: behind the sweep of the same members (one control array)
+    // they read the propagators that sweep stored, push the direction hvp_xdot forward, weight the tangents of the read-out
+    // and pull the result back.  The fields that mean the same are the pull-back's and the HVP's: the probes, the
+    // decomposition, the rows and the groups' sums (vjp_*; vjp_ybar / vjp_xbar are not read, vjp_only stays 0), the general
+    // flow's states (vjp_xs), the direction (hvp_xdot); the groups' sums go into vjp_G by a vjp_only = 2 launch.  (Appended.)
+    int32_t gnvp_only;
+    int32_t gnvp_w_per_member;      // 0: gnvp_wy is (N + 1, vjp_n, 3), shared; 1: (N + 1, vjp_n, vjp_Etot, 3)
+    const double *gnvp_wy;          // the weight blocks of y's entries, planes rr, ri, ii slowest; nullable (zero)
+    const double *gnvp_wf;          // (vjp_Etot) the weights of the final states; nullable (zero)
+    double2 *gnvp_src;              // the costate's source per slice, chunk-major like props with n m elements per slice
 };
 // A member's image record: what the lane-pair sweep's prologue puts into LDS, laid out as the LDS holds it.
 //   [0, 2 PS)        both parity images of A', B'_c, B'_c^T, Xi, Xt, Xi Xt' (every mode but the anti-Hermitian sweep), pads zero
@@ -388,6 +399,8 @@ hipError_t launch_vjp_rows_sum(const SweepParams &p, hipStream_t stream);
 constexpr bool hvp_walks_back(int n, int m) { return !(n == 3 && m == 3); }
 // hvp.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::hvp_only) only
 hipError_t run_trajectory_hvp(int n, const SweepParams &p, hipStream_t stream);
+// gnvp.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::gnvp_only) only
+hipError_t run_trajectory_gnvp(int n, const SweepParams &p, hipStream_t stream);
 // traj_mean.hip; reached through launch_copy (DoneSignal::basis, BasisOp::mean) only
 hipError_t run_traj_mean(const MeanOp &op, hipStream_t stream);
 // traj_frechet.hip; reached through run_trajectory_vjp (dir = false) / run_trajectory_jvp (dir = true) only

@@ -1,5 +1,6 @@
 // traj_chunk.hpp -- the chunk-scan skeleton of the kernels that run behind the small-n sweeps on the propagators those left
-// in the workspace: running_cost_kernel, observe_kernel, trajectory_vjp_kernel, trajectory_jvp_kernel, trajectory_hvp_kernel.
+// in the workspace: running_cost_kernel, observe_kernel, trajectory_vjp_kernel, trajectory_jvp_kernel, trajectory_hvp_kernel,
+// trajectory_gnvp_kernel.
 //
 // The workspace is chunk-major: element e of slice t = c S + jj of row k at ((k S + jj) n^2 + e) CH + c.  Every kernel of the
 // family runs one workgroup per row and one lane per time chunk of S consecutive slices, so every workspace access is
@@ -13,10 +14,12 @@
 //   traj_walk_store      general flow: the forward walk over the chunk that stores the states
 //   traj_affine_suffix   exclusive suffix scan of the affine maps z -> Q_c' z + b_c  (the pull-backs: costates)
 //   traj_probe_trace     tr(O' D)
-// The forward twin of traj_affine_suffix, the prefix scan of z -> Q_c z + d_c with one offset per tangent direction, has one
-// user and is written out in it (trajectory_jvp_kernel, jvp.hip): as a function of this header it compiled to the same
-// arithmetic, but the register allocation of the instances with several directions and m >= 2 columns came out worse (320
-// instead of 235 registers at n = m = 2 with 8 directions: one wave per SIMD instead of two).
+// The forward twin of traj_affine_suffix, the prefix scan of z -> Q_c z + d_c with one offset per tangent direction, is
+// written out in its users: trajectory_jvp_kernel (jvp.hip, DB directions) and, in the one-direction form,
+// trajectory_hvp_kernel (hvp.hip) and trajectory_gnvp_kernel (gnvp.hip).  As a function of this header it compiled to the same
+// arithmetic for the JVP kernel, but the register allocation of the instances with several directions and m >= 2 columns
+// came out worse (320 instead of 235 registers at n = m = 2 with 8 directions: one wave per SIMD instead of two).  A
+// one-direction function for the other two kernels alone was not tried: their copies are hvp.hip's text, line for line.
 // Ragged decompositions: a lane whose chunk starts at or behind N, and the padding lanes behind chunk CH - 1, own no slice
 // (cnt = 0: Q = 1, zero offset); the last chunk may be short.  The scans run wave shuffles in a fixed tree and pass wave totals
 // through the CALLER's __shared__ arrays, combined in wave order: every number has one fixed evaluation order, whatever the

@@ -46,6 +46,7 @@ EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_oper
            "grape_eval", "grape_eval_device", "grape_eval_batch", "grape_eval_batch_device", "grape_eval_fom", "grape_eval_observables",
            "grape_eval_vjp", "grape_eval_observables_device", "grape_eval_vjp_device", "grape_eval_jvp", "grape_eval_jvp_device",
            "grape_eval_jvp_multi", "grape_eval_jvp_multi_device", "grape_eval_hvp", "grape_eval_hvp_device",
+           "grape_eval_gnvp", "grape_eval_gnvp_device",
            "grape_eval_vjp_multi", "grape_eval_vjp_multi_device",
            "grape_eval_observables_mean", "grape_eval_vjp_mean", "grape_eval_jvp_mean",
            "grape_set_trajectory_derivative", "grape_set_running_cost_derivative",
@@ -160,6 +161,8 @@ def load_library():
     L.grape_eval_jvp_multi_device.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
     L.grape_eval_hvp.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.grape_eval_hvp_device.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.grape_eval_gnvp.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp]
+    L.grape_eval_gnvp_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]
     L.grape_eval_observables_mean.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, dp]
     L.grape_eval_vjp_mean.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.grape_eval_jvp_mean.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
@@ -874,6 +877,73 @@ class GrapeEngine:
         self._check(self._lib.grape_eval_hvp(self._h, _p(xf), _p(xdf), n_obs, 1 if per_member else 0, _p(Of), _p(yb), _p(xb),
                                              _p(ybd), _p(xbd), _p(Gd)))
         return np.ascontiguousarray(Gd.T)
+
+    def _gnvp_weights(self, who, w, n_obs, blocks):
+        """(w_per_member, the three planes rr / ri / ii as the library reads them) of observe_gnvp's w"""
+        E, N = self.E, self.N
+        w = np.asarray(w, dtype=np.float64)
+        shared, member = (n_obs, N + 1), (E, n_obs, N + 1)
+        if blocks is not True and w.shape in (shared, member):    # scalar weights: rr = ii = w, ri = 0
+            planes = np.stack([w, np.zeros_like(w), w])
+        elif blocks is not False and w.shape in ((3,) + shared, (3,) + member):
+            planes = w
+        else:
+            raise ValueError(f"{who}: w must be ({n_obs},{N + 1}) or ({E},{n_obs},{N + 1}), or the three planes rr, ri, ii of "
+                             f"either behind a leading axis of 3")
+        return (1 if planes.ndim == 4 else 0), np.ascontiguousarray(planes)
+
+    def observe_gnvp(self, x, xdot, ops, w=None, wf=None, per_member=False, blocks=None):
+        """grape_eval_gnvp: the weighted Gauss-Newton product J' W J xdot of observe() in one trajectory pass --
+        observe_vjp(x, ops, ybar = W ydot, xbar_final = wf Xdot_final) of (ydot, Xdot_final) = observe_jvp(x, xdot, ops,
+        final=True), without either array.  w: real weights of y's entries, (E, n_obs, N+1) or (n_obs, N+1) shared by the
+        members; behind a leading axis of 3 the planes rr, ri, ii of a real symmetric 2x2 block per entry, acting on
+        (Re ydot, Im ydot).  blocks=None infers which from the shape, and an array of y's own shape is scalar weights per member
+        -- with E = 3 that is also the shape of shared planes: blocks=True reads the leading axis of 3 as the planes,
+        blocks=False never does.  wf (E,): the weights of the final
+        states, the Gauss-Newton term of 1/2 wf_k |X_N - T|^2.  Either may be None, not both.  Returns Gn (K, cols) in the
+        coordinates of x (basis and bounds are served), first order in dt, without ensemble weights, penalties, running cost
+        or risk.  The contexts observe_vjp serves, in the first-order trajectory derivative mode (include/grape_hip.h)."""
+        x = np.asarray(x, dtype=np.float64)
+        xd = np.asarray(xdot, dtype=np.float64)
+        if x.shape != (self.K, self._cols):
+            raise ValueError(f"x must be ({self.K},{self._cols})")
+        if xd.shape != x.shape:
+            raise ValueError(f"observe_gnvp: xdot must be ({self.K},{self._cols}), the shape of x")
+        if w is None and wf is None:
+            raise ValueError("observe_gnvp: nothing to weight (w and wf are both None)")
+        if ops is None and w is not None:
+            raise ValueError("observe_gnvp: w needs the probes it belongs to")
+        n_obs, O = self._jvp_probes("observe_gnvp", ops, per_member)
+        Of = None if O is None else _cm(np.swapaxes(O, 0, 1) if per_member else O)
+        wpm, wy = 0, None
+        if w is not None:
+            wpm, wy = self._gnvp_weights("observe_gnvp", w, n_obs, blocks)
+        else:
+            n_obs, Of = 0, None                                   # (probes without weights: nothing of theirs enters)
+        wff = None
+        if wf is not None:
+            wff = np.ascontiguousarray(wf, dtype=np.float64)
+            if wff.shape != (self.E,):
+                raise ValueError(f"observe_gnvp: wf must be ({self.E},)")
+        Gn = np.empty((self._cols, self.K))
+        xf, xdf = np.ascontiguousarray(x.T), np.ascontiguousarray(xd.T)
+        self._check(self._lib.grape_eval_gnvp(self._h, _p(xf), _p(xdf), n_obs, 1 if per_member else 0, _p(Of), wpm, _p(wy), _p(wff),
+                                              _p(Gn)))
+        return np.ascontiguousarray(Gn.T)
+
+    def observe_gnvp_device(self, d_x, d_xdot, n_obs, per_member, d_O, w_per_member, d_wy, d_wf, d_Gn, stream=0):
+        """grape_eval_gnvp_device with raw device pointers, layouts as observe_jvp_device; d_wy f64 (N+1, n_obs, [E,] 3), planes
+        rr, ri, ii slowest, d_wf f64 (E), 0 for zero (not both); d_Gn f64 (K, cols) column-major.  d_x=0: reuse -- along the
+        trajectory the last device form left in the workspace, without a sweep (GrapeError NOT_READY when anything else has
+        touched the context since, or under a member chunk); the other reuse forms may follow.  One call per CG iteration."""
+        n_obs = self._traj_device_args("observe_gnvp_device", 1, n_obs, d_O, d_wy, d_wf, "d_wy and d_wf")
+        if not d_xdot:
+            raise ValueError("observe_gnvp_device: d_xdot is null")
+        if not d_Gn:
+            raise ValueError("observe_gnvp_device: d_Gn is null")
+        self._check(self._lib.grape_eval_gnvp_device(self._h, C.c_void_p(d_x), C.c_void_p(d_xdot), n_obs, 1 if per_member else 0,
+                                                     C.c_void_p(d_O), int(w_per_member), C.c_void_p(d_wy), C.c_void_p(d_wf),
+                                                     C.c_void_p(d_Gn), C.c_void_p(stream)))
 
     def observe_device(self, d_x, n_obs, per_member, d_O, d_y, d_X_final, d_fg=0, stream=0):
         """grape_eval_observables_device with raw device pointers (e.g. torch tensor .data_ptr()), in the library's layouts:
