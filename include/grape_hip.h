@@ -761,7 +761,9 @@ int grape_eval_jvp_multi_device(grape_ctx *ctx, const double *d_x, int32_t n_dir
  * Served: the contexts grape_eval_vjp serves, refused with its reasons first.  Two refusals of this call alone follow them,
  * GRAPE_ERR_UNSUPPORTED: grape_set_bounds in force ("bounds": the saturation's second derivative and the first-order G would
  * enter) and grape_set_trajectory_derivative(GRAPE_TRAJ_EXACT) in force ("trajectory_derivative": a second Frechet derivative
- * would be needed).
+ * would be needed).  They are checked in this order ("bounds" first where both stand), in front of the argument checks and of
+ * the GRAPE_ERR_NOT_READY of a reuse; a device-form call refused by either clears the "trajectory valid" flag like any failed
+ * call of the device forms.
  * GRAPE_ERR_INVALID_ARG: null x, xdot or Gdot; ybar and Xbar_final both NULL; n_obs outside 0..16; n_obs = 0 with a non-NULL
  * ybar or ybar_dot; n_obs > 0 with a NULL O; per_member other than 0 or 1; a non-finite entry of a host array ("not finite").
  * Before grape_set_operators: GRAPE_ERR_NOT_READY.  After any refusal the context evaluates exactly as before. */
