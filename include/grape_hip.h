@@ -839,6 +839,62 @@ int grape_eval_gnvp_device(grape_ctx *ctx, const double *d_x, const double *d_xd
                            const double *d_O, int32_t w_per_member, const double *d_wy, const double *d_wf, double *d_Gn,
                            void *stream);
 
+/* ABI v8 (additive).  grape_gn_step: one Levenberg-Marquardt step of the least-squares trajectory loss
+ *   L(x) = 1/2 sum_{s,j,k} r' W r + 1/2 sum_k wf_k |X_{k,N} - T_k|^2 ,   r = y - y_target split into (Re, Im)
+ * solved on the device: its loss, its gradient g and the damped Gauss-Newton step p of (J' W J + lambda 1) p = -g from ONE
+ * sweep and ONE upload of everything; the CG iterations run along the stored trajectory with their vectors and scalars in
+ * device memory. */
+typedef struct grape_gn_options {
+    double  lambda;        /* damping, finite and >= 0: the system is (J' W J + lambda 1) p = -g in the coordinates of x */
+    double  cg_rtol;       /* stop when |r|_2 <= cg_rtol |g|_2 (CG's own recurrence residual); < 0 = 1e-10; 0 = never */
+    int32_t cg_max_iter;   /* operator applications at most; 0 = loss and gradient only (p = 0); < 0 invalid */
+    int32_t reserved;      /* must be 0 */
+} grape_gn_options;
+
+typedef struct grape_gn_result {
+    double  loss;          /* L(x) */
+    double  g_norm;        /* |g|_2 */
+    double  g_inf;         /* |g|_inf */
+    double  residual;      /* |r|_2 of the recurrence at exit */
+    double  p_norm;        /* |p|_2 */
+    double  predicted;     /* -g'p - p'Hp/2 with Hp = Ap - lambda p, Ap accumulated from CG's own products */
+    int32_t cg_iterations; /* operator applications that updated the state */
+    int32_t status;        /* 0 converged, 1 iteration limit, 2 direction without positive curvature (also: NaN), 3 g = 0 */
+} grape_gn_result;
+
+/*   x, n_obs, per_member, O, w_per_member, wy, wf   exactly as in grape_eval_gnvp, the planes rr, ri, ii of wy included
+ *   y_target        host c128 (N+1, n_obs, E) column-major, y's layout; it comes with wy or not at all
+ *   Xf_target       host c128 (n, m, E) column-major, X_final's layout; it comes with wf or not at all.  One pair at least
+ *   p, g            host f64 (K, N), or (K, M) in parameter mode: the shape and coordinates of grape_eval_vjp's G; g may be NULL
+ * g is what grape_eval_vjp(ybar = W r, Xbar_final = wf (X_N - T)) returns, the cotangent
+ * c = (w_rr Re r + w_ri Im r) + i (w_ri Re r + w_ii Im r) as in grape_eval_gnvp; with unit weights bit for bit.  The operator is
+ * grape_eval_gnvp's, first order in dt; bounds and a basis are served as they are there.  The iteration is conjugate gradients
+ * from p = 0 with apply(v) = J' W J v + lambda v: the test r.r <= (cg_rtol |g|)^2 stands in front of every application, a
+ * direction d with !(d' apply(d) > 0) ends the solve (status 2) with the state it found.
+ * One call: every check, the host arrays' entries included; one upload; ONE evaluation of x as the context is configured, its
+ * [G, F] discarded; gn_residual_kernel (the read-out with the residual and the weights formed on the device: only the
+ * cotangents and L leave it, y never exists); the pull-back along the stored trajectory; per CG iteration one reuse launch of
+ * trajectory_gnvp_kernel + vjp_sum_kernel and one gn_cg_step_kernel, enqueued in blocks of 4 (GRAPE_GN_CG_BLOCK = 1..64)
+ * between which the host reads the scalars through the bounded wait of every blocking call (GRAPE_EVAL_TIMEOUT_S); launches
+ * behind convergence are no-ops, so p, g and result do not depend on the block size, bit for bit.  Every sum has one fixed
+ * tree: results are bitwise reproducible; a standing running cost, penalties or risk do not change a bit; an eval -> gn_step
+ * -> eval sequence returns the first evaluation's bits.  The scratch (the targets, the cotangents, the CG vectors, the record)
+ * is allocated on first use and counted in grape_info.workspace_bytes.  Blocking; the "trajectory valid" flag of the device
+ * forms is left clear.
+ * Refused with grape_eval_gnvp's refusals first, in its order and words ("trajectory_derivative" under GRAPE_TRAJ_EXACT
+ * included); then GRAPE_ERR_UNSUPPORTED on a member-chunked context ("member_chunk": the iterations run along ONE stored
+ * trajectory).  GRAPE_ERR_INVALID_ARG: null x, p, result or opts; wy without y_target or the reverse, wf without Xf_target or
+ * the reverse, neither pair; lambda negative or not finite; cg_rtol not finite; cg_max_iter < 0; reserved != 0; n_obs,
+ * per_member, w_per_member out of range as in grape_eval_gnvp; a non-finite entry of a host array other than x ("not
+ * finite").  Before grape_set_operators: GRAPE_ERR_NOT_READY.  After any refusal the context evaluates exactly as before.  A
+ * non-finite x is not refused: the call returns GRAPE_OK with status = 2, loss = NaN and p = 0.
+ * Not served (refused as above): a device-pointer form, member-chunked contexts, the exact trajectory derivative, n >= 5, the
+ * sandwich types. */
+int grape_gn_step(grape_ctx *ctx, const double *x, int32_t n_obs, int32_t per_member, const double *O,
+                  const double *y_target, int32_t w_per_member, const double *wy,
+                  const double *Xf_target, const double *wf,
+                  const grape_gn_options *opts, double *p, double *g, grape_gn_result *result);
+
 /* ABI v8 (additive).  The ensemble-averaged host forms of the trajectory read-out, its pull-back and its push-forward: the
  * member axis of y / ybar / ydot never crosses the bus.  What an experiment on an inhomogeneously broadened ensemble measures
  * is sum_k v_k y[k]; a loss on it has the cotangent ybar[k] = v_k ybar_mean, ONE block broadcast over the members.

@@ -398,6 +398,70 @@ function observables_gnvp_device(ctx::GrapeContext, d_x::Ptr{Cvoid}, d_xdot::Ptr
     ctx
 end
 
+# struct grape_gn_options / grape_gn_result (include/grape_hip.h) -- field order and types must match exactly
+struct GrapeGnOptions
+    lambda::Float64
+    cg_rtol::Float64
+    cg_max_iter::Int32
+    reserved::Int32
+end
+
+struct GrapeGnResult
+    loss::Float64
+    g_norm::Float64
+    g_inf::Float64
+    residual::Float64
+    p_norm::Float64
+    predicted::Float64
+    cg_iterations::Int32
+    status::Int32
+end
+
+# grape_gn_step: one Levenberg-Marquardt step of L = 1/2 sum r' W r + 1/2 sum_k wf_k |X_N - Xf_target|^2, r = y - y_target,
+# solved on the device: one sweep, one upload, the CG iterations on (J' W J + lambda 1) p = -g along the stored trajectory.
+# O, wy, wf as in `observables_gnvp`; y_target (N+1, n_obs, E) comes with wy, Xf_target (n, m, E) with wf, one pair at least.
+# Returns (p, g, result::GrapeGnResult) with p, g (K, N).  (Written, NOT executed, like `observables_gnvp`; the Python binding
+# makes the same call and is tested on the GPU.)
+function gn_step(ctx::GrapeContext, x::Matrix{Float64}, O::Union{Nothing,Array{ComplexF64}},
+                 y_target::Union{Nothing,Array{ComplexF64,3}}, wy::Union{Nothing,Array{Float64}},
+                 Xf_target::Union{Nothing,Array{ComplexF64,3}}, wf::Union{Nothing,Vector{Float64}};
+                 lambda::Float64 = 0.0, cg_iter::Integer = 20, cg_rtol::Float64 = 1e-10)
+    size(x) == (ctx.K, ctx.N) || throw(DimensionMismatch("x must be (n_controls, n_slices)"))
+    (wy === nothing) == (y_target === nothing) || throw(ArgumentError("gn_step: wy and y_target come together or not at all"))
+    (wf === nothing) == (Xf_target === nothing) || throw(ArgumentError("gn_step: wf and Xf_target come together or not at all"))
+    (wy === nothing && wf === nothing) && throw(ArgumentError("gn_step: nothing to fit"))
+    n_obs, pm, wpm = 0, Int32(0), Int32(0)
+    if wy !== nothing
+        O === nothing && throw(ArgumentError("gn_step: y_target needs the probes it belongs to"))
+        n_obs = size(O, ndims(O))
+        (ndims(O) == 3 && size(O) == (ctx.n, ctx.m, n_obs)) || (ndims(O) == 4 && size(O) == (ctx.n, ctx.m, ctx.E, n_obs)) ||
+            throw(DimensionMismatch("O must be (n, m, n_obs) or (n, m, E, n_obs) with the context's n, m and E"))
+        1 <= n_obs <= 16 || throw(ArgumentError("gn_step: 1 to 16 probes"))
+        size(wy) == (ctx.N + 1, n_obs, 3) || size(wy) == (ctx.N + 1, n_obs, ctx.E, 3) ||
+            throw(DimensionMismatch("wy must be (N+1, n_obs, 3) or (N+1, n_obs, E, 3)"))
+        size(y_target) == (ctx.N + 1, n_obs, ctx.E) || throw(DimensionMismatch("y_target must be (N+1, n_obs, E)"))
+        pm, wpm = Int32(ndims(O) == 4 ? 1 : 0), Int32(ndims(wy) == 4 ? 1 : 0)
+    end
+    if wf !== nothing
+        length(wf) == ctx.E || throw(DimensionMismatch("wf must have one entry per member"))
+        size(Xf_target) == (ctx.n, ctx.m, ctx.E) || throw(DimensionMismatch("Xf_target must be (n, m, E)"))
+    end
+    p_O = wy === nothing ? Ptr{ComplexF64}(C_NULL) : pointer(O)
+    p_yt = wy === nothing ? Ptr{ComplexF64}(C_NULL) : pointer(y_target)
+    p_wy = wy === nothing ? Ptr{Float64}(C_NULL) : pointer(wy)
+    p_xt = wf === nothing ? Ptr{ComplexF64}(C_NULL) : pointer(Xf_target)
+    p_wf = wf === nothing ? Ptr{Float64}(C_NULL) : pointer(wf)
+    opts = Ref(GrapeGnOptions(lambda, cg_rtol, Int32(cg_iter), Int32(0)))
+    res = Ref(GrapeGnResult(0.0, 0.0, 0.0, 0.0, 0.0, 0.0, Int32(0), Int32(0)))
+    p = Matrix{Float64}(undef, ctx.K, ctx.N)
+    g = Matrix{Float64}(undef, ctx.K, ctx.N)
+    GC.@preserve x O y_target wy Xf_target wf p g check(ctx, ccall((:grape_gn_step, libgrape), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{ComplexF64}, Ptr{ComplexF64}, Int32, Ptr{Float64}, Ptr{ComplexF64}, Ptr{Float64},
+         Ref{GrapeGnOptions}, Ptr{Float64}, Ptr{Float64}, Ref{GrapeGnResult}),
+        ctx.handle, x, Int32(n_obs), pm, p_O, p_yt, wpm, p_wy, p_xt, p_wf, opts, p, g, res))
+    p, g, res[]
+end
+
 # grape_eval_jvp_multi: `observables_jvp` for a block of directions behind ONE evaluation of x.  xdot is (K, N, n_dir) (the
 # direction index slowest, 1 <= n_dir <= 8); ydot (N+1, n_obs, E, n_dir) and Xdf (n, m, E, n_dir) are written in place and
 # returned.  Slice [:, :, :, d] of either is bit for bit what `observables_jvp` returns for xdot[:, :, d].  (Written, NOT

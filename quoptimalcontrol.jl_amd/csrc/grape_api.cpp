@@ -283,6 +283,15 @@ struct grape_ctx {
     double2 *d_gnvp_src = nullptr;
     size_t gnvp_wy_bytes = 0, gnvp_wf_bytes = 0, gnvp_src_bytes = 0;
     const double *gnvp_wy_call = nullptr, *gnvp_wf_call = nullptr;
+    // grape_gn_step (gn_step.hip): the loss, its gradient and the damped Gauss-Newton step from ONE evaluation.  The call is
+    // described by the product's fields above (probes, weights, direction = CG's d, result = H d) and the pull-back's
+    // (d_vjp_ybar / d_vjp_xbar: the cotangents gn_residual_kernel writes); its own are the targets and one block of doubles,
+    // [x | g | p | Ap | r | d | Hd] (KP entries each), the members' shares of L (E) and the record.  The buffers belong to this
+    // blocking entry point alone and only ever grow.
+    double2 *d_gn_yt = nullptr;                // (N + 1, n_obs, E)
+    double2 *d_gn_xt = nullptr;                // (n, m, E)
+    double *d_gn_vec = nullptr;
+    size_t gn_yt_bytes = 0, gn_xt_bytes = 0, gn_vec_bytes = 0;
     // grape_eval_observables_mean / _vjp_mean / _jvp_mean (traj_mean.hip): mean_on is set by the entry point around ONE
     // evaluation with obs_on / jvp_on / vjp_on.  Behind the read-out (push-forward) of the last member block the member
     // reduction sums the host form's full-size arrays over the members into d_mean_io; in front of a pull-back the
@@ -710,6 +719,7 @@ static void free_all(grape_ctx *c)
     (void)hipFree(c->d_jvp_O); (void)hipFree(c->d_jvp_xdot); (void)hipFree(c->d_jvp_xphys); (void)hipFree(c->d_jvp_ydot); (void)hipFree(c->d_jvp_xf);
     (void)hipFree(c->d_hvp_ybd); (void)hipFree(c->d_hvp_xbd); (void)hipFree(c->d_hvp_xs);
     (void)hipFree(c->d_gnvp_wy); (void)hipFree(c->d_gnvp_wf); (void)hipFree(c->d_gnvp_src);
+    (void)hipFree(c->d_gn_yt); (void)hipFree(c->d_gn_xt); (void)hipFree(c->d_gn_vec);
     (void)hipFree(c->d_mean_v); (void)hipFree(c->d_mean_io); (void)hipFree(c->d_mean_part);
     (void)hipFree(c->d_basis_phi); (void)hipFree(c->d_basis_x0);
     (void)hipFree(c->d_bounds); (void)hipFree(c->d_slope);
@@ -4925,6 +4935,228 @@ extern "C" int grape_eval_gnvp_device(grape_ctx *c, const double *d_x, const dou
     HIP_TRY(c, hipEventRecord(c->ev_dev, st));
     c->dev_pending = true;
     c->traj_valid = !chunked(c);
+    return GRAPE_OK;
+}
+
+// ---- grape_gn_step: the loss, its gradient and the damped Gauss-Newton step from one evaluation ---------------------------------
+// iterations the host enqueues between two looks at the record: GRAPE_GN_CG_BLOCK = 1..64, else 4
+static int gn_cg_block()
+{
+    const char *v = std::getenv("GRAPE_GN_CG_BLOCK");
+    if (!v || !v[0]) return 4;
+    const long b = std::strtol(v, nullptr, 10);
+    return b >= 1 && b <= 64 ? (int)b : 4;
+}
+
+// one kernel of gn_step.hip: the launch that carries the call's record INSTEAD of a sweep (SweepParams::gn)
+static int gn_launch(grape_ctx *c, SweepParams s, const grape::GnOp &op, int mode, hipStream_t stream)
+{
+    s.gn = &op;
+    HIP_TRY(c, launch_small_family(c, 0, mode, s, stream));
+    return GRAPE_OK;
+}
+
+extern "C" int grape_gn_step(grape_ctx *c, const double *x, int32_t n_obs, int32_t per_member, const double *O,
+                             const double *y_target, int32_t w_per_member, const double *wy, const double *Xf_target,
+                             const double *wf, const grape_gn_options *opts, double *p, double *g, grape_gn_result *result)
+{
+    DeviceGuard guard;
+    if (!c) return fail(nullptr, GRAPE_ERR_INVALID_ARG, "grape_gn_step: null context");
+    const char *who = "grape_gn_step";
+    c->traj_valid = false;
+    // grape_eval_gnvp's refusals, in its order and words (the direction and the product are this call's own: never null)
+    if (int rc0 = gnvp_check(c, who, x, true, c, n_obs, per_member, O, w_per_member, wy, wf, c)) return rc0;
+    if (chunked(c))
+        return fail(c, GRAPE_ERR_UNSUPPORTED, std::string(who) + ": the context is under member_chunk (its workspace holds one block of "
+                                              "members): the iterations run along ONE stored trajectory");
+    if (!p) return fail(c, GRAPE_ERR_INVALID_ARG, std::string(who) + ": p is null");
+    if (!result) return fail(c, GRAPE_ERR_INVALID_ARG, std::string(who) + ": result is null");
+    if (!opts) return fail(c, GRAPE_ERR_INVALID_ARG, std::string(who) + ": opts is null");
+    if ((wy != nullptr) != (y_target != nullptr))
+        return fail(c, GRAPE_ERR_INVALID_ARG, std::string(who) + ": wy and y_target come together or not at all");
+    if ((wf != nullptr) != (Xf_target != nullptr))
+        return fail(c, GRAPE_ERR_INVALID_ARG, std::string(who) + ": wf and Xf_target come together or not at all");
+    if (!std::isfinite(opts->lambda) || opts->lambda < 0.0)
+        return fail(c, GRAPE_ERR_INVALID_ARG, std::string(who) + ": lambda = " + std::to_string(opts->lambda) + " (must be finite and >= 0)");
+    if (!std::isfinite(opts->cg_rtol))
+        return fail(c, GRAPE_ERR_INVALID_ARG, std::string(who) + ": cg_rtol is not finite");
+    if (opts->cg_max_iter < 0)
+        return fail(c, GRAPE_ERR_INVALID_ARG, std::string(who) + ": cg_max_iter = " + std::to_string(opts->cg_max_iter) + " (must be >= 0)");
+    if (opts->reserved != 0) return fail(c, GRAPE_ERR_INVALID_ARG, std::string(who) + ": reserved must be 0");
+    const size_t n = (size_t)c->cfg.n, m = (size_t)c->m, E = (size_t)c->cfg.n_ensemble, N = (size_t)c->cfg.n_slices;
+    const size_t n_O = n * m * (per_member ? E : 1) * (size_t)n_obs, n_y = (N + 1) * (size_t)n_obs * E, n_X = n * m * E;
+    const size_t n_w = (N + 1) * (size_t)n_obs * (w_per_member ? E : 1) * 3;
+    const size_t kn = KN(c), kp = KP(c);
+    int rc = check_finite(c, O, 2 * n_O, who, "O", 2);
+    if (rc) return rc;
+    if (wy) rc = check_finite(c, wy, n_w, who, "wy");
+    if (rc) return rc;
+    if (wy) rc = check_finite(c, y_target, 2 * n_y, who, "y_target", 2);
+    if (rc) return rc;
+    if (wf) rc = check_finite(c, wf, E, who, "wf");
+    if (rc) return rc;
+    if (wf) rc = check_finite(c, Xf_target, 2 * n_X, who, "Xf_target", 2);
+    if (rc) return rc;
+    // the product's and the pull-back's buffers are the device forms' too, and those do not block: nothing is in flight from here on
+    rc = drain(c, c);
+    if (rc) return rc;
+    if (!c->lds_cap) HIP_TRY(c, hipDeviceGetAttribute(&c->lds_cap, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device));
+    // ---- the one upload
+    if (wy) {
+        rc = grow(c, &c->d_vjp_O, &c->vjp_O_bytes, sizeof(double2) * n_O, who, "the probes");
+        if (rc) return rc;
+        rc = grow(c, &c->d_gnvp_wy, &c->gnvp_wy_bytes, sizeof(double) * n_w, who, "the weights of the expectation values");
+        if (rc) return rc;
+        rc = grow(c, &c->d_gn_yt, &c->gn_yt_bytes, sizeof(double2) * n_y, who, "the targets of the expectation values");
+        if (rc) return rc;
+        rc = grow(c, &c->d_vjp_ybar, &c->vjp_ybar_bytes, sizeof(double2) * n_y, who, "the cotangents of the expectation values");
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpy(c->d_vjp_O, O, sizeof(double2) * n_O, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(c->d_gnvp_wy, wy, sizeof(double) * n_w, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(c->d_gn_yt, y_target, sizeof(double2) * n_y, hipMemcpyHostToDevice));
+    }
+    if (wf) {
+        rc = grow(c, &c->d_gnvp_wf, &c->gnvp_wf_bytes, sizeof(double) * E, who, "the weights of the final states");
+        if (rc) return rc;
+        rc = grow(c, &c->d_gn_xt, &c->gn_xt_bytes, sizeof(double2) * n_X, who, "the targets of the final states");
+        if (rc) return rc;
+        rc = grow(c, &c->d_vjp_xbar, &c->vjp_xbar_bytes, sizeof(double2) * n_X, who, "the cotangents of the final states");
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpy(c->d_gnvp_wf, wf, sizeof(double) * E, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(c->d_gn_xt, Xf_target, sizeof(double2) * n_X, hipMemcpyHostToDevice));
+    }
+    rc = grow(c, &c->d_gn_vec, &c->gn_vec_bytes, sizeof(double) * (7 * kp + E) + sizeof(grape::GnRecord), who,
+              "the vectors and the record of the CG iteration");
+    if (rc) return rc;
+    double *const d_x = c->d_gn_vec, *const d_g = d_x + kp, *const d_p = d_g + kp, *const d_Ap = d_p + kp, *const d_r = d_Ap + kp,
+                 *const d_d = d_r + kp, *const d_Hd = d_d + kp, *const d_ml = d_Hd + kp;
+    grape::GnRecord *const d_rec = (grape::GnRecord *)(d_ml + E);
+    if (pulse_map(c)) {
+        rc = grow(c, &c->d_jvp_xphys, &c->jvp_xphys_bytes, sizeof(double) * kn, who, "the direction of the physical pulse");
+        if (rc) return rc;
+    }
+    rc = vjp_grow_sums(c, who, 1, true);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpy(d_x, x, sizeof(double) * kp, hipMemcpyHostToDevice));
+    // ---- the one evaluation, as the context is configured (its [G, F] are not wanted); the propagators stay in the workspace
+    hipStream_t st = c->stream;
+    rc = traj_device_eval(c, d_x, pulse_map(c) ? c->d_vjp_out : c->d_fg, st);
+    c->traj_valid = false;
+    if (rc) return rc;
+    rc = vjp_rows_ensure(c);                                 // (the rows, and the states of the general flow)
+    if (rc) return rc;
+    rc = gnvp_ensure(c, who);
+    if (rc) return rc;
+    const int mode = c->unitary ? 2 : (c->d_costates ? 1 : 0);
+    SweepParams q = sweep_params(c, nullptr, 1);
+    q.props = c->d_props;
+    grape::BasisOp proj;                                     // a summed physical row -> the coordinates of x (no F slot)
+    if (pulse_map(c)) {
+        proj = basis_op(c, true, 1);
+        proj.no_f = 1;
+    }
+    grape::DoneSignal dproj;
+    dproj.basis = &proj;
+    grape::GnOp op;
+    op.Q = (int32_t)kp;
+    op.E = (int32_t)E;
+    op.max_iter = opts->cg_max_iter;
+    op.lambda = opts->lambda;
+    op.rtol = opts->cg_rtol < 0.0 ? 1e-10 : opts->cg_rtol;
+    op.g = d_g;
+    op.Hd = d_Hd;
+    op.p = d_p;
+    op.Ap = d_Ap;
+    op.r = d_r;
+    op.d = d_d;
+    op.rec = d_rec;
+    op.member_loss = d_ml;
+    c->vjp_n = n_obs;
+    c->vjp_per_member = per_member;
+    c->vjp_O_call = c->d_vjp_O;
+    c->gnvp_w_per_member = w_per_member;
+    c->gnvp_wy_call = wy ? c->d_gnvp_wy : nullptr;
+    c->gnvp_wf_call = wf ? c->d_gnvp_wf : nullptr;
+    {
+        KernelLogScope log_scope(&c->kernel_log, true);
+        // ---- the residuals: the cotangents and the members' shares of L
+        SweepParams o = q;
+        o.obs_n = wy ? n_obs : 0;
+        o.obs_m = c->m;
+        o.obs_per_member = per_member;
+        o.obs_CH = c->CH;
+        o.obs_Etot = c->cfg.n_ensemble;
+        o.obs_E0 = 0;
+        o.obs_O = c->d_vjp_O;
+        o.gnvp_w_per_member = w_per_member;
+        o.gnvp_wy = c->gnvp_wy_call;
+        o.gnvp_wf = c->gnvp_wf_call;
+        op.kind = 1;
+        op.y_target = wy ? c->d_gn_yt : nullptr;
+        op.xf_target = wf ? c->d_gn_xt : nullptr;
+        op.ybar = wy ? c->d_vjp_ybar : nullptr;
+        op.xbar = wf ? c->d_vjp_xbar : nullptr;
+        rc = gn_launch(c, o, op, mode, st);
+        if (rc) return rc;
+        // ---- the pull-back of the cotangents along the stored trajectory: g
+        c->vjp_has_y = wy != nullptr;
+        c->vjp_has_x = wf != nullptr;
+        c->vjp_ybar_call = c->d_vjp_ybar;
+        c->vjp_xbar_call = c->d_vjp_xbar;
+        c->vjp_G_call = pulse_map(c) ? c->d_vjp_g : d_g;
+        c->vjp_staged = wy ? traj_staged_bytes(c, n_obs, true) : 0;
+        SweepParams v = vjp_params(c, q, 0);
+        HIP_TRY(c, launch_small_family(c, 0, mode, v, st));
+        v.vjp_only = 2;
+        HIP_TRY(c, launch_small_family(c, 0, mode, v, st));
+        if (pulse_map(c)) HIP_TRY(c, grape::launch_copy(c->d_vjp_g, d_g, (int)kp, st, dproj));
+        // ---- r = d = -g, p = Ap = 0, L and the scalars
+        op.kind = 2;
+        rc = gn_launch(c, q, op, mode, st);
+        if (rc) return rc;
+    }
+    // ---- the iterations: the product's reuse launch on d, then one update; the host looks at the record between blocks
+    c->vjp_has_y = false;
+    c->vjp_has_x = false;
+    c->jvp_xdot_call = d_d;
+    c->vjp_G_call = pulse_map(c) ? c->d_vjp_g : d_Hd;
+    c->vjp_staged = 0;
+    grape::GnRecord rec;
+    const int block = gn_cg_block();
+    for (int it = 0;; ++it) {
+        const bool more = it < opts->cg_max_iter;
+        if (more) {
+            KernelLogScope log_scope(it == 0 ? &c->kernel_log : nullptr, true);        // (the names of ONE iteration)
+            if (pulse_map(c)) {
+                rc = jvp_tangent_map(c, st);
+                if (rc) return rc;
+            }
+            rc = gnvp_launch(c, q, 0, true, mode, st);
+            if (rc) return rc;
+            if (pulse_map(c)) HIP_TRY(c, grape::launch_copy(c->d_vjp_g, d_Hd, (int)kp, st, dproj));
+            op.kind = 3;
+            rc = gn_launch(c, q, op, mode, st);
+            if (rc) return rc;
+        }
+        if (more && (it + 1) % block != 0 && it + 1 < opts->cg_max_iter) continue;
+        op.kind = 4;
+        rc = gn_launch(c, q, op, mode, st);
+        if (rc) return rc;
+        rc = wait_stream(c, st);
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpy(&rec, d_rec, sizeof(rec), hipMemcpyDeviceToHost));
+        if (rec.done || !more) break;
+    }
+    HIP_TRY(c, hipMemcpy(p, d_p, sizeof(double) * kp, hipMemcpyDeviceToHost));
+    if (g) HIP_TRY(c, hipMemcpy(g, d_g, sizeof(double) * kp, hipMemcpyDeviceToHost));
+    result->loss = rec.loss;
+    result->g_norm = rec.g_norm;
+    result->g_inf = rec.g_inf;
+    result->residual = rec.residual;
+    result->p_norm = rec.p_norm;
+    result->predicted = rec.predicted;
+    result->cg_iterations = rec.iter;
+    result->status = rec.status;
     return GRAPE_OK;
 }
 

@@ -308,6 +308,36 @@ struct SweepParams {
     const double *gnvp_wy;          // the weight blocks of y's entries, planes rr, ri, ii slowest; nullable (zero)
     const double *gnvp_wf;          // (vjp_Etot) the weights of the final states; nullable (zero)
     double2 *gnvp_src;              // the costate's source per slice, chunk-major like props with n m elements per slice
+    // grape_gn_step (gn_step.hip): HOST pointer to the record of the call's own, never dereferenced on the device.  Non-null:
+    // launch_sweep_small / launch_sweep_pair hand the launch to run_gn_step INSTEAD of the sweep (GnOp::kind says which of
+    // its kernels).  The residual kernel is described by the read-out's fields (obs_*) and the weights of the product
+    // (gnvp_wy, gnvp_wf, gnvp_w_per_member).  nullptr: everything above.  (Appended.)
+    const struct GnOp *gn;
+};
+// grape_gn_step: the scalars of one call's CG iteration, in device memory; the host reads it between blocks of iterations
+struct GnRecord {
+    double loss;                    // L(x)
+    double g_norm, g_inf;           // |g|_2, |g|_inf
+    double rr, stop;                // the recurrence's r.r and the threshold rtol^2 |g|^2
+    double residual, p_norm, predicted;     // written by gn_cg_finish_kernel from the vectors as they stand
+    int32_t iter;                   // operator applications that updated the state
+    int32_t status;                 // grape_gn_result::status; meaningful once done
+    int32_t done;                   // set: gn_cg_step_kernel changes nothing any more
+    int32_t pad;
+};
+struct GnOp {
+    int32_t kind = 0;               // 1: gn_residual_kernel, 2: gn_cg_init_kernel, 3: gn_cg_step_kernel, 4: gn_cg_finish_kernel
+    // 1: the targets (null: that term is absent), the cotangents it writes and the members' shares of L
+    const double2 *y_target = nullptr;      // (N + 1, obs_n, obs_Etot)
+    const double2 *xf_target = nullptr;     // (n, m, obs_Etot)
+    double2 *ybar = nullptr, *xbar = nullptr;
+    double *member_loss = nullptr;          // (obs_Etot)
+    // 2, 3, 4: the vectors of Q entries each and the record
+    int32_t Q = 0, E = 0, max_iter = 0;
+    double lambda = 0.0, rtol = 0.0;
+    const double *g = nullptr, *Hd = nullptr;
+    double *p = nullptr, *Ap = nullptr, *r = nullptr, *d = nullptr;
+    GnRecord *rec = nullptr;
 };
 // A member's image record: what the lane-pair sweep's prologue puts into LDS, laid out as the LDS holds it.
 //   [0, 2 PS)        both parity images of A', B'_c, B'_c^T, Xi, Xt, Xi Xt' (every mode but the anti-Hermitian sweep), pads zero
@@ -401,6 +431,8 @@ constexpr bool hvp_walks_back(int n, int m) { return !(n == 3 && m == 3); }
 hipError_t run_trajectory_hvp(int n, const SweepParams &p, hipStream_t stream);
 // gnvp.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::gnvp_only) only
 hipError_t run_trajectory_gnvp(int n, const SweepParams &p, hipStream_t stream);
+// gn_step.hip; reached through launch_sweep_small / launch_sweep_pair (SweepParams::gn) only
+hipError_t run_gn_step(int n, const SweepParams &p, hipStream_t stream);
 // traj_mean.hip; reached through launch_copy (DoneSignal::basis, BasisOp::mean) only
 hipError_t run_traj_mean(const MeanOp &op, hipStream_t stream);
 // traj_frechet.hip; reached through run_trajectory_vjp (dir = false) / run_trajectory_jvp (dir = true) only

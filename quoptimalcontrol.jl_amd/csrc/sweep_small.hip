@@ -629,6 +629,8 @@ hipError_t launch_sweep_small(int n, int sandwich, int mode, const SweepParams &
         return run_trajectory_hvp(n, p, stream);
     if (p.gnvp_only)                                 // grape_eval_gnvp: the kernels behind the sweep (gnvp.hip)
         return run_trajectory_gnvp(n, p, stream);
+    if (p.gn)                                        // grape_gn_step: the kernels of the call's record (gn_step.hip)
+        return run_gn_step(n, p, stream);
     switch (n * 2 + (sandwich ? 1 : 0)) {
     case 4: return launch_ns<2, 0>(mode, p, stream);
     case 5: return launch_ns<2, 1>(mode, p, stream);

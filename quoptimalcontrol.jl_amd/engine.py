@@ -46,7 +46,7 @@ EXPORTS = ["grape_abi_version", "grape_create", "grape_destroy", "grape_set_oper
            "grape_eval", "grape_eval_device", "grape_eval_batch", "grape_eval_batch_device", "grape_eval_fom", "grape_eval_observables",
            "grape_eval_vjp", "grape_eval_observables_device", "grape_eval_vjp_device", "grape_eval_jvp", "grape_eval_jvp_device",
            "grape_eval_jvp_multi", "grape_eval_jvp_multi_device", "grape_eval_hvp", "grape_eval_hvp_device",
-           "grape_eval_gnvp", "grape_eval_gnvp_device",
+           "grape_eval_gnvp", "grape_eval_gnvp_device", "grape_gn_step",
            "grape_eval_vjp_multi", "grape_eval_vjp_multi_device",
            "grape_eval_observables_mean", "grape_eval_vjp_mean", "grape_eval_jvp_mean",
            "grape_set_trajectory_derivative", "grape_set_running_cost_derivative",
@@ -96,6 +96,15 @@ class GrapeLbfgsResult(C.Structure):
     _fields_ = [("minimum", C.c_double), ("g_norm", C.c_double), ("seconds", C.c_double), ("iterations", C.c_int32),
                 ("evaluations", C.c_int32), ("status", C.c_int32), ("probes", C.c_int32),
                 ("line_search", C.c_int32), ("ladder_fallbacks", C.c_int32)]
+
+
+class GrapeGnOptions(C.Structure):
+    _fields_ = [("lambda", C.c_double), ("cg_rtol", C.c_double), ("cg_max_iter", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GrapeGnResult(C.Structure):
+    _fields_ = [("loss", C.c_double), ("g_norm", C.c_double), ("g_inf", C.c_double), ("residual", C.c_double),
+                ("p_norm", C.c_double), ("predicted", C.c_double), ("cg_iterations", C.c_int32), ("status", C.c_int32)]
 
 
 class GrapeCommId(C.Structure):
@@ -163,6 +172,7 @@ def load_library():
     L.grape_eval_hvp_device.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.grape_eval_gnvp.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp]
     L.grape_eval_gnvp_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp]
+    L.grape_gn_step.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp, C.POINTER(GrapeGnOptions), vp, vp, C.POINTER(GrapeGnResult)]
     L.grape_eval_observables_mean.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, dp]
     L.grape_eval_vjp_mean.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.grape_eval_jvp_mean.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
@@ -930,6 +940,56 @@ class GrapeEngine:
         self._check(self._lib.grape_eval_gnvp(self._h, _p(xf), _p(xdf), n_obs, 1 if per_member else 0, _p(Of), wpm, _p(wy), _p(wff),
                                               _p(Gn)))
         return np.ascontiguousarray(Gn.T)
+
+    def gn_step(self, x, ops, y_target=None, w=None, xf_target=None, wf=None, lam=0.0, cg_iter=20, cg_rtol=1e-10, per_member=False,
+                blocks=None):
+        """grape_gn_step: one Levenberg-Marquardt step of L(x) = 1/2 sum r' W r + 1/2 sum_k wf_k |X_N - xf_target|^2
+        (r = observe(x) - y_target) solved on the device -- one sweep, one upload, the CG iterations on
+        (J' W J + lam 1) p = -g along the stored trajectory.  y_target (E, n_obs, N+1) complex with w (None: ones; shaped and
+        inferred exactly as in observe_gnvp) and / or xf_target (E, n, m) with wf (None: ones).  cg_iter: operator
+        applications at most (0: loss and gradient only, p = 0); cg_rtol: stop at |r| <= cg_rtol |g|.  Returns dict(p, g
+        (K, cols) in the coordinates of x, loss, predicted (the model decrease -g'p - p'Hp/2), iterations, status (0 converged,
+        1 iteration limit, 2 no positive curvature / NaN, 3 g = 0), residual, g_norm, g_inf, p_norm)."""
+        x = np.asarray(x, dtype=np.float64)
+        if x.shape != (self.K, self._cols):
+            raise ValueError(f"x must be ({self.K},{self._cols})")
+        n, m, E, N = self.n, self.m, self.E, self.N
+        if y_target is None and xf_target is None:
+            raise ValueError("gn_step: nothing to fit (y_target and xf_target are both None)")
+        if y_target is None and w is not None:
+            raise ValueError("gn_step: w needs the y_target it weights")
+        if xf_target is None and wf is not None:
+            raise ValueError("gn_step: wf needs the xf_target it weights")
+        if ops is None and y_target is not None:
+            raise ValueError("gn_step: y_target needs the probes it belongs to")
+        n_obs, O = self._jvp_probes("gn_step", ops, per_member)
+        Of = None if O is None else _cm(np.swapaxes(O, 0, 1) if per_member else O)
+        wpm, wy, yt = 0, None, None
+        if y_target is not None:
+            yt = np.ascontiguousarray(y_target, dtype=np.complex128)
+            if yt.shape != (E, n_obs, N + 1):
+                raise ValueError(f"gn_step: y_target must be ({E},{n_obs},{N + 1})")
+            wpm, wy = self._gnvp_weights("gn_step", np.ones((n_obs, N + 1)) if w is None else w, n_obs, blocks)
+        else:
+            n_obs, Of = 0, None                                   # (probes without a target: nothing of theirs enters)
+        wff, xt = None, None
+        if xf_target is not None:
+            xt = np.asarray(xf_target, dtype=np.complex128)
+            if xt.shape != (E, n, m):
+                raise ValueError(f"gn_step: xf_target must be ({E},{n},{m})")
+            xt = _cm(xt)
+            wff = np.ones(E) if wf is None else np.ascontiguousarray(wf, dtype=np.float64)
+            if wff.shape != (E,):
+                raise ValueError(f"gn_step: wf must be ({E},)")
+        opts = GrapeGnOptions(float(lam), float(cg_rtol), int(cg_iter), 0)
+        res = GrapeGnResult()
+        p, g = np.empty((self._cols, self.K)), np.empty((self._cols, self.K))
+        xf = np.ascontiguousarray(x.T)
+        self._check(self._lib.grape_gn_step(self._h, _p(xf), n_obs, 1 if per_member else 0, _p(Of), _p(yt), wpm, _p(wy), _p(xt),
+                                            _p(wff), C.byref(opts), _p(p), _p(g), C.byref(res)))
+        return dict(p=np.ascontiguousarray(p.T), g=np.ascontiguousarray(g.T), loss=res.loss, predicted=res.predicted,
+                    iterations=res.cg_iterations, status=res.status, residual=res.residual, g_norm=res.g_norm, g_inf=res.g_inf,
+                    p_norm=res.p_norm)
 
     def observe_gnvp_device(self, d_x, d_xdot, n_obs, per_member, d_O, w_per_member, d_wy, d_wf, d_Gn, stream=0):
         """grape_eval_gnvp_device with raw device pointers, layouts as observe_jvp_device; d_wy f64 (N+1, n_obs, [E,] 3), planes

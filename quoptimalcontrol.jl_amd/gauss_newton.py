@@ -70,13 +70,16 @@ def _cg(apply, b, iters, rtol):
 
 
 def fit_trajectory(engine, x0, ops, y_target=None, w=None, xf_target=None, wf=None, max_iter=20, cg_iter=20, lam0=1e-2,
-                   operator="fused", per_member=False, cg_rtol=1e-10, g_tol=0.0, blocks=None):
+                   operator="fused", per_member=False, cg_rtol=1e-10, g_tol=0.0, blocks=None, solver="host"):
     """Levenberg-Marquardt on L(x) above, from x0.  y_target (E, n_obs, N+1) complex with w (None: ones), and / or xf_target
     (E, n, m) with wf (None: ones).  Per iteration: the gradient from observe_vjp, the step p from cg_iter CG iterations on
     (J' W J + lam 1) p = -g, and the usual rule on the gain ratio rho = (L(x) - L(x + p)) / (model decrease): rho > 0 accepts
     the step (lam / 3 when rho > 0.75, lam * 2 when rho < 0.25), otherwise lam * 4 and the step is retried at the same x.
     operator: "fused" | "composed" (gn_operator), or a callable x -> (v -> J' W J v) of the caller's own.  blocks: how w is
     read (GrapeEngine.observe_gnvp).  One operator application per CG iteration, none besides.
+    solver: "host" runs the CG loop above over the host forms; "device" leaves an iteration to GrapeEngine.gn_step -- one call
+    at x for L, g, p and the model decrease (one sweep, one upload, the CG iterations on the device), one with cg_iter = 0 at
+    x + p for L(x + p) -- under the same accept and lam rules.  It applies the fused operator; a callable operator is refused.
     Returns dict(x, loss, losses (L at x0 and at every accepted iterate), steps (the accepted p), lam, iterations, accepted)."""
     if y_target is None and xf_target is None:
         raise ValueError("fit_trajectory: nothing to fit (y_target and xf_target are both None)")
@@ -92,6 +95,13 @@ def fit_trajectory(engine, x0, ops, y_target=None, w=None, xf_target=None, wf=No
     else:
         wf = None
     probes = ops if w is not None else None
+    if solver == "device":
+        if callable(operator):
+            raise ValueError('fit_trajectory: solver="device" applies the library\'s own operator; a callable operator needs solver="host"')
+        return _fit_on_device(engine, x, probes, y_target, w, xf_target, wf, max_iter, cg_iter, lam0, per_member and probes is not None,
+                              cg_rtol, g_tol, blocks)
+    if solver != "host":
+        raise ValueError('fit_trajectory: solver must be "host" or "device"')
 
     def residuals(xx):
         """(L, ybar, xbar) at xx"""
@@ -124,6 +134,38 @@ def fit_trajectory(engine, x0, ops, y_target=None, w=None, xf_target=None, wf=No
         rho = (L - L_new) / model if model > 0.0 else -1.0
         if rho > 0.0 and L_new < L:
             x, L, ybar, xbar = x + p, L_new, yb_new, xb_new
+            losses.append(L)
+            steps.append(p)
+            lam = lam / 3.0 if rho > 0.75 else (lam * 2.0 if rho < 0.25 else lam)
+        else:
+            lam *= 4.0
+    return dict(x=x, loss=L, losses=losses, steps=steps, lam=lam, iterations=it, accepted=len(steps))
+
+
+def _fit_on_device(engine, x, probes, y_target, w, xf_target, wf, max_iter, cg_iter, lam0, per_member, cg_rtol, g_tol, blocks):
+    """fit_trajectory's loop with GrapeEngine.gn_step in place of residuals / observe_vjp / _cg"""
+    def step(xx, lam, iters):
+        return engine.gn_step(xx, probes, y_target=y_target, w=w, xf_target=xf_target, wf=wf, lam=lam, cg_iter=iters,
+                              cg_rtol=cg_rtol, per_member=per_member, blocks=blocks)
+
+    lam = float(lam0)
+    if max_iter < 1:
+        L = step(x, lam, 0)["loss"]
+        return dict(x=x, loss=L, losses=[L], steps=[], lam=lam, iterations=0, accepted=0)
+    L, losses, steps, it = None, [], [], 0
+    for it in range(1, max_iter + 1):
+        s = step(x, lam, cg_iter)
+        if L is None:                                             # (the first call's own loss: no call for L(x0) alone)
+            L = s["loss"]
+            losses.append(L)
+        if s["g_inf"] <= g_tol:
+            it -= 1
+            break
+        p, model = s["p"], s["predicted"]
+        L_new = step(x + p, lam, 0)["loss"]
+        rho = (L - L_new) / model if model > 0.0 else -1.0
+        if rho > 0.0 and L_new < L:
+            x, L = x + p, L_new
             losses.append(L)
             steps.append(p)
             lam = lam / 3.0 if rho > 0.75 else (lam * 2.0 if rho < 0.25 else lam)
